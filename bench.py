@@ -15,7 +15,15 @@ lengths, which the clustering chain publishes early; the tensors' contents are s
 and the timed region is closed by a full device synchronise, so every step's GPU work is inside it.
 Scenes are sharded by scene id with no data-path collective (weak scaling).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run (no --full) sets up, warms up, times exactly --steps steps in one block and prints
+the headline: `value` (scenes/s), `ms_per_step`, `timed_blocks`; `roofline` and `cpu_baseline` are null.  --dump-outputs DIR
+writes what the last timed step returned (one float32 array per scene, DIR/out_scene<id>.npy, scene ids as in InputSets; the
+inputs are seeded, so two builds can be compared file for file).
+
+--full adds everything else, as before: --repeats 5 timed blocks (median reported), the roofline kernel timed inside them, the
+legs of the same workload with fp32-stored features / bf16 compute / graph replay, the per-pass reports, the training step and
+the CPU baseline (--no-passes / --no-cpu-baseline drop parts of it).  --pipeline follows the same split: one timed block plain,
+with --full five blocks plus per-stage times, the host-draw variant and its CPU baseline.  Extra objects:
   roofline         dominant kernel (the pass over img_feat after the means: k_img_pool for 16-bit features, k_img_scores
                    for fp32): algorithmic bytes per launch / average launch duration, timed with HIP events recorded by
                    the library on the kernel's own stream during the timed steps; `traffic` = HBM bytes per launch from
@@ -80,9 +88,14 @@ def parse():
                          "several forwards in flight).  Measured SLOWER than one lane at every count (profiles/r04_lanes_pipelining.txt): "
                          "the pooling pass needs every CU's register file, the neighbouring forward's small kernels take its slots")
     ap.add_argument("--single-thread", action="store_true", help="with --streams > 1: issue round-robin from ONE host thread")
-    ap.add_argument("--time-kernel", default="img_pass2", help="launch site timed inside the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-passes", action="store_true", help="skip roofline_passes / fp32-feature extras")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated timed blocks, roofline kernel timing, fp32-feature / bf16-compute / "
+                         "graph-replay legs, per-pass reports, training step, CPU baseline (a plain run times --steps steps once)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MiB in all)")
+    ap.add_argument("--time-kernel", default="img_pass2", help="launch site timed inside the timed region (with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-passes", action="store_true", help="with --full: skip roofline_passes / fp32-feature extras")
     ap.add_argument("--cpu-scenes", type=int, default=None, help="scenes in the CPU baseline sample")
     ap.add_argument("--breakdown", action="store_true", help="print per-kernel event timings to stderr")
     ap.add_argument("--setup-forwards", type=int, default=32,
@@ -90,9 +103,10 @@ def parse():
                          "buffers, every input set paged in -- and the device out of its idle state: with 6 of them and the "
                          "driver's --steps 20 --warmup 5 the 5 ms that are timed start 3 ms after the first kernel and read 4 %% "
                          "low, 15.7k vs 16.3-16.5k scenes/s; reported in config.setup_forwards)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="timed blocks of exactly --steps steps each (every block bracketed by barrier + synchronise, MAX over "
-                         "ranks per block); `value` is the MEDIAN block, the spread is reported beside it (timed_blocks)")
+                         "ranks per block); `value` is the MEDIAN block, the spread is reported beside it (timed_blocks).  "
+                         "Default: 1, or 5 with --full")
     ap.add_argument("--time-every", type=int, default=4,
                     help="the roofline kernel is bracketed by HIP events on every n-th measured step (each event record costs "
                          "the stream ~6 us of idle between two kernels; 1 = every step)")
@@ -104,7 +118,10 @@ def parse():
                          "sampling, chained on one stream (proxytransformation_amd/pipeline.py); use with --config cfg4_room")
     ap.add_argument("--share-gpu", action="store_true",
                     help="test aid for 1-GPU boxes: every rank uses cuda:0 (with --backend gloo); numbers are meaningless")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def build_module(cfg, device):
@@ -280,13 +297,42 @@ def cpu_baseline(cfg, sd, n_scenes):
                        f"single-thread C ball query / FPS")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_LIMIT_BYTES):
+    """Write {name: tensor} as out_dir/<name>.npy: floating tensors as float32 (float64 stays float64), integer ones as float64
+    (exact for int32).  If together larger than `budget` bytes, every array keeps the same fraction of its rows, a sample seeded
+    by its name (sorted, identical on every run).  The samples of different arrays are drawn independently, so sampled rows of two
+    arrays that are row-aligned in full (the pipeline's voxel `coordinates` / `features`, a level's points / sampled features) no
+    longer correspond; each file is meant for comparing the same array between two builds."""
+    import zlib
+
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if frac < 1.0 and a.ndim > 0:
+            keep = int(a.shape[0] * frac)
+            rows = np.random.RandomState(zlib.crc32(name.encode())).choice(a.shape[0], keep, replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class InputSets:
     """`nsets` device-resident input sets of B scenes each; set j of rank r holds scenes (j * world + r) * B ..."""
 
     def __init__(self, cfg, B, nsets, rank, world, device, tdt):
         self.sets = []
+        self.scene_ids = []
         for j in range(nsets):
             first = (j * world + rank) * B
+            self.scene_ids.append(list(range(first, first + B)))
             pts, text, mask, img = make_scene_batch(cfg, scene_ids=range(first, first + B))
             img_t = torch.from_numpy(img).to(device)
             self.sets.append(dict(
@@ -456,7 +502,9 @@ def pipeline_bench(args, cfg, device):
     """BASELINE configs[3] ("EmbodiedScan mv-grounding config, full pipeline on 1xMI355X") as ONE chained call per step: B scenes of
     V = 50 synthetic 480 x 640 depth maps -> MultiViewIngest(100 000) -> forward(..., bbox=) with the shipped configuration's weights and
     fp32 features -> module.quantize(0.01) -> MinkResNet's four level coordinate sets -> batch_point_sample on the four 2D-backbone
-    levels (DET:385-448, CFG:105-142).  Prints one JSON line with a `pipeline` object (ms per stage, ms total, scenes/s)."""
+    levels (DET:385-448, CFG:105-142).  Prints one JSON line with a `pipeline` object (ms total, scenes/s; with --full also ms per
+    stage, the call with host pixel draws and the CPU baseline).  --dump-outputs: the last timed call's points, voxel rows / features,
+    level points and sampled image features."""
     import numpy as np
     from proxytransformation_amd.pipeline import MINK_RESNET_STRIDES, GroundingFeaturePrefix
     from proxytransformation_amd.synth import FPN_LEVELS, make_depth_scene
@@ -491,20 +539,33 @@ def pipeline_bench(args, cfg, device):
             torch.cuda.synchronize()
             blocks.append((time.perf_counter() - t0) / args.steps)
         el = sorted(blocks)[len(blocks) // 2]
-        # per-stage times: events on the caller's stream between the stages (they perturb the chain a little: separate calls)
-        stage = {}
-        for i in range(max(5, args.steps // 2)):
-            r_ = pipe(pre, text, feats, time_stages=True)
-            for k, v in r_.stage_ms.items():
-                stage.setdefault(k, []).append(v)
-        stage = {k: round(sorted(v)[len(v) // 2], 4) for k, v in stage.items()}
-        # (b) the same call drawing the pixels itself on the host (np.random.choice per view + per scene, in the reference's order)
-        t0 = time.perf_counter()
-        nb = max(2, args.steps // 4)
-        for i in range(nb):
-            pipe(scenes, text, feats, rng=np.random.RandomState(i))
-        torch.cuda.synchronize()
-        el_draw = (time.perf_counter() - t0) / nb
+        if args.dump_outputs:
+            arrays = {"coordinates": res.coordinates, "features": res.features}
+            for b in range(B):
+                arrays[f"points_scene{b}"] = res.points[b]
+                for li in range(len(res.level_points)):
+                    arrays[f"level{li}_points_scene{b}"] = res.level_points[li][b]
+                    arrays[f"level{li}_imgfeats_scene{b}"] = res.points_imgfeats[b][li]
+            dump_outputs(args.dump_outputs, arrays)
+        stage, draws = None, None
+        if args.full:
+            # per-stage times: events on the caller's stream between the stages (they perturb the chain a little: separate calls)
+            stage = {}
+            for i in range(max(5, args.steps // 2)):
+                r_ = pipe(pre, text, feats, time_stages=True)
+                for k, v in r_.stage_ms.items():
+                    stage.setdefault(k, []).append(v)
+            stage = {k: round(sorted(v)[len(v) // 2], 4) for k, v in stage.items()}
+            # (b) the same call drawing the pixels itself on the host (np.random.choice per view + per scene, in the reference's order)
+            t0 = time.perf_counter()
+            nb = max(2, args.steps // 4)
+            for i in range(nb):
+                pipe(scenes, text, feats, rng=np.random.RandomState(i))
+            torch.cuda.synchronize()
+            el_draw = (time.perf_counter() - t0) / nb
+            draws = dict(ms_total=round(1e3 * el_draw, 3), scenes_per_s=round(B / el_draw, 2),
+                         what="the call draws the PointSample indices itself (np.random.choice per view and per scene on the host, the "
+                              "reference's order): dataloader-worker work in the reference (CFG:146 num_workers=6)")
         mod.check()
     depth_bytes = B * V * 480 * 640 * 2
     img_bytes = sum(int(f.numel()) * 4 for f in feats[-1:])
@@ -520,20 +581,17 @@ def pipeline_bench(args, cfg, device):
                                      f"fp32 features) -> 1 cm voxels -> levels {MINK_RESNET_STRIDES} -> point sampling on "
                                      f"{[c for c, _ in FPN_LEVELS]}-channel maps", scenes_per_gpu=B, img_feat_dtype="f32"),
                 pipeline=dict(ms_total=round(1e3 * el, 4), scenes_per_s=round(B / el, 2), ms_blocks=[round(1e3 * x, 4) for x in blocks],
-                              ms_per_stage=stage,
-                              with_host_pixel_draws=dict(ms_total=round(1e3 * el_draw, 3), scenes_per_s=round(B / el_draw, 2),
-                                                         what="the call draws the PointSample indices itself (np.random.choice per view and "
-                                                              "per scene on the host, the reference's order): dataloader-worker work in the "
-                                                              "reference (CFG:146 num_workers=6)"),
+                              ms_per_stage=stage, with_host_pixel_draws=draws,
                               voxel_rows=nvox, level_rows=lvl_rows, surviving_points=sum(int(o.shape[0]) for o in res.points),
                               what="ms_total: wall clock of `steps` chained calls between device synchronises / steps, pixel draws "
-                                   "precomputed; ms_per_stage: HIP events between the stages of separate calls (median)"),
+                                   "precomputed; ms_per_stage: HIP events between the stages of separate calls (median); "
+                                   "ms_per_stage and with_host_pixel_draws are measured with --full only"),
                 roofline=dict(bound="hbm", kernel="whole chain", achieved=round(alg / el / 1e9, 1), peak=HBM_PEAK_GBS, unit="GB/s",
                               frac=round(alg / el / 1e9 / HBM_PEAK_GBS, 4), traffic=None, algorithmic_bytes_per_launch=alg,
                               what="depth maps (2 B/pixel) + one read of img_features[-1] + the neck's point side (60 N + 40 M K per "
                                    "scene) + voxel pass (12 N in, 28 B per row out) + level points and sampled features written; the "
                                    "chain is ~60 dependent launches: latency-bound, not a bandwidth figure"))
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             from oracle import oracle
             from proxytransformation_amd.pipeline import projection_matrices
@@ -635,8 +693,9 @@ def main():
                 workers = LaneWorkers(mod, inputs, streams)
                 workers.run(0, 4 * len(streams))            # the threads' first calls
         n_out = sum(int(o.shape[0]) for o in outs)
-        lib.ptx_timing_every(max(1, args.time_every))
-        lib.ptx_timing_select(kid)
+        if args.full:
+            lib.ptx_timing_every(max(1, args.time_every))
+            lib.ptx_timing_select(kid)
         # R blocks of exactly K steps; the input-set rotation continues across blocks
         block_s = []
         for r in range(max(1, args.repeats)):
@@ -645,11 +704,17 @@ def main():
         if workers is not None:
             workers.close()
         launches, total_ms = ctypes.c_int(0), ctypes.c_float(0.0)
-        lib.ptx_timing_read(ctypes.byref(launches), ctypes.byref(total_ms))
-        lib.ptx_timing_select(-1)
-        lib.ptx_timing_every(1)
+        if args.full:
+            lib.ptx_timing_read(ctypes.byref(launches), ctypes.byref(total_ms))
+            lib.ptx_timing_select(-1)
+            lib.ptx_timing_every(1)
+        if args.dump_outputs:
+            # `outs` is the last timed step's result: step max(1, repeats) * steps - 1 of the rotation
+            last_set = (max(1, args.repeats) * args.steps - 1) % len(inputs.sets)
+            dump_outputs(args.dump_outputs, {f"out_scene{sid:05d}": o for sid, o in zip(inputs.scene_ids[last_set], outs)},
+                         DUMP_LIMIT_BYTES // world)
 
-        if not args.no_passes:
+        if args.full and not args.no_passes:
             steps2 = max(10, args.steps // 2)
             if tdt is not torch.float32:        # the same workload with fp32-stored image features (non-AMP layout)
                 for i in range(4):
@@ -716,7 +781,7 @@ def main():
                                           value_bf16_compute=round(wide.B / t32["bf16"], 2))
                     extras["passes"].append(passes_report(cfg, wide.B, wide_us, wide.sets[0]["img"].element_size(), pm, t32["fp32"]))
                     del wide
-        if not args.no_passes and rank == 0 and world == 1:
+        if args.full and not args.no_passes and rank == 0 and world == 1:
             with torch.enable_grad():
                 try:
                     extras["train"] = train_step_ms(device)
@@ -806,7 +871,7 @@ def main():
             line["train_step"] = extras["train"]
         if "passes" in extras:
             line["roofline_passes"] = extras["passes"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg, sd, args.cpu_scenes or min(B, 2))
             except Exception as e:                               # the baseline must never sink the GPU number

@@ -5,6 +5,6 @@ cp $L /tmp/real.so
 for rep in 1 2; do
 for v in "$@"; do
   if [ $v = real ]; then cp /tmp/real.so $L; else cp scratch/lab/lib_$v.so $L; fi
-  echo "== $v $(timeout 300 python bench.py --no-cpu-baseline --no-passes $BENCH_ARGS 2>&1 | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"])')"
+  echo "== $v $(timeout 300 python bench.py --full --no-cpu-baseline --no-passes $BENCH_ARGS 2>&1 | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"])')"
 done; done
 cp /tmp/real.so $L

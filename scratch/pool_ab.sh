@@ -9,7 +9,7 @@ for envs in "$@"; do
   ( for kv in $envs; do export "$kv"; done
     timeout 600 python -m pytest $R/tests/test_gpu_parity.py $R/tests/test_gpu_workloads.py -m gpu -x -q -k "img or forward or workload or bench" 2>&1 | tail -2
     for sc in 4 32; do
-      timeout 300 python $R/bench.py --steps 60 --warmup 12 --no-cpu-baseline --no-passes --scenes-per-gpu $sc 2>/dev/null | python -c "
+      timeout 300 python $R/bench.py --full --steps 60 --warmup 12 --no-cpu-baseline --no-passes --scenes-per-gpu $sc 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     l=l.strip()

@@ -7,7 +7,7 @@ bash tools/profile_round.sh r04 > gpurun_out/profile_round_r04.log 2>&1
 O=$R/gpurun_out/r04; F=$R/gpurun_out/r04_final; mkdir -p $F
 bash scratch/final_lines.sh r04 > $F/final_lines.log 2>&1
 # cfg5 as the roofline run BASELINE calls it: 16 scenes per GPU, with the per-pass report
-timeout 900 python bench.py --config cfg5 --scenes-per-gpu 16 --steps 10 --warmup 3 --repeats 3 --setup-forwards 6 --no-cpu-baseline > $F/bench_cfg5_b16.json 2> $F/bench_cfg5_b16.err
+timeout 900 python bench.py --full --config cfg5 --scenes-per-gpu 16 --steps 10 --warmup 3 --repeats 3 --setup-forwards 6 --no-cpu-baseline > $F/bench_cfg5_b16.json 2> $F/bench_cfg5_b16.err
 # N2 / N4 stage timings, the training step's kernel statistics, lanes
 python scratch/vox_time.py > $F/vox_time.txt 2>&1
 python scratch/ingest_time.py 4 > $F/ingest_time.txt 2>&1

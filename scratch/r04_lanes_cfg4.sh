@@ -1,7 +1,7 @@
 #!/bin/bash
 # lanes (several forwards in flight, bench.py --streams) at the shapes whose step is the farthest point sampling
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-run() { echo "== $1: $(timeout 600 python bench.py --no-cpu-baseline --no-passes $2 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); b=d.get("blocks") or {}; print("%.0f scenes/s  %.4f ms/step  %s" % (d["value"], d["ms_per_step"], {k: b[k] for k in b if k in ("min","max","median","value_min","value_max")}))')"; }
+run() { echo "== $1: $(timeout 600 python bench.py --full --no-cpu-baseline --no-passes $2 2>/dev/null | tail -1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); b=d.get("blocks") or {}; print("%.0f scenes/s  %.4f ms/step  %s" % (d["value"], d["ms_per_step"], {k: b[k] for k in b if k in ("min","max","median","value_min","value_max")}))')"; }
 for i in 1 2; do
 run "cfg4 b1 1 lane" "--config cfg4"
 run "cfg4 b1 2 lanes" "--config cfg4 --streams 2"

@@ -210,7 +210,7 @@ def test_forward_is_ordered_behind_in_place_input_writes():
                     assert a.shape == b.shape and torch.equal(a, b), f"forward {i} (variant {key}) differs from the first pass"
 
 
-def test_bench_multi_rank_path_on_one_gpu():
+def test_bench_multi_rank_path_on_one_gpu(tmp_path):
     """bench.py's own N > 1 path -- self-launch under torch.distributed.run, process-group init, barrier-bracketed timing,
     MAX all-reduce, the rank census -- exercised on the 1-GPU box: two ranks share cuda:0 over gloo (the numbers mean
     nothing; with --backend nccl the same code runs over RCCL on an 8-GPU node)."""
@@ -218,9 +218,9 @@ def test_bench_multi_rank_path_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    # (a) the reduced line, (b) the DRIVER's flags -- `--gpus N --steps K --warmup W` and nothing else: the extra legs
+    # (a) the reduced --full line, (b) the whole --full line: the extra legs
     # (fp32-stored features, bf16 compute) run on every rank behind real barriers, the rank-0-only reports are skipped
-    for extra in (["--no-passes", "--no-cpu-baseline", "--time-every", "1"], ["--time-every", "1"]):
+    for extra in (["--full", "--no-passes", "--no-cpu-baseline", "--time-every", "1"], ["--full", "--time-every", "1"]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
                             "--steps", "2", "--warmup", "1", "--repeats", "2"] + extra,
                            env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -236,6 +236,87 @@ def test_bench_multi_rank_path_on_one_gpu():
         assert tb["blocks"] == 2 and len(tb["values"]) == 2 and tb["value_min"] <= d["value"] <= tb["value_max"]
         if "--no-passes" not in extra:
             assert d["value_f32_features"] > 0 and d["value_bf16_compute"] > 0 and "roofline_passes" not in d
+    # (c) the plain line of `bench.py --gpus N` with --dump-outputs: one block, the headline alone, and both ranks writing their own
+    # scenes into one directory.  Last timed step = step 1 -> input set 1 -> scenes (1 * 2 + rank) * 4 + b = 8..15.
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and [x[0] for x in d["ranks_seen"]] == [0, 1] and d["value"] > 0
+    assert d["timed_blocks"]["blocks"] == 1 and d["timed_blocks"]["steps_per_block"] == 2
+    assert d["roofline"] is None and d["cpu_baseline"] is None and not {"value_f32_features", "value_bf16_compute"} & set(d)
+    assert sorted(os.listdir(out)) == [f"out_scene{s:05d}.npy" for s in range(8, 16)]
+    arrs = [np.load(out / f"out_scene{s:05d}.npy") for s in range(8, 16)]
+    assert all(a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 3 and len(a) > 0 for a in arrs)
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """The plain line `--gpus 1 --steps K --warmup W`: ONE block of exactly K timed steps and the headline alone (no roofline,
+    CPU baseline or extra legs).  --dump-outputs writes what the last timed step returned -- step K - 1 of the rotation over
+    three input sets -- the same bits on a second run, and the same as this process's own forward over those scenes."""
+    import json
+    from proxytransformation_amd.synth import CONFIGS
+    steps, dumps = 5, []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                            "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["unit"] == "scenes/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["timed_blocks"]["blocks"] == 1 and d["timed_blocks"]["steps_per_block"] == steps
+        assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 4e3 - 1) < 1e-3        # 4 scenes per step
+        assert d["roofline"] is None and d["cpu_baseline"] is None
+        assert not {"value_f32_features", "value_bf16_compute", "value_graph_replay", "train_step", "roofline_passes"} & set(d)
+        ids = range(4, 8)                                   # step 4 -> input set 4 % 3 = 1 -> scenes 4..7
+        assert sorted(os.listdir(out)) == [f"out_scene{s:05d}.npy" for s in ids]
+        arrs = [np.load(out / f"out_scene{s:05d}.npy") for s in ids]
+        assert all(a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 3 for a in arrs)
+        assert sum(a.nbytes for a in arrs) <= 64 << 20
+        dumps.append(arrs)
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))
+    cfg = CONFIGS["cfg2"]
+    m, _, (pts, td, img) = _setup(cfg, scene_ids=ids)
+    with torch.no_grad():
+        outs = m(pts, td, img.to(torch.bfloat16))
+    assert all(np.array_equal(o.cpu().numpy(), a) for o, a in zip(outs, dumps[0]))
+
+
+def test_bench_pipeline_plain_run_and_dumped_outputs(tmp_path):
+    """`--pipeline` without --full: one timed block, no per-stage events / host-draw variant / CPU baseline.  --dump-outputs writes
+    every output array of the last chained call (points, voxel rows, level points, sampled image features) within 64 MiB (a seeded
+    sample of each array's rows once the cap applies), and the same files on a second run."""
+    import json
+    names, dumps = None, []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg4_room", "--pipeline", "--steps", "2",
+                            "--warmup", "1", "--dump-outputs", str(out)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        p = d["pipeline"]
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and len(p["ms_blocks"]) == 1 and d["cpu_baseline"] is None
+        assert p["ms_per_stage"] is None and p["with_host_pixel_draws"] is None
+        B = d["config"]["scenes_per_gpu"]
+        names = ["coordinates", "features"] + [f"points_scene{b}" for b in range(B)] + \
+            [f"level{li}_{k}_scene{b}" for li in range(4) for k in ("points", "imgfeats") for b in range(B)]
+        assert sorted(os.listdir(out)) == sorted(n + ".npy" for n in names)
+        arrs = {n: np.load(out / f"{n}.npy") for n in names}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["coordinates"].dtype == np.float64 and np.array_equal(arrs["coordinates"], np.round(arrs["coordinates"]))
+        assert all(a.dtype == np.float32 for n, a in arrs.items() if n != "coordinates")
+        assert 0 < sum(len(arrs[f"points_scene{b}"]) for b in range(B)) <= p["surviving_points"]
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in names)
 
 
 _NT_WORKER = r"""

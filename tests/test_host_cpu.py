@@ -173,6 +173,27 @@ def test_product_never_touches_the_oracle():
     subprocess.run([sys.executable, "-c", code], check=True)
 
 
+def test_bench_dump_outputs_types_and_size_cap(tmp_path):
+    """bench.dump_outputs: float32 / float64 files only; over the budget every array keeps the same fraction of its rows, the
+    same rows on every call."""
+    sys.path.insert(0, ROOT)
+    import bench
+    arrays = {"a": torch.arange(3000, dtype=torch.float32).view(1000, 3), "b": torch.arange(500, dtype=torch.int32),
+              "c": torch.ones(10, dtype=torch.float64), "d": torch.ones(4, 2, dtype=torch.bfloat16)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in arrays}
+    assert [got[k].dtype for k in "abcd"] == [np.float32, np.float64, np.float64, np.float32]
+    assert np.array_equal(got["a"], arrays["a"].numpy()) and np.array_equal(got["b"], np.arange(500))
+    budget = 6000
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+    s1 = {k: np.load(tmp_path / "s1" / f"{k}.npy") for k in arrays}
+    assert sum(a.nbytes for a in s1.values()) <= budget
+    assert s1["a"].shape[1] == 3 and 0 < len(s1["a"]) < 1000 and len(np.unique(s1["a"][:, 0])) == len(s1["a"])
+    assert np.all(np.diff(s1["a"][:, 0]) > 0) and np.all(s1["a"][:, 0] % 3 == 0)     # whole rows, in order
+    assert all(np.array_equal(s1[k], np.load(tmp_path / "s2" / f"{k}.npy")) for k in arrays)
+
+
 def test_synth_is_deterministic():
     from proxytransformation_amd.synth import CONFIGS, fill_tensor, make_scene_batch, PreshapeConfig
     a = fill_tensor("textformer.0.attn.qkv.weight", (768, 256))

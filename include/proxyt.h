@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PTX_ABI_VERSION 12
+#define PTX_ABI_VERSION 13
 
 /* The library is built with -fvisibility=hidden: the entry points below are its ONLY dynamic symbols
  * (tests/test_host_cpu.py::test_library_exports_every_declared_symbol asserts "these and nothing else"). */
@@ -327,9 +327,9 @@ PTX_API int ptx_wait_counts(const int32_t *counts_host, int B, int64_t timeout_u
  * What the reference's data pipeline computes on the host between the decoded depth maps and the (N,3) cloud handed to
  * the path (configs/grounding/proxy-tiblock33-gs12-wbias-ddr0.6-clip.py:105-142):
  *   ConvertRGBDToPoints       datasets/transforms/points.py:20-98  (points_img2cam, structures/bbox_3d/utils.py:336-368)
- *   PointSample per view      datasets/transforms/points.py:290-420          [np.random.choice stays on the host]
+ *   PointSample per view      datasets/transforms/points.py:290-420          [np.random.choice on the host, or ptx_ingest_draw]
  *   AggregateMultiViewPoints  datasets/transforms/multiview.py:195-253       (torch.linalg.solve(global2ego, [p;1]))
- *   PointSample of the scene  datasets/transforms/points.py:290-420          [np.random.choice stays on the host]
+ *   PointSample of the scene  datasets/transforms/points.py:290-420          [np.random.choice on the host, or ptx_ingest_draw]
  *   GlobalRotScaleTrans       datasets/transforms/augmentation.py:253-       (points only; parameters from the host)
  * depth (V,H,W): float32 metres (depth_dtype 0) or the decoded uint16 image (1; value / depth_shift as LoadDepthFromFile
  * does).  ptx_ingest_index builds a rank / select index over the pixels with depth != 0 (one streaming pass) and
@@ -347,6 +347,32 @@ PTX_API int ptx_ingest_index(const void *depth, int depth_dtype, int V, int H, i
 PTX_API int ptx_ingest_gather(const void *depth, int depth_dtype, float depth_shift, int V, int H, int W, const float *inv_intrinsic,
                       const float *lu, const int32_t *piv, const int64_t *sel, int N, const float *aug, float *points,
                       uint32_t *bbox_enc, int32_t *status, const void *workspace, size_t ws_bytes, void *stream);
+
+/* ABI 13.  The two PointSample draws ON THE DEVICE (MultiViewIngest(sampler="device"); the numpy path above stays the default and
+ * the parity mode).  Runs on `stream` after ptx_ingest_index, reads the per-view counts from the index workspace and writes
+ * sel (N int64, device) for the unchanged ptx_ingest_gather: the host neither waits for the counts nor uploads anything per point.
+ * The draws are a pure function of (key, view counts, per_view, N) -- integer arithmetic only, the same on every device and stream --
+ * and follow the reference's rules (points.py:335-336, 395-411; multiview.py:195-253); they do not reproduce numpy's stream.
+ * ingest.device_choices restates them exactly on the host.  Definition (all arithmetic mod 2^64):
+ *   mix(z)      splitmix64 finaliser: z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   G           0x9E3779B97F4A7C15
+ *   K(s)        stage key = mix(key ^ mix(s + G)):  s = 0 the aggregate draw, s = v + 1 the draw of view v
+ *   P(k, m, x)  keyed permutation of [0, m): h = max(1, ceil(bitlen(m - 1) / 2)); a balanced Feistel network on 2h bits,
+ *               (L, R) = (x >> h, x & (2^h - 1)), 6 rounds r = 0..5 of (L, R) <- (R, L ^ (mix(k ^ ((r + 1) << 56) ^ R) >> (64 - h))),
+ *               x <- (L << h) | R; repeated (cycle walking) until x < m.  A draw without replacement of n out of m is P(k, m, 0..n-1):
+ *               distinct, in random order (never sorted), as np.random.choice(m, n, replace=False) returns them.
+ *   U(k, m, i)  draw with replacement: the high 64 bits of mix(k + (i + 1) * G) * m (every value within 2^-64 of probability 1/m)
+ *   cnt_v       depth != 0 pixels of view v, off_v = those of the views before v; E = views with cnt_v > 0, T = E * per_view
+ *   per output point j in [0, N):  q = T >= N ? P(K(0), T, j) : U(K(0), T, j);  e = q / per_view, i = q % per_view;
+ *               v = the e-th view with cnt_v > 0 (view order);  sel[j] = off_v + (cnt_v >= per_view ? P(K(v+1), cnt_v, i)
+ *                                                                                                   : U(K(v+1), cnt_v, i))
+ * status (1 int32, device): written by the kernel, PTX_DRAW_EMPTY when no view has a pixel (E = 0; sel is then all zeros, which
+ * ptx_ingest_gather reports in its own status word), 0 otherwise.  Host checks only (PTX_EINVAL before anything is enqueued):
+ * null pointers, V, H, W, per_view, N >= 1, V <= PTX_DRAW_MAX_VIEWS. */
+#define PTX_DRAW_EMPTY 1
+#define PTX_DRAW_MAX_VIEWS 4096
+PTX_API int ptx_ingest_draw(int V, int H, int W, int per_view, int N, uint64_t key, const void *workspace, size_t ws_bytes,
+                    int64_t *sel, int32_t *status, void *stream);
 
 /* ------------------------------------------------------------------ voxel quantisation
  * The step right after the path in the reference's detector (detectors/sparse_featfusion_grounder_preshape.py:388-397):

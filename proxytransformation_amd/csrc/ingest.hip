@@ -6,7 +6,8 @@
 //   AggregateMultiViewPoints multiview.py:195-253                  per view solve(global2ego, [p;1]), concatenate
 //   PointSample (scene)      points.py:290-420                     np.random.choice over the concatenation   [host RNG]
 //   (GlobalRotScaleTrans     augmentation.py:253-: rotate, scale, translate -- optional, parameters from the host RNG)
-// The host keeps the RNG (np.random) and composes the two choices into ONE index per output point: `sel[j]` = position
+// By default the host keeps the RNG (np.random) and composes the two choices into ONE index per output point (ptx_ingest_draw
+// makes both draws on the device instead): `sel[j]` = position
 // of output point j in the concatenation, over the views in order, of each view's depth != 0 pixels in row-major order
 // (the reference's `grid3d[nonzero_indices]`).  The device resolves that rank to a pixel with a two-level rank / select
 // index over 64-pixel groups and computes only the N points that survive -- the reference un-projects all V*H*W pixels.
@@ -15,6 +16,8 @@
 //                    depth != 0 and its exclusive count prefix inside a chunk of 256 groups; per chunk the total
 //   k_ingest_scan    exclusive prefix over the chunk totals (one work-group), per-view counts for the host (the
 //                    reference's len(points) per view, which decides `replace` in np.random.choice)
+//   k_ingest_draw    (optional, ptx_ingest_draw) both PointSample draws on the device from a counter-based hash, one thread per
+//                    output point, written as `sel` for the gather: no host wait for the counts, no upload per point
 //   k_ingest_gather  one thread per output point: binary search chunk -> group, select the r-th set bit of the group's
 //                    mask, read ONE depth value, un-project, transform, (augment,) store; the scene's bounding box is
 //                    reduced on the way and published in the encoding k_cluster reads (the forward then skips k_minmax)
@@ -270,6 +273,91 @@ __global__ __launch_bounds__(256) void k_ingest_gather(IngestGatherArgs a)
     }
 }
 
+// ---- the two PointSample draws on the device (ptx_ingest_draw; the exact definition is in include/proxyt.h, ingest.device_choices
+// restates it on the host).  Integer arithmetic only: the same key gives the same sel on every device and stream.
+constexpr unsigned long long kDrawGold = 0x9E3779B97F4A7C15ull;
+
+__device__ __forceinline__ unsigned long long draw_mix(unsigned long long z)          // splitmix64 finaliser
+{
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ unsigned long long draw_stage_key(unsigned long long key, unsigned long long s)
+{
+    return draw_mix(key ^ draw_mix(s + kDrawGold));
+}
+
+// x-th value of a draw without replacement from [0, m), x < m: a 6-round balanced Feistel network on 2h bits (2^2h < 4m) with
+// cycle walking until the image falls inside [0, m) -- a bijection of [0, m), so x = 0..n-1 gives n distinct values in random order
+__device__ __forceinline__ unsigned long long draw_perm(unsigned long long k, unsigned long long m, unsigned long long x)
+{
+    const int bits = m > 1ull ? 64 - __clzll((long long)(m - 1ull)) : 0;
+    const int h = max(1, (bits + 1) >> 1);
+    const unsigned long long mask = (1ull << h) - 1ull;
+    do {
+        unsigned long long L = x >> h, R = x & mask;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            const unsigned long long f = draw_mix(k ^ ((unsigned long long)(r + 1) << 56) ^ R) >> (64 - h);
+            const unsigned long long t = L ^ f;
+            L = R; R = t;
+        }
+        x = (L << h) | R;
+    } while (x >= m);
+    return x;
+}
+
+// i-th value of a draw with replacement from [0, m): multiply-high of a 64-bit hash (bias below 2^-64 per value)
+__device__ __forceinline__ unsigned long long draw_repl(unsigned long long k, unsigned long long m, unsigned long long i)
+{
+    return __umul64hi(draw_mix(k + (i + 1ull) * kDrawGold), m);
+}
+
+// one thread per output point; every work-group first lists the non-empty views in LDS (V <= PTX_DRAW_MAX_VIEWS, counts from the
+// index workspace's chunk offsets at the view boundaries), then resolves q = aggregate draw -> (view, position) -> per-view draw
+__global__ __launch_bounds__(256) void k_ingest_draw(int V, int cpv, int per_view, int N, unsigned long long key,
+                                                     const unsigned long long *__restrict__ chunk_off, long long *__restrict__ sel,
+                                                     int32_t *__restrict__ status)
+{
+    __shared__ int s_ne[PTX_DRAW_MAX_VIEWS];
+    __shared__ int s_wcnt[4];
+    __shared__ int s_base;
+    const int tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int v0 = 0; v0 < V; v0 += 256) {
+        const int v = v0 + tid;
+        const bool ne = v < V && chunk_off[(size_t)(v + 1) * cpv] > chunk_off[(size_t)v * cpv];
+        const unsigned long long bal = __ballot(ne);
+        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wcnt[wv] = __popcll(bal);
+        __syncthreads();
+        int base = s_base;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) base += w < wv ? s_wcnt[w] : 0;
+        if (ne) s_ne[base + rank] = v;
+        __syncthreads();
+        if (tid == 0) s_base += s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
+        __syncthreads();
+    }
+    const int E = s_base;
+    if (blockIdx.x == 0 && tid == 0) status[0] = E == 0 ? PTX_DRAW_EMPTY : 0;
+    const int j = blockIdx.x * 256 + tid;
+    if (j >= N) return;
+    if (E == 0) { sel[j] = 0; return; }
+    const unsigned long long T = (unsigned long long)E * (unsigned long long)per_view;
+    const unsigned long long ka = draw_stage_key(key, 0ull);
+    const unsigned long long q = T >= (unsigned long long)N ? draw_perm(ka, T, (unsigned long long)j) : draw_repl(ka, T, (unsigned long long)j);
+    const unsigned long long e = q / (unsigned long long)per_view, i = q - e * (unsigned long long)per_view;
+    const int v = s_ne[e];
+    const unsigned long long off = chunk_off[(size_t)v * cpv], cnt = chunk_off[(size_t)(v + 1) * cpv] - off;
+    const unsigned long long kv = draw_stage_key(key, (unsigned long long)v + 1ull);
+    const unsigned long long r = cnt >= (unsigned long long)per_view ? draw_perm(kv, cnt, i) : draw_repl(kv, cnt, i);
+    sel[j] = (long long)(off + r);
+}
+
 }  // namespace ptx
 
 using namespace ptx;
@@ -339,6 +427,24 @@ int ptx_ingest_gather(const void *depth, int depth_dtype, float depth_shift, int
     if (depth_dtype == 0) hipLaunchKernelGGL(k_ingest_gather<float>, dim3(cdiv(N, 256)), dim3(256), 0, st, a);
     else                  hipLaunchKernelGGL(k_ingest_gather<uint16_t>, dim3(cdiv(N, 256)), dim3(256), 0, st, a);
     PTX_LAUNCHED("k_ingest_gather");
+    return PTX_OK;
+}
+
+int ptx_ingest_draw(int V, int H, int W, int per_view, int N, uint64_t key, const void *workspace, size_t ws_bytes, int64_t *sel,
+                    int32_t *status, void *stream)
+{
+    PTX_REQUIRE(workspace && sel && status, "ptx_ingest_draw: null argument");
+    PTX_REQUIRE(V >= 1 && H >= 1 && W >= 1 && per_view >= 1 && N >= 1, "ptx_ingest_draw: V=%d H=%d W=%d per_view=%d N=%d",
+                V, H, W, per_view, N);
+    PTX_REQUIRE(V <= PTX_DRAW_MAX_VIEWS, "ptx_ingest_draw: V=%d views (at most %d)", V, PTX_DRAW_MAX_VIEWS);
+    PTX_REQUIRE((long)V * H * W <= (1l << 40), "ptx_ingest_draw: V=%d H=%d W=%d", V, H, W);
+    const IngestLayout L = ingest_layout(V, H, W);
+    if (ws_bytes < L.total) { set_error("ptx_ingest_draw: workspace too small: %zu < %zu bytes", ws_bytes, L.total); return PTX_ENOSPACE; }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const auto *coff = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(workspace) + L.chunk_off);
+    hipLaunchKernelGGL(k_ingest_draw, dim3(cdiv(N, 256)), dim3(256), 0, st, V, L.cpv, per_view, N, (unsigned long long)key, coff,
+                       reinterpret_cast<long long *>(sel), status);
+    PTX_LAUNCHED("k_ingest_draw");
     return PTX_OK;
 }
 

@@ -8,9 +8,11 @@ between the decoded depth maps and the ``(N,3)`` cloud that ``ProxyTransformatio
     PointSample(num_points=n_points)                datasets/transforms/points.py:290-420      the scene
     GlobalRotScaleTrans (points only, optional)     datasets/transforms/augmentation.py:253-   train pipeline
 
-The random draws stay where the reference has them -- ``np.random.choice`` on the host, consumed in the reference's order
-(one draw per non-empty view in view order, then one for the scene) so that a seeded run picks the same pixels -- and
-are composed into ONE index per output point.  Everything else runs in HIP behind the C ABI (``ptx_ingest_index`` /
+By default (``sampler="host"``) the random draws stay where the reference has them -- ``np.random.choice`` on the host, consumed in
+the reference's order (one draw per non-empty view in view order, then one for the scene) so that a seeded run picks the same
+pixels -- and are composed into ONE index per output point.  ``sampler="device"`` draws both stages on the GPU instead
+(``ptx_ingest_draw``: a counter-based hash under the same sampling rules, restated exactly on the host by ``device_choices``), so the
+host neither waits for the per-view counts nor uploads an index per point.  Everything else runs in HIP behind the C ABI (``ptx_ingest_index`` /
 ``ptx_ingest_gather``, csrc/ingest.hip): a streaming pass over the depth maps builds a rank / select index of the pixels
 with depth != 0, then only the N selected points are un-projected, moved to the global frame and written, together with
 the cloud's bounding box in the encoding the forward's clustering kernel reads (``forward(..., bbox=batch.bbox)`` skips
@@ -29,7 +31,8 @@ import torch
 
 from . import _abi
 
-__all__ = ["MultiViewIngest", "IngestedBatch", "compose_choices", "lu_factor_4x4", "lu_factor_4x4_batch"]
+__all__ = ["MultiViewIngest", "IngestedBatch", "compose_choices", "device_choices", "scene_key", "lu_factor_4x4",
+           "lu_factor_4x4_batch"]
 
 _DEPTH_DTYPES = {torch.float32: 0, torch.uint16: 1, torch.int16: 1}       # int16: a reinterpreted uint16 image
 
@@ -38,8 +41,23 @@ _DEPTH_DTYPES = {torch.float32: 0, torch.uint16: 1, torch.int16: 1}       # int1
 class IngestedBatch:
     points: List[torch.Tensor]          # B views (N,3) of one (B,N,3) buffer: the ``points`` argument of the forward
     bbox: torch.Tensor                  # (B,6) int32 = encoded min / max per scene (``forward(..., bbox=...)``)
-    view_counts: List[np.ndarray]       # per scene: pixels with depth != 0 per view (the reference's len(points))
-    sel: List[np.ndarray]               # per scene: the composed index per output point (tests / debugging)
+    view_counts: List[Optional[np.ndarray]]   # per scene: pixels with depth != 0 per view (the reference's len(points)); None for
+                                              # a scene drawn on the device (the host never waited for its counts)
+    sel: List[Optional[np.ndarray]]     # per scene: the composed index per output point (tests / debugging); None where drawn on the device
+    sel_device: Optional[List[Optional[torch.Tensor]]] = None   # sampler="device": per scene the (N,) int64 device index, None where
+                                                                # the scene brought its own ``choices``
+    draw_status: Optional[torch.Tensor] = None   # sampler="device": (B,) int32 device, PTX_DRAW_EMPTY (1) = no depth != 0 pixel
+    keys: Optional[List[Optional[int]]] = None   # sampler="device": per scene the 64-bit draw key (``device_choices(..., key)``)
+
+    def check(self) -> None:
+        """Raise ``ValueError`` if a scene drawn on the device had no valid pixel (its points are then zeros), as ``compose_choices``
+        does on the host.  Reads the status words back: this waits for the ingest."""
+        if self.draw_status is None:
+            return
+        st = self.draw_status.cpu().numpy()
+        bad = [b for b in range(len(st)) if st[b] & 1]
+        if bad:
+            raise ValueError(f"every depth map of the scene is empty (scene(s) {bad})")
 
 
 def lu_factor_4x4(a: np.ndarray):
@@ -103,6 +121,105 @@ def compose_choices(view_counts: Sequence[int], per_view: int, n_points: int, rn
     return cat[ch2]
 
 
+# ---- the device sampler's exact host restatement (include/proxyt.h, ptx_ingest_draw); uint64 arithmetic wraps mod 2^64
+_M64 = (1 << 64) - 1
+_GOLD = 0x9E3779B97F4A7C15
+_MIX1, _MIX2 = np.uint64(0xBF58476D1CE4E5B9), np.uint64(0x94D049BB133111EB)
+
+
+def _mix(z):
+    """splitmix64 finaliser on a uint64 array."""
+    z = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * _MIX1
+        z = (z ^ (z >> np.uint64(27))) * _MIX2
+    return z ^ (z >> np.uint64(31))
+
+
+def _mix_int(z: int) -> int:
+    return int(_mix(np.uint64(z & _M64)))
+
+
+def _stage_key(key: int, s: int) -> int:
+    return _mix_int((key & _M64) ^ _mix_int(s + _GOLD))
+
+
+def scene_key(base: int, b: int) -> int:
+    """Draw key of the scene at position ``b`` of a call whose 64-bit seed is ``base``: output ``b + 1`` of a splitmix64 stream seeded
+    with ``base`` (what ``MultiViewIngest(sampler="device")`` uses for a scene without ``draw_seed``)."""
+    return _mix_int((int(base) + (int(b) + 1) * _GOLD) & _M64)
+
+
+def _perm(k, m, x):
+    """P(k, m, x) of include/proxyt.h, elementwise: k, m, x uint64 arrays (broadcast), x < m.  6-round Feistel + cycle walking."""
+    m = np.asarray(m, np.uint64)
+    h = np.array([max(1, ((int(v) - 1).bit_length() + 1) // 2) for v in m.reshape(-1)], np.uint64).reshape(m.shape)
+    k, m, h, x = (a.copy() for a in np.broadcast_arrays(np.asarray(k, np.uint64), m, h, np.asarray(x, np.uint64)))
+    mask = (np.uint64(1) << h) - np.uint64(1)
+    todo = np.ones(x.shape, bool)
+    while todo.any():                                            # cycle walking: re-encrypt what fell outside [0, m)
+        kk, hh, xx = k[todo], h[todo], x[todo]
+        L, R = xx >> hh, xx & mask[todo]
+        for r in range(6):
+            f = _mix(kk ^ np.uint64((r + 1) << 56) ^ R) >> (np.uint64(64) - hh)
+            L, R = R, L ^ f
+        x[todo] = (L << hh) | R
+        todo = x >= m
+    return x
+
+
+def _repl(k, m, i):
+    """U(k, m, i) of include/proxyt.h: high 64 bits of mix(k + (i + 1) G) * m, exact for m < 2^32."""
+    k, m, i = np.broadcast_arrays(np.asarray(k, np.uint64), np.asarray(m, np.uint64), np.asarray(i, np.uint64))
+    if np.any(m >= np.uint64(1 << 32)):
+        raise ValueError("draw with replacement from 2^32 or more values")
+    u = _mix(k + (i + np.uint64(1)) * np.uint64(_GOLD))
+    hi, lo = u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)
+    return (hi * m + ((lo * m) >> np.uint64(32))) >> np.uint64(32)
+
+
+def device_choices(view_counts: Sequence[int], per_view: int, n_points: int, key: int, return_stages: bool = False):
+    """The composed index ``sel`` (N,) int64 that ``ptx_ingest_draw`` writes for a scene with per-view pixel counts ``view_counts`` and
+    draw key ``key`` -- bit for bit (the definition is in include/proxyt.h).  The same sampling rules as ``compose_choices``: per
+    non-empty view ``per_view`` draws, with replacement iff the view has fewer pixels; then ``n_points`` draws over the concatenation
+    (length E * per_view), with replacement iff it is shorter; a view without pixels draws nothing.
+
+    ``return_stages=True`` returns ``(sel, stages)`` with ``stages`` = the draws as ``np.random.choice`` would return them in the
+    reference's order: one (per_view,) array of ranks inside the view per non-empty view, in view order, then the (n_points,)
+    positions in the concatenation.  Raises ``ValueError`` if every view is empty."""
+    with np.errstate(over="ignore"):
+        cnt = np.asarray(view_counts, dtype=np.int64).reshape(-1)
+        per_view, n_points, key = int(per_view), int(n_points), int(key) & _M64
+        if per_view < 1 or n_points < 1:
+            raise ValueError(f"per_view={per_view}, n_points={n_points}")
+        ne = np.flatnonzero(cnt > 0)
+        if len(ne) == 0:
+            raise ValueError("every depth map of the scene is empty")
+        off = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int64)
+        E = len(ne)
+        T = E * per_view
+        # stage 1: per non-empty view the per_view ranks inside the view, all views at once
+        kv = np.array([_stage_key(key, int(v) + 1) for v in ne], np.uint64)[:, None]
+        m = cnt[ne].astype(np.uint64)[:, None]
+        i = np.arange(per_view, dtype=np.uint64)[None, :]
+        first = np.empty((E, per_view), np.uint64)
+        rep = (cnt[ne] < per_view)
+        if (~rep).any():
+            first[~rep] = _perm(kv[~rep], m[~rep], i)
+        if rep.any():
+            first[rep] = _repl(kv[rep], m[rep], i)
+        # stage 2: n_points positions in the concatenation
+        ka = np.uint64(_stage_key(key, 0))
+        j = np.arange(n_points, dtype=np.uint64)
+        q = _perm(ka, np.uint64(T), j) if T >= n_points else _repl(ka, np.uint64(T), j)
+        q = q.astype(np.int64)
+        cat = (first.astype(np.int64) + off[ne][:, None]).reshape(-1)
+        sel = cat[q]
+    if return_stages:
+        return sel, [first[e].astype(np.int64) for e in range(E)] + [q]
+    return sel
+
+
 class MultiViewIngest:
     """``MultiViewIngest(n_points)(scenes)``: scenes = list of dicts with the reference pipeline's keys
 
@@ -111,14 +228,25 @@ class MultiViewIngest:
         depth_cam2img  (3,3) / (3,4) / (4,4) intrinsic, one for the scene or (V,...) per view
         extrinsic      (V,4,4) float32 global2ego (results['depth2img']['extrinsic'])
         aug            optional dict(rot_mat_T (3,3), scale, trans (3)): GlobalRotScaleTrans's effect on the points
-        choices        optional precomputed (N,) index (see ``compose_choices``); otherwise drawn from ``rng``
+        choices        optional precomputed (N,) index (see ``compose_choices``); wins over either sampler
+        draw_seed      optional 64-bit draw key of the scene (``sampler="device"``): its cloud then does not depend on its
+                       position in the batch or on ``seed`` / ``rng``
+
+    ``sampler="host"`` (default): both ``PointSample`` draws with ``rng.choice`` in the reference's order (``compose_choices``);
+    the host waits for each scene's per-view counts.  ``sampler="device"``: both draws on the GPU (``ptx_ingest_draw``), exactly
+    ``device_choices(counts, per_view, N, key)``; the call neither waits nor uploads an index per point.  The key of a scene
+    without ``draw_seed`` is ``scene_key(base, b)``, ``base`` = ``seed`` or one 64-bit draw from ``rng`` per call (so a seeded
+    ``np.random`` reproduces a run).  ``IngestedBatch.check()`` raises on a scene without valid pixels.
     """
 
     def __init__(self, n_points: int = 100000, per_view_points: Optional[int] = None, depth_map_size=None,
-                 use_color: bool = False):
+                 use_color: bool = False, sampler: str = "host"):
         if depth_map_size is not None or use_color:
             raise NotImplementedError("ConvertRGBDToPoints(depth_map_size=..., use_color=True) is not part of the shipped "
                                       "pipeline (CFG:112, 134) and is not implemented on the device")
+        if sampler not in ("host", "device"):
+            raise ValueError(f"sampler must be 'host' or 'device', got {sampler!r}")
+        self.sampler = sampler
         self.n_points = int(n_points)
         self.per_view_points = int(per_view_points) if per_view_points is not None else self.n_points // 10   # CFG:113, 135
 
@@ -178,12 +306,32 @@ class MultiViewIngest:
             sl.copied = None
         return sl
 
+    @staticmethod
+    def _base_seed(rng) -> int:
+        """One 64-bit value from ``rng`` (np.random / RandomState: randint; Generator: integers)."""
+        draw = rng.integers if hasattr(rng, "integers") else rng.randint
+        return int(draw(0, 2 ** 64, dtype=np.uint64))
+
     @torch.no_grad()
-    def __call__(self, scenes: Sequence[Dict], rng=np.random) -> IngestedBatch:
+    def __call__(self, scenes: Sequence[Dict], rng=np.random, seed: Optional[int] = None) -> IngestedBatch:
         lib = _abi.lib()
         B, N = len(scenes), self.n_points
         if B == 0:
             raise ValueError("no scenes")
+        on_dev = self.sampler == "device"
+        keys = None
+        if on_dev:
+            base = None
+            keys = []
+            for b, sc in enumerate(scenes):
+                if sc.get("choices") is not None:
+                    keys.append(None)
+                elif sc.get("draw_seed") is not None:
+                    keys.append(int(sc["draw_seed"]) & _M64)
+                else:
+                    if base is None:
+                        base = (int(seed) & _M64) if seed is not None else self._base_seed(rng)
+                    keys.append(scene_key(base, b))
         dev = scenes[0]["depth_img"].device
         if dev.type != "cuda":
             raise RuntimeError("MultiViewIngest (HIP) needs GPU tensors: there is no CPU path")
@@ -193,6 +341,9 @@ class MultiViewIngest:
         # (cleared and set by ptx_ingest_gather: bit 0 = a rank beyond the scene's pixels.  The host has already checked the ranks
         #  against the published counts below, so the word is not read back -- the C ABI wants the buffer)
         status = torch.empty((B,), dtype=torch.int32, device=dev)
+        if on_dev:
+            sel_dev = torch.empty((B, N), dtype=torch.int64, device=dev)
+            draw_status = torch.zeros((B,), dtype=torch.int32, device=dev)      # written by k_ingest_draw for the drawn scenes
         work = []
         for b, sc in enumerate(scenes):                          # 1. index every scene's depth maps (one pass each)
             depth = sc["depth_img"]
@@ -217,30 +368,38 @@ class MultiViewIngest:
         ext_all = np.concatenate([np.asarray(sc["extrinsic"], dtype=np.float32).reshape(V, 4, 4) for sc, V in zip(scenes, Vs)])
         lus_all, pivs_all = lu_factor_4x4_batch(ext_all)
         voff = np.concatenate([[0], np.cumsum(Vs)])
-        sels, vcs = [], []
-        for b, (sc, (depth, sl)) in enumerate(zip(scenes, work)):           # 2. host RNG, 3. gather
+        sels, vcs, sels_dev = [], [], []
+        for b, (sc, (depth, sl)) in enumerate(zip(scenes, work)):           # 2. host RNG or device draw, 3. gather
             V, H, W = depth.shape
-            # the per-view counts decide `replace` on the host: wait for THESE V words (not for the stream to drain)
-            if lib.ptx_wait_counts(sl.counts.data_ptr(), V, 20_000_000) != 0:
-                st.synchronize()
-            vc = sl.counts_np[:V].copy()
-            if vc.min() < 0:
-                raise RuntimeError("ptx_ingest_index finished without publishing the per-view counts")
-            sel = sc.get("choices")
-            if sel is None:
-                sel = compose_choices(vc, self.per_view_points, N, rng)
-            sel = np.ascontiguousarray(sel, dtype=np.int64)
-            if sel.shape != (N,):
-                raise ValueError(f"choices must be ({N},), got {sel.shape}")
-            if sel.min() < 0 or sel.max() >= int(vc.sum()):      # checked where the counts are: no device round trip for it
-                raise IndexError(f"choices beyond the scene's depth != 0 pixels in scene {b}")
+            if on_dev and keys[b] is not None:
+                # both PointSample draws on the device, from the counts in the index workspace: no host wait, no upload of sel
+                _abi.check(lib.ptx_ingest_draw(V, H, W, self.per_view_points, N, keys[b], sl.ws.data_ptr(), sl.ws.numel(),
+                                               sel_dev[b].data_ptr(), draw_status[b:].data_ptr(), st.cuda_stream), "ptx_ingest_draw")
+                sel, vc, sel_ptr = None, None, sel_dev[b].data_ptr()
+            else:
+                # the per-view counts decide `replace` on the host: wait for THESE V words (not for the stream to drain)
+                if lib.ptx_wait_counts(sl.counts.data_ptr(), V, 20_000_000) != 0:
+                    st.synchronize()
+                vc = sl.counts_np[:V].copy()
+                if vc.min() < 0:
+                    raise RuntimeError("ptx_ingest_index finished without publishing the per-view counts")
+                sel = sc.get("choices")
+                if sel is None:
+                    sel = compose_choices(vc, self.per_view_points, N, rng)
+                sel = np.ascontiguousarray(sel, dtype=np.int64)
+                if sel.shape != (N,):
+                    raise ValueError(f"choices must be ({N},), got {sel.shape}")
+                if sel.min() < 0 or sel.max() >= int(vc.sum()):      # checked where the counts are: no device round trip for it
+                    raise IndexError(f"choices beyond the scene's depth != 0 pixels in scene {b}")
+                sel_ptr = None
             inv_k, lus, pivs = inv_all[voff[b]:voff[b + 1]], lus_all[voff[b]:voff[b + 1]], pivs_all[voff[b]:voff[b + 1]]
             aug = sc.get("aug")
             if sl.copied is not None and not sl.copied.query():
                 sl.copied.synchronize()                          # the previous call's copy out of the staging buffer (long done)
             o_sel, o_small = 0, (8 * N + 15) // 16 * 16          # 16-byte aligned tables
             o_piv = o_small + 4 * (32 * V + 16)
-            sl.stage_np[o_sel:o_sel + 8 * N].view(np.int64)[:] = sel
+            if sel is not None:
+                sl.stage_np[o_sel:o_sel + 8 * N].view(np.int64)[:] = sel
             small = sl.stage_np[o_small:o_small + 4 * (32 * V + 13)].view(np.float32)
             small[:16 * V] = inv_k.reshape(-1)
             small[16 * V:32 * V] = lus.reshape(-1)
@@ -249,7 +408,10 @@ class MultiViewIngest:
                 small[32 * V + 9] = np.float32(aug["scale"])
                 small[32 * V + 10:32 * V + 13] = np.asarray(aug["trans"], np.float32).reshape(3)
             sl.stage_np[o_piv:o_piv + 16 * V].view(np.int32)[:] = pivs.astype(np.int32).reshape(-1)
-            sl.stage_dev.copy_(sl.stage, non_blocking=True)
+            if sel is not None:
+                sl.stage_dev.copy_(sl.stage, non_blocking=True)
+            else:                                                # the small tables only: sel is already on the device
+                sl.stage_dev[o_small:].copy_(sl.stage[o_small:], non_blocking=True)
             sl.copied = torch.cuda.Event()
             sl.copied.record(st)
             shift = float(sc.get("depth_shift", 1.0))
@@ -257,8 +419,12 @@ class MultiViewIngest:
             fp = dp + o_small
             _abi.check(lib.ptx_ingest_gather(
                 depth.data_ptr(), _DEPTH_DTYPES[depth.dtype], shift, V, H, W, fp, fp + 4 * V * 16, dp + o_piv,
-                dp + o_sel, N, (fp + 4 * V * 32) if aug is not None else None, out[b].data_ptr(), bbox[b].data_ptr(),
+                dp + o_sel if sel_ptr is None else sel_ptr, N, (fp + 4 * V * 32) if aug is not None else None, out[b].data_ptr(), bbox[b].data_ptr(),
                 status[b:].data_ptr(), sl.ws.data_ptr(), sl.ws.numel(), st.cuda_stream), "ptx_ingest_gather")
             sels.append(sel)
             vcs.append(vc)
-        return IngestedBatch(points=[out[b] for b in range(B)], bbox=bbox, view_counts=vcs, sel=sels)
+            sels_dev.append(sel_dev[b] if sel_ptr is not None else None)
+        if not on_dev:
+            return IngestedBatch(points=[out[b] for b in range(B)], bbox=bbox, view_counts=vcs, sel=sels)
+        return IngestedBatch(points=[out[b] for b in range(B)], bbox=bbox, view_counts=vcs, sel=sels, sel_device=sels_dev,
+                             draw_status=draw_status, keys=keys)

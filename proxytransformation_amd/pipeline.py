@@ -18,7 +18,7 @@ that set (rows in first-occurrence order; ME's own row order is unspecified) by 
 rows (``ptx_voxel_coarsen``); the features that travel with them in the reference are the backbone's and stay out.
 
 Nothing in ``__call__`` synchronises the device: the host waits only for small integers the kernels publish through pinned memory
-(per-view pixel counts, survivor counts, voxel row counts) -- the list LENGTHS the reference obtains with blocking ``.item()`` /
+(per-view pixel counts -- none with sampler="device" --, survivor counts, voxel row counts) -- the list LENGTHS the reference obtains with blocking ``.item()`` /
 ``nonzero`` / ``unique`` calls -- and every stage is enqueued on the caller's current stream; only the channels-last copies of the
 feature maps that the sampling gathers from (they do not depend on the points) run on a side stream beside the ingest, forked and
 joined by events (``overlap_feature_layout=False``: on the caller's stream as well).
@@ -123,14 +123,17 @@ class GroundingFeaturePrefix:
 
     ``scenes``: one dict per sample with what the loading transforms hand on -- ``depth_img`` (V,H,W) float32 metres or uint16 raw
     (+ ``depth_shift``), ``depth_cam2img``, ``depth2img = dict(extrinsic=[V x (4,4) global2cam], intrinsic=[V x cam2img] | one)``
-    (mv_3dvg_dataset.py:544-553), optional ``aug`` / ``choices`` (ingest.MultiViewIngest) and ``img_meta`` (``scale_factor``, ``flip``,
+    (mv_3dvg_dataset.py:544-553), optional ``aug`` / ``choices`` / ``draw_seed`` (ingest.MultiViewIngest) and ``img_meta`` (``scale_factor``, ``flip``,
     ``img_crop_offset``, ``img_shape``, the 3D flow record) for the sampling.  ``img_features``: the 2D backbone's levels, each
-    (B,V,C_l,H_l,W_l); the LAST one feeds the neck (DET:385)."""
+    (B,V,C_l,H_l,W_l); the LAST one feeds the neck (DET:385).  ``sampler``: where the ingest's two ``PointSample`` draws are made
+    (``MultiViewIngest``): "host" (np.random, the reference's stream; the host waits for each scene's per-view counts) or "device"
+    (ptx_ingest_draw; ``seed=`` / ``rng`` / a scene's ``draw_seed`` give the keys, no host wait in the ingest)."""
 
     def __init__(self, preshape, n_points: int = 100000, voxel_size: float = 0.01,
-                 level_strides: Sequence[int] = MINK_RESNET_STRIDES, coord_type: str = "DEPTH", overlap_feature_layout: bool = True):
+                 level_strides: Sequence[int] = MINK_RESNET_STRIDES, coord_type: str = "DEPTH", overlap_feature_layout: bool = True,
+                 sampler: str = "host"):
         self.preshape = preshape
-        self.ingest = MultiViewIngest(n_points)
+        self.ingest = MultiViewIngest(n_points, sampler=sampler)
         self.voxel_size = float(voxel_size)
         self.level_strides = tuple(int(s) for s in level_strides)
         self.coord_type = coord_type
@@ -173,7 +176,8 @@ class GroundingFeaturePrefix:
 
     @torch.no_grad()
     def __call__(self, scenes: Sequence[dict], text_dict: dict, img_features: Sequence[torch.Tensor],
-                 img_pad_shape: Sequence[int] = (480, 480), rng=np.random, time_stages: bool = False) -> PrefixOutput:
+                 img_pad_shape: Sequence[int] = (480, 480), rng=np.random, time_stages: bool = False,
+                 seed: Optional[int] = None) -> PrefixOutput:
         if len(img_features) != len(self.level_strides):
             raise ValueError(f"{len(self.level_strides)} levels of image features expected, got {len(img_features)}")
         dev = img_features[-1].device
@@ -197,7 +201,7 @@ class GroundingFeaturePrefix:
             flat[0].record_stream(st)                        # ONE allocation under the side stream, consumed on the caller's
             prepared = [flat[b * nl:(b + 1) * nl] for b in range(len(scenes))]
         proj_t, flow_t = self._upload_matrices(scenes, dev, st)
-        batch = self.ingest(scenes, rng=rng)                                               # N4
+        batch = self.ingest(scenes, rng=rng, seed=seed)                                    # N4
         mark("ingest")
         outs = self.preshape(batch.points, text_dict, img_features[-1], bbox=batch.bbox)   # the path, DET:385
         mark("preshape")

@@ -201,6 +201,20 @@ PTX_API int ptx_ball_query(const float *centers, const float *points, int B, int
  * fp32 MFMA (v_mfma_f32_32x32x2_f32); n_in % 4 == 0, x and w 16-byte aligned. */
 PTX_API int ptx_linear(const float *x, const float *w, const float *bias, const float *residual, float *y,
                int rows, int n_out, int n_in, int gelu, void *stream);
+/* The LayerNorm -> Linear seam of the eval forward (norm2 -> fc1 of both blocks, norm_img -> proxy_proj), as operators: the same
+ * launch_gemm / k_prep_lnfold calls the forward makes, steered by ptx_gemm_policy the same way.
+ * Producer: ptx_linear without GELU, and per row and per 32-column tile of y the fp32 LayerNorm partial of the FINAL values,
+ * lnp[(row * ceil(n_out / 32) + tile) * 2 + {0, 1}] (rows * ceil(n_out / 32) * 2 floats, 8-byte aligned). */
+PTX_API int ptx_linear_ln_partials(const float *x, const float *w, const float *bias, const float *residual, float *y, float *lnp,
+               int rows, int n_out, int n_in, void *stream);
+/* Consumer: y (rows,n_out) = Linear(LayerNorm(x; gamma, beta, eps); w, bias) [-> GELU(erf)] on the RAW rows x (rows,n_in) of a
+ * producer and its partials lnp (rows, n_in / 32, 2); the normalised rows are never formed.  n_in a multiple of 32, at most 512
+ * (anything else is PTX_EINVAL, nothing is launched); bias may be NULL.  scratch: ptx_ln_linear_scratch_bytes(n_out, n_in) bytes,
+ * 16-byte aligned, overwritten with the folded tables (w diag(gamma), w beta + bias). */
+PTX_API size_t ptx_ln_linear_scratch_bytes(int n_out, int n_in);
+PTX_API int ptx_ln_linear(const float *x, const float *lnp, const float *w, const float *gamma, const float *beta,
+               const float *bias, float eps, int gelu, float *y, void *scratch, size_t scratch_bytes,
+               int rows, int n_out, int n_in, void *stream);
 /* ABI 12.  Tile policy of the split-operand GEMMs behind every nn.Linear of the path (csrc/gemm.hip): a launch (all its groups
  * together) of at least `min_tiles_128` tiles of 128 x 128 outputs, with K a multiple of 256, runs on 128 x 128 tiles (k_gemm128x),
  * anything else on 64 x 64 tiles / the latency-regime kernel (between 1 and 1.5 x `min_tiles_128` tiles the large tile is taken only

@@ -180,8 +180,8 @@ def point_encoder(sd, center, cluster, training: bool = False) -> torch.Tensor:
     return _slot_mlp(sd, "simple_encoder", center, cluster, training).max(dim=2)[0]
 
 
-def img_proxy(sd, img_feat: torch.Tensor, heads: int) -> torch.Tensor:
-    """get_img_proxy + AttentionPool2d, PRE:335-342, 154-177 -> (B,V,C).
+def img_cproj(sd, img_feat: torch.Tensor, heads: int) -> torch.Tensor:
+    """get_img_proxy up to and including AttentionPool2d's c_proj, PRE:335-341, 154-177 -> (B*V,C): the rows norm_img sees.
 
     Written in the 'all queries' form of the reference (token 0 returned)."""
     B, V, Cin, H, W = img_feat.shape
@@ -200,7 +200,14 @@ def img_proxy(sd, img_feat: torch.Tensor, heads: int) -> torch.Tensor:
     v = v.reshape(-1, T, heads, hd).transpose(1, 2)
     a = torch.softmax(q @ k.transpose(-1, -2), dim=-1) @ v          # (BV,h,T,hd)
     a = a.transpose(1, 2).reshape(-1, T, C)
-    out = F.linear(a, sd["attn_pool2d.c_proj.weight"], sd["attn_pool2d.c_proj.bias"])[:, 0]
+    return F.linear(a, sd["attn_pool2d.c_proj.weight"], sd["attn_pool2d.c_proj.bias"])[:, 0]
+
+
+def img_proxy(sd, img_feat: torch.Tensor, heads: int) -> torch.Tensor:
+    """get_img_proxy + AttentionPool2d, PRE:335-342, 154-177 -> (B,V,C)."""
+    B, V = img_feat.shape[:2]
+    out = img_cproj(sd, img_feat, heads)
+    C = out.shape[-1]
     out = F.layer_norm(out, (C,), sd["norm_img.weight"], sd["norm_img.bias"], LN_EPS)
     return out.reshape(B, V, C)
 

@@ -140,6 +140,9 @@ SIGNATURES = {
     "ptx_grid_centers": (_I, [_P, _I, _I, _P, _I, _F, _P, _P, _P, _Z, _P]),
     "ptx_ball_query": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "ptx_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ptx_linear_ln_partials": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ptx_ln_linear_scratch_bytes": (_Z, [_I, _I]),
+    "ptx_ln_linear": (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _Z, _I, _I, _I, _P]),
     "ptx_gemm_policy": (_I, [_I]),
     "ptx_offset_net": (_I, [_SH, _W, _P, _P, _P, _P, _P, _P, _P]),
     "ptx_select_clusters": (_I, [_SH] + [_P] * 14),

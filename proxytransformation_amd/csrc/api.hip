@@ -138,9 +138,9 @@ PrepLayout prep_layout(const PtxShape &s)
     P.w3 = take((size_t)3 * s.C * s.in_dim); P.b3 = take((size_t)3 * s.C);
     P.t1 = take((size_t)s.heads * P.KT1 * P.hd);
     P.t2 = take((size_t)s.heads * P.hd * P.KT2p);
-    P.ppg_w = take((size_t)s.C * s.C); P.ppg_s = take(s.C); P.ppg_c = take(s.C);
+    P.ppg_w = take((size_t)s.C * s.C); P.ppg_c = take(s.C);
     for (int i = 0; i < 2; ++i) {
-        P.fc1g_w[i] = take((size_t)s.hidden * s.C); P.fc1g_s[i] = take(s.hidden); P.fc1g_c[i] = take(s.hidden);
+        P.fc1g_w[i] = take((size_t)s.hidden * s.C); P.fc1g_c[i] = take(s.hidden);
         const size_t planes = mlp_fused_supported(s.C, s.hidden, 1, 0) ? (size_t)s.hidden * s.C * 3 / 2 : 0;   // bf16 x 3, in floats
         P.mlp_w1p[i] = take(planes); P.mlp_w2p[i] = take(planes);
     }
@@ -572,8 +572,8 @@ struct Branch {
     const float *head_w, *head_b, *head_ab; int nout; float *head_out; float *guide; int slot;
     bool late_proxy;     // the proxies of this branch are produced on the side stream (image proxies)
     // proxies given as RAW rows + LayerNorm partials (the forward's image branch): proxy_proj folds the LayerNorm
-    const float *proxy_lnp, *pp_gw, *pp_gs, *pp_gc;
-    const float *fc1_gw, *fc1_gs, *fc1_gc;      // norm2 folded into fc1
+    const float *proxy_lnp, *pp_gw, *pp_gc;
+    const float *fc1_gw, *fc1_gc;      // norm2 folded into fc1
     const float *prep;                          // the parameter tables (weight planes of the fused Mlp)
 };
 
@@ -613,7 +613,7 @@ static int run_blocks(const PtxShape &s, const Branch *br, int nb, const float *
                              nullptr, nullptr, nullptr, s.B * br[i].Lp, C, C, C, C, C, 0, 0, 0, EPI_NONE};
                 if (br[i].proxy_lnp != nullptr) {       // LayerNorm(norm_img) folded into this GEMM
                     q.W = br[i].pp_gw; q.bias = nullptr;
-                    q.lnp_in = br[i].proxy_lnp; q.ln_s = br[i].pp_gs; q.ln_c = br[i].pp_gc;
+                    q.lnp_in = br[i].proxy_lnp; q.ln_c = br[i].pp_gc;
                     q.ln_parts = C / 32; q.ln_C = C; q.ln_eps = s.ln_eps;
                 }
             }
@@ -671,7 +671,7 @@ static int run_blocks(const PtxShape &s, const Branch *br, int nb, const float *
         for (int i = 0; i < nb; ++i) {
             const int sl = br[i].slot;
             mb.p[i] = MlpProb{at<float>(ws, L.x1[sl]), at<float>(ws, L.lnp_x1[sl]), br[i].prep + P.mlp_w1p[sl],
-                              br[i].prep + P.mlp_w2p[sl], br[i].fc1_gs, br[i].fc1_gc, br[i].blk->fc2_b,
+                              br[i].prep + P.mlp_w2p[sl], br[i].fc1_gc, br[i].blk->fc2_b,
                               at<float>(ws, L.x2[sl]), R,
                               br[i].blk->out_norm_w, br[i].blk->out_norm_b, br[i].head_w, br[i].head_b, br[i].head_ab,
                               br[i].head_out, br[i].guide, br[i].nout};
@@ -686,7 +686,7 @@ static int run_blocks(const PtxShape &s, const Branch *br, int nb, const float *
             g.p[i] = GemmProb{at<float>(ws, L.x1[sl]), br[i].fc1_gw, at<float>(ws, L.hbuf[sl]),
                               nullptr, nullptr, nullptr, nullptr, R, s.hidden, C, C, C, s.hidden,
                               0, 0, 0, EPI_GELU};
-            g.p[i].lnp_in = at<float>(ws, L.lnp_x1[sl]); g.p[i].ln_s = br[i].fc1_gs; g.p[i].ln_c = br[i].fc1_gc;
+            g.p[i].lnp_in = at<float>(ws, L.lnp_x1[sl]); g.p[i].ln_c = br[i].fc1_gc;
             g.p[i].ln_parts = C / 32; g.p[i].ln_C = C; g.p[i].ln_eps = s.ln_eps;
         }
         PTX_TIMED(KID_BLK_FC1, st, launch_gemm(g, st, cd));
@@ -725,8 +725,8 @@ static Branch make_branch(const PtxShape &s, const PtxWeights &w, const float *p
     b.head_ab = prep + (which == 0 ? P.ttn_ab : P.itn_ab);
     b.nout = which == 0 ? 3 : 9;
     b.head_out = head_out; b.guide = guide; b.slot = which; b.late_proxy = which == 1;
-    b.proxy_lnp = nullptr; b.pp_gw = prep + P.ppg_w; b.pp_gs = prep + P.ppg_s; b.pp_gc = prep + P.ppg_c;
-    b.fc1_gw = prep + P.fc1g_w[which]; b.fc1_gs = prep + P.fc1g_s[which]; b.fc1_gc = prep + P.fc1g_c[which];
+    b.proxy_lnp = nullptr; b.pp_gw = prep + P.ppg_w; b.pp_gc = prep + P.ppg_c;
+    b.fc1_gw = prep + P.fc1g_w[which]; b.fc1_gc = prep + P.fc1g_c[which];
     b.prep = prep;
     return b;
 }
@@ -945,6 +945,42 @@ int ptx_linear(const float *x, const float *w, const float *bias, const float *r
     g.p[0] = GemmProb{x, w, y, bias, residual, nullptr, nullptr, rows, n_out, n_in, n_in, n_in, n_out, n_out, 0, 0,
                       gelu ? EPI_GELU : EPI_NONE};
     return launch_gemm(g, static_cast<hipStream_t>(stream));
+}
+
+int ptx_linear_ln_partials(const float *x, const float *w, const float *bias, const float *residual, float *y, float *lnp,
+                           int rows, int n_out, int n_in, void *stream)
+{
+    PTX_REQUIRE(x && w && y && lnp, "ptx_linear_ln_partials: null argument");
+    PTX_REQUIRE(rows >= 1 && n_out >= 1 && n_in >= 4, "ptx_linear_ln_partials: rows=%d n_out=%d n_in=%d", rows, n_out, n_in);
+    GemmBatch g{}; g.n = 1;
+    g.p[0] = GemmProb{x, w, y, bias, residual, nullptr, nullptr, rows, n_out, n_in, n_in, n_in, n_out, n_out, 0, 0, EPI_NONE};
+    g.p[0].lnp_out = lnp;
+    return launch_gemm(g, static_cast<hipStream_t>(stream));
+}
+
+size_t ptx_ln_linear_scratch_bytes(int n_out, int n_in)
+{
+    return n_out >= 1 && n_in >= 1 ? ((size_t)n_out * n_in + (size_t)n_out) * sizeof(float) : 0;
+}
+
+int ptx_ln_linear(const float *x, const float *lnp, const float *w, const float *gamma, const float *beta, const float *bias,
+                  float eps, int gelu, float *y, void *scratch, size_t scratch_bytes, int rows, int n_out, int n_in, void *stream)
+{
+    PTX_REQUIRE(x && lnp && w && gamma && beta && y && scratch, "ptx_ln_linear: null argument");
+    PTX_REQUIRE(rows >= 1 && n_out >= 1, "ptx_ln_linear: rows=%d n_out=%d", rows, n_out);
+    PTX_REQUIRE(n_in >= 32 && n_in % 32 == 0 && n_in <= 512, "ptx_ln_linear: n_in=%d must be a multiple of 32, at most 512", n_in);
+    PTX_REQUIRE(eps > 0.0f, "ptx_ln_linear: eps=%g", (double)eps);
+    PTX_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0 && scratch_bytes >= ptx_ln_linear_scratch_bytes(n_out, n_in),
+                "ptx_ln_linear: scratch of %zu bytes (16-byte aligned) needed", ptx_ln_linear_scratch_bytes(n_out, n_in));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *wg = static_cast<float *>(scratch), *cv = wg + (size_t)n_out * n_in;
+    PTX_TRY(launch_prep_lnfold(w, gamma, beta, bias, n_out, n_in, wg, cv, st));
+    GemmBatch g{}; g.n = 1;
+    g.p[0] = GemmProb{x, wg, y, nullptr, nullptr, nullptr, nullptr, rows, n_out, n_in, n_in, n_in, n_out, 0, 0, 0,
+                      gelu ? EPI_GELU : EPI_NONE};
+    g.p[0].lnp_in = lnp; g.p[0].ln_c = cv;
+    g.p[0].ln_parts = n_in / 32; g.p[0].ln_C = n_in; g.p[0].ln_eps = eps;
+    return launch_gemm(g, st);
 }
 
 int ptx_gemm_policy(int min_tiles_128) { return gemm_policy(min_tiles_128); }

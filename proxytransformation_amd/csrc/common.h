@@ -227,8 +227,8 @@ struct PrepLayout {
     size_t t1;                      // (heads, KT1, hd): scale * [WkWc | K-proj of (bc+pos_i)]
     size_t t2;                      // (heads, hd, KT2p): [WvWc | V-proj of (bc+pos_i)] (transposed)
     // LayerNorm folds (GemmProb::lnp_in): norm_img -> proxy_proj of the image block; norm2 -> fc1 of both blocks
-    size_t ppg_w, ppg_s, ppg_c;     // (C,C), (C), (C)
-    size_t fc1g_w[2], fc1g_s[2], fc1g_c[2];   // (hidden,C), (hidden), (hidden) for the text / image block
+    size_t ppg_w, ppg_c;            // (C,C), (C)
+    size_t fc1g_w[2], fc1g_c[2];    // (hidden,C), (hidden) for the text / image block
     size_t mlp_w1p[2], mlp_w2p[2];  // fused Mlp (mlp.hip): fc1g_w / fc2_w as three bf16 planes in MFMA fragment order
     size_t qkvb[2];                 // (Mk,3C): slot-bias rows through the qkv projection + its bias (the early-proxy path, api.hip)
     size_t total;                   // floats
@@ -254,7 +254,7 @@ struct WsLayout {
     size_t order_e;                        // clusters that enter the sampling, in its order (order_e: the ordering, computed beside k_select)
     size_t fm, qkv0, we, pool, gbuf, obuf, cbuf, img_proxy;
     size_t qkv[2], pt[2], pv[2], ao[2], x1[2], xn2[2], hbuf[2], x2[2], guide[2], head[2];
-    size_t lnp_img, lnp_x1[2];      // LayerNorm partials (rows, C/32, 2) of c_proj's / proj's output
+    size_t lnp_img, lnp_x1[2];      // LayerNorm partials (rows, C/32, 2) = (sum, M2 about the tile mean) per 32 columns of c_proj's / proj's output
     size_t fa_part;                 // (2, B*heads, split, Mk, 34) partial results of the split fused attention
     size_t mlp_part;                // (2, row tiles, 4, 32, 256) partial fc2 sums of the fused Mlp
     size_t total;
@@ -278,13 +278,15 @@ struct GemmProb {
     // `rs` is then a_h(0) = ct (gemm.hip, k_gemm32<SK, 1>)
     const float *pg, *pe, *pml; int ldg, gslab, lde, ldml, kg;
     // LayerNorm folded across a GEMM -> GEMM seam (no LayerNorm launch, no normalised copy of the rows):
-    //   producer (lnp_out != null): besides C, every 32-column tile writes the partial (sum, sum of squares) of its
-    //     rows' FINAL values to lnp_out[(row * ceil(N/32) + tile) * 2 + {0,1}];
-    //   consumer (lnp_in != null): A holds the RAW rows of the producer (width ln_C), W = W' diag(gamma), and the
-    //     epilogue applies  y = rstd_r (acc - mean_r s_n) + c_n  with s_n = sum_k W[n][k], c_n = W' beta + bias
-    //     (mean_r, rstd_r from the ln_parts partials of row r; `bias` must be null) -- LN(x) W'^T + b, reassociated.
+    //   producer (lnp_out != null): besides C, every 32-column tile writes the partial (sum, M2 = sum of squared distances from
+    //     the tile's own mean) of its rows' FINAL values over its columns inside N to lnp_out[(row * ceil(N/32) + tile) * 2 + {0,1}];
+    //   consumer (lnp_in != null): A holds the RAW rows of the producer (width ln_C = K = 32 ln_parts <= 512), W = W' diag(gamma);
+    //     mean_r, rstd_r come from the ln_parts partials of row r (Chan's combination: no E[x^2] - mean^2), the rows are centred on
+    //     their way into LDS and the epilogue applies  y = rstd_r acc + c_n,  acc = (x_r - mean_r) W^T,  c_n = W' beta + bias
+    //     (`bias` must be null) -- LN(x) W'^T + b without forming LN(x), and without a difference of two products |mean| / sigma
+    //     times the size of the answer.
     float *lnp_out;
-    const float *lnp_in, *ln_s, *ln_c; int ln_parts, ln_C; float ln_eps;
+    const float *lnp_in, *ln_c; int ln_parts, ln_C; float ln_eps;
     // Chained product (latency-regime kernel, 32-column tiles): the work-group of column tile t < chain_tiles multiplies
     // its finished 32 x 32 tile Y (rows x 32 columns) by a second weight table,  C2_t[r][m] = sum_k Y[r][k] W2_t[m][k]
     // (m < n2, K = 32), W2_t = w2 + t * w2_stride (row-major (n2,32)), C2_t = c2 + t * c2_stride -- the attention pool's
@@ -342,7 +344,7 @@ int launch_proxy_attn(const FAttnBatch &ab, hipStream_t st);
 struct MlpProb {
     const float *x1, *lnp;          // rows (R,256) and their LayerNorm partials (R,8,2) from the proj GEMM
     const void *w1p, *w2p;          // weight planes (k_prep_planes) of fc1 (with norm2's gamma folded in) and fc2
-    const float *fc1_s, *fc1_c, *b2;
+    const float *fc1_c, *b2;
     float *x2; int R;
     // the block's output head, applied by the work-group that finishes a row tile (k_heads' arithmetic; head_out = NULL: not)
     const float *nw, *nb, *hw, *hb, *ab; float *head_out, *guide; int nout;
@@ -353,6 +355,9 @@ size_t mlp_part_bytes(int R);
 size_t mlp_ticket_bytes(int R);
 int launch_mlp(const MlpBatch &mb, hipStream_t st);
 int launch_prep_planes(const float *W, int rows, int K, void *out, hipStream_t st);
+// the LayerNorm fold's tables (prep.hip, k_prep_lnfold): Wg (N,K) = W diag(gamma), cv (N) = W beta + bias
+int launch_prep_lnfold(const float *W, const float *gamma, const float *beta, const float *bias, int N, int K, float *Wg,
+                       float *cv, hipStream_t st);
 
 // Per-scene base pointers of the point clouds, passed by value as a kernel argument: the caller's
 // list of (N,3) tensors is used in place (the reference stacks them into a copy, PRE:426-427; the

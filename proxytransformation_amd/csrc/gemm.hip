@@ -22,7 +22,9 @@ constexpr int BK = 32, LDT = BK + 4;   // 144-B LDS rows: 16-B aligned, b128 fra
 // pure VALU work across s_barrier, which turns a three-steps-ahead prefetch into a wait on the loads just issued)
 __device__ __forceinline__ void pin4(float4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 // ---- LayerNorm fold helpers (GemmProb::lnp_out / lnp_in) ----------------------------------------------------------
-// consumer: mean / rstd of row `row` from the producer's per-tile partials
+// consumer: mean / rstd of row `row` from the producer's per-tile partials (sum, M2 about the tile's own mean; 32 columns each),
+// combined by Chan's formula for equal counts:  M2 = sum_t M2_t + 32 sum_t (m_t - mu)^2 = sum_t M2_t + sum_t (s_t - 32 mu)^2 / 32.
+// Nothing here is a difference of two numbers of the size of mu^2, as E[x^2] - mu^2 is for rows with |mu| >> sigma.
 __device__ __forceinline__ void ln_row_stats(const GemmProb &pr, int row, float &mu, float &rstd)
 {
     // (all partials are requested before the first is added: as a loop the compiler waited for each load before issuing the
@@ -37,12 +39,17 @@ __device__ __forceinline__ void ln_row_stats(const GemmProb &pr, int row, float 
     for (int t = 0; t < kMaxParts; ++t) { s1 += t < pr.ln_parts ? v[t].x : 0.0f; s2 += t < pr.ln_parts ? v[t].y : 0.0f; }
     const float inv = 1.0f / (float)pr.ln_C;
     mu = s1 * inv;
-    const float var = fmaxf(fmaf(-mu, mu, s2 * inv), 0.0f);
-    rstd = 1.0f / sqrtf(var + pr.ln_eps);
+    float between = 0.0f;
+#pragma unroll
+    for (int t = 0; t < kMaxParts; ++t) { const float d = t < pr.ln_parts ? fmaf(-32.0f, mu, v[t].x) : 0.0f; between = fmaf(d, d, between); }
+    rstd = 1.0f / sqrtf(fmaf(between, 1.0f / 32.0f, s2) * inv + pr.ln_eps);
 }
+// consumer: the A operand is centred on its way into LDS, (x - mu) Wg^T instead of x Wg^T - mu s: the product of a row with
+// |mu| >> sigma is then of the size of the answer, not two numbers |mu| / sigma times as large whose difference is the answer
+__device__ __forceinline__ void sub4(float4 &a, float mu) { a.x -= mu; a.y -= mu; a.z -= mu; a.w -= mu; }
 // producer: one wave holds the final values v[r] of a 32x32 tile in the MFMA C layout (col = lane & 31,
-// row = (r&3) + 8 (r>>2) + 4 (lane>>5)); scratch = 32 x 33 floats of wave-private LDS.  Writes the (sum, sum of
-// squares) of each row's 32 columns (invalid columns / rows contribute 0) to lnp_out[(row * parts + part) * 2].
+// row = (r&3) + 8 (r>>2) + 4 (lane>>5)); scratch = 32 x 33 floats of wave-private LDS.  Writes the (sum, M2 = sum of
+// squared distances from the tile's own mean) of each row's valid columns to lnp_out[(row * parts + part) * 2].
 __device__ __forceinline__ void ln_tile_partials(const GemmProb &pr, const float (&v)[16], float *scratch, int row0,
                                                  int part, int parts)
 {
@@ -51,13 +58,18 @@ __device__ __forceinline__ void ln_tile_partials(const GemmProb &pr, const float
     for (int r = 0; r < 16; ++r) scratch[((r & 3) + 8 * (r >> 2) + 4 * hh) * 33 + li] = v[r];
     // same wave: LDS operations complete in order, no barrier needed
     const float *rowp = scratch + li * 33 + 16 * hh;       // lane (li, hh) sums columns 16 hh .. 16 hh + 15 of row li
-    float s1 = 0.0f, s2 = 0.0f;
+    const int nvalid = min(32, pr.N - 32 * part);          // columns of this tile inside N (invalid ones hold 0)
+    float x[16], s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) { const float x = rowp[c]; s1 += x; s2 = fmaf(x, x, s2); }
+    for (int c = 0; c < 16; ++c) { x[c] = rowp[c]; s1 += x[c]; }
     s1 += __shfl_xor(s1, 32, 64);
+    const float mean = s1 / (float)max(nvalid, 1);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) { const float d = 16 * hh + c < nvalid ? x[c] - mean : 0.0f; s2 = fmaf(d, d, s2); }
     s2 += __shfl_xor(s2, 32, 64);
     const int row = row0 + li;
-    if (hh == 0 && row < pr.R)
+    // (part < parts, wave-uniform: the 64- and 128-column tiles hand a wave 32-column quadrants that can lie wholly past N)
+    if (hh == 0 && row < pr.R && part < parts)
         *reinterpret_cast<float2 *>(pr.lnp_out + ((size_t)row * parts + part) * 2) = make_float2(s1, s2);
 }
 
@@ -86,6 +98,7 @@ __device__ __forceinline__ void ln_tile_partials(const GemmProb &pr, const float
     } while (0)
 #define PTX_G64_STASH(S, buf_)                                                             \
     do {                                                                                   \
+        if (LN) { sub4(a##S##0, mu0); sub4(a##S##1, mu1); }                                \
         *reinterpret_cast<float4 *>(&As[buf_][sr][kq]) = a##S##0;                          \
         *reinterpret_cast<float4 *>(&As[buf_][sr + 32][kq]) = a##S##1;                     \
         *reinterpret_cast<float4 *>(&Ws[buf_][sr][kq]) = w##S##0;                          \
@@ -103,6 +116,7 @@ __device__ __forceinline__ void ln_tile_partials(const GemmProb &pr, const float
         }                                                                                  \
     } while (0)
 
+template <bool LN>      // LN: some group of the launch is a LayerNorm consumer (its A rows are centred in the stash)
 __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
 {
     const GemmProb pr = gb.p[blockIdx.z];          // by value: fields live in SGPRs, not re-read from kernarg
@@ -112,11 +126,7 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
     __shared__ __attribute__((aligned(16))) float Ws[2][64][LDT];
     __shared__ float s_mu[64], s_rs[64];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    if (pr.lnp_in != nullptr && tid < 64) {
-        float mu, rs;
-        ln_row_stats(pr, min(row0 + tid, pr.R - 1), mu, rs);
-        s_mu[tid] = mu; s_rs[tid] = rs;                    // read after the barriers of the K loop
-    }
+    const bool ln = LN && pr.lnp_in != nullptr;            // work-group uniform
     const int wr = wid >> 1, wc = wid & 1;
     const int li = lane & 31, hh = lane >> 5;
     const int sr = tid >> 3, kq = (tid & 7) * 4;        // staging: rows sr and sr + 32
@@ -139,6 +149,16 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
     }
     PTX_G64_FETCH(A, 0);
     PTX_G64_FETCH(B, 1);
+    float mu0 = 0.0f, mu1 = 0.0f;                          // means of this thread's two staging rows (0: nothing to centre)
+    if (ln) {                                              // behind the first tiles' requests
+        if (tid < 64) {
+            float mu, rs;
+            ln_row_stats(pr, min(row0 + tid, pr.R - 1), mu, rs);
+            s_mu[tid] = mu; s_rs[tid] = rs;
+        }
+        __syncthreads();
+        mu0 = s_mu[sr]; mu1 = s_mu[sr + 32];
+    }
     PTX_G64_STASH(A, 0);
     __syncthreads();
     for (int it = 0; it < nk; it += 2) {
@@ -154,14 +174,14 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
     }
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     const bool ncol = n < pr.N;
-    float lns = 0.0f, lnc = 0.0f;
-    if (pr.lnp_in != nullptr && ncol) { lns = pr.ln_s[n]; lnc = pr.ln_c[n]; }
+    float lnc = 0.0f;
+    if (ln && ncol) lnc = pr.ln_c[n];
     float fin[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh, row = row0 + rl;
         float v = acc[r] + bias;
-        if (pr.lnp_in != nullptr) v = fmaf(s_rs[rl], fmaf(-s_mu[rl], lns, acc[r]), lnc);
+        if (ln) v = fmaf(s_rs[rl], acc[r], lnc);
         if (pr.epi == EPI_GELU) v = gelu_erf(v);
         const bool ok = ncol && row < pr.R;
         if (ok) {
@@ -204,6 +224,7 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
 #define PTX_X64_STASH(S, buf_)                                                             \
     do {                                                                                   \
         pin4(a##S##0); pin4(a##S##1); pin4(w##S##0); pin4(w##S##1);                        \
+        if (LN) { sub4(a##S##0, mu0); sub4(a##S##1, mu1); }                                \
         char *d_ = smem + (buf_) * kXBuf + sr * XROW + xswz(sr, kq >> 3) + (kq & 4) * 2;   /* (sr + 32) swizzles alike */ \
         stash_parts<NP>(d_, kXPlane, a##S##0);                                             \
         stash_parts<NP>(d_ + 32 * XROW, kXPlane, a##S##1);                                 \
@@ -235,8 +256,9 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
         }                                                                                  \
     } while (0)
 
-template <int NKG, int REP, int NP = 3>   // K = 128 NKG REP: the written-out body runs REP times (one drain of the prefetch per
-                                         // repetition); NP = 3: split operands (fp32-equivalent), 1: plain bf16 operands
+template <int NKG, int REP, int NP = 3, bool LN = false>   // K = 128 NKG REP: the written-out body runs REP times (one drain of the
+                                         // prefetch per repetition); NP = 3: split operands (fp32-equivalent), 1: plain bf16 operands;
+                                         // LN: some group of the launch is a LayerNorm consumer (k_gemm64)
 __global__ __launch_bounds__(256) void k_gemm64x(GemmBatch gb)
 {
     constexpr int kXPlane = 64 * XROW, kXBuf = 6 * kXPlane;     // one plane of a 64 x 32 tile; [A1 A2 A3 W1 W2 W3] per buffer
@@ -247,6 +269,7 @@ __global__ __launch_bounds__(256) void k_gemm64x(GemmBatch gb)
     __shared__ __attribute__((aligned(16))) char smem[2 * kXBuf];
     __shared__ float s_mu[64], s_rs[64];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const bool ln = LN && pr.lnp_in != nullptr;            // work-group uniform
     const int wr = wid >> 1, wc = wid & 1;
     const int li = lane & 31, hh = lane >> 5;
     const int sr = tid >> 3, kq = (tid & 7) * 4;        // staging: rows sr and sr + 32
@@ -259,8 +282,8 @@ __global__ __launch_bounds__(256) void k_gemm64x(GemmBatch gb)
     // epilogue operands are requested up front: a dependent ~1 us round trip after the K loop otherwise
     const int n = col0 + wc * 32 + li;
     const float bias = (pr.bias && n < pr.N) ? pr.bias[n] : 0.0f;
-    float lns = 0.0f, lnc = 0.0f;                           // LayerNorm-consumer column terms: requested here, not after the K loop
-    if (pr.lnp_in != nullptr) { lns = pr.ln_s[min(n, pr.N - 1)]; lnc = pr.ln_c[min(n, pr.N - 1)]; }
+    float lnc = 0.0f;                                       // LayerNorm-consumer column term: requested here, not after the K loop
+    if (ln) lnc = pr.ln_c[min(n, pr.N - 1)];
     float resv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -288,10 +311,15 @@ __global__ __launch_bounds__(256) void k_gemm64x(GemmBatch gb)
     PTX_X64_FETCH(A, 0); PTX_X64_FETCH(B, 1); PTX_X64_FETCH(C, 2); PTX_X64_FETCH(D, 3);
     // (behind the first four tiles' requests: in front of them the statistics were a round trip of their own before the
     //  work-group's first wave had requested anything -- r03 stamps: 3 k of the 6.5 k cycles in front of the K loop)
-    if (pr.lnp_in != nullptr && tid < 64) {
-        float mu, rs;
-        ln_row_stats(pr, min(row0 + tid, pr.R - 1), mu, rs);
-        s_mu[tid] = mu; s_rs[tid] = rs;                    // read after the barriers of the K loop
+    float mu0 = 0.0f, mu1 = 0.0f;                          // means of this thread's two staging rows (0: nothing to centre)
+    if (ln) {
+        if (tid < 64) {
+            float mu, rs;
+            ln_row_stats(pr, min(row0 + tid, pr.R - 1), mu, rs);
+            s_mu[tid] = mu; s_rs[tid] = rs;
+        }
+        __syncthreads();
+        mu0 = s_mu[sr]; mu1 = s_mu[sr + 32];
     }
     PTX_X64_STASH(A, 0);
     __syncthreads();
@@ -313,7 +341,7 @@ __global__ __launch_bounds__(256) void k_gemm64x(GemmBatch gb)
     for (int r = 0; r < 16; ++r) {
         const int rl = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh, row = row0 + rl;
         float v = acc[r] + bias;
-        if (pr.lnp_in != nullptr) v = fmaf(s_rs[rl], fmaf(-s_mu[rl], lns, acc[r]), lnc);
+        if (ln) v = fmaf(s_rs[rl], acc[r], lnc);
         if (pr.epi == EPI_GELU) v = gelu_erf(v);
         const bool ok = ncol && row < pr.R;
         if (ok) {
@@ -382,6 +410,7 @@ constexpr int kYHalf = 128 * 16 + 64, kYPlane = 2 * kYHalf, kYBuf = 6 * kYPlane;
         float4 &pa_ = (h_) ? a##S##1 : a##S##0, &pb_ = (h_) ? a##S##3 : a##S##2;           \
         float4 &pc_ = (h_) ? w##S##1 : w##S##0, &pd_ = (h_) ? w##S##3 : w##S##2;           \
         pin4(pa_); pin4(pb_); pin4(pc_); pin4(pd_);                                        \
+        if (LN) { sub4(pa_, mu0); sub4(pb_, mu1); }                                        \
         char *d_ = smem + (buf_) * kYBuf + stash_off;                                      \
         stash_parts<NP>(d_, kYPlane, pa_);                                                 \
         stash_parts<NP>(d_ + 64 * 16, kYPlane, pb_);                                       \
@@ -414,8 +443,8 @@ constexpr int kYHalf = 128 * 16 + 64, kYPlane = 2 * kYHalf, kYBuf = 6 * kYPlane;
         }                                                                                  \
     } while (0)
 
-template <int NM, int NP = 3>     // K = 32 NM nrep: the written-out body of NM macro steps runs nrep times (one drain of the prefetch
-                                  // per repetition, like k_gemm64x's REP)
+template <int NM, int NP = 3, bool LN = false>     // K = 32 NM nrep: the written-out body of NM macro steps runs nrep times (one drain
+                                  // of the prefetch per repetition, like k_gemm64x's REP); LN: as in k_gemm64
 __global__ __launch_bounds__(256, 2) void k_gemm128x(GemmBatch gb, int nrep)
 {
     static_assert(NM >= 2 && NM % 2 == 0, "macro steps come in P / Q pairs");
@@ -454,10 +483,16 @@ __global__ __launch_bounds__(256, 2) void k_gemm128x(GemmBatch gb, int nrep)
     const int total = NM * nrep;
     PTX_Y_FETCH(P, 0);
     PTX_Y_FETCH(Q, 1);
-    if (pr.lnp_in != nullptr && tid < 128) {               // behind the first tiles' requests (k_gemm64x)
-        float mu, rs;
-        ln_row_stats(pr, min(row0 + tid, pr.R - 1), mu, rs);
-        s_mu[tid] = mu; s_rs[tid] = rs;
+    const bool ln = LN && pr.lnp_in != nullptr;            // work-group uniform
+    float mu0 = 0.0f, mu1 = 0.0f;                          // means of this thread's two staging rows (0: nothing to centre)
+    if (ln) {                                              // behind the first tiles' requests (k_gemm64x)
+        if (tid < 128) {
+            float mu, rs;
+            ln_row_stats(pr, min(row0 + tid, pr.R - 1), mu, rs);
+            s_mu[tid] = mu; s_rs[tid] = rs;
+        }
+        __syncthreads();
+        mu0 = s_mu[sr]; mu1 = s_mu[sr + 64];
     }
     PTX_Y_STASH(P, 0, 0);
     __syncthreads();
@@ -505,8 +540,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm128x(GemmBatch gb, int nrep)
         const int n = col0 + wc * 64 + j * 32 + li, nc = min(n, pr.N - 1);
         const bool ncol = n < pr.N;
         const float bias = pr.bias ? pr.bias[nc] : 0.0f;
-        float lns = 0.0f, lnc = 0.0f;
-        if (pr.lnp_in != nullptr) { lns = pr.ln_s[nc]; lnc = pr.ln_c[nc]; }
+        float lnc = 0.0f;
+        if (ln) lnc = pr.ln_c[nc];
         float resv[16], adv[16], rsv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -520,7 +555,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm128x(GemmBatch gb, int nrep)
         for (int r = 0; r < 16; ++r) {
             const int rl = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh, row = row0 + rl;
             float v = acc[q][r] + bias;
-            if (pr.lnp_in != nullptr) v = fmaf(s_rs[rl], fmaf(-s_mu[rl], lns, acc[q][r]), lnc);
+            if (ln) v = fmaf(s_rs[rl], acc[q][r], lnc);
             if (pr.epi == EPI_GELU) v = gelu_erf(v);
             const bool ok = ncol && row < pr.R;
             if (pr.rs) v = fmaf(rsv[r], adv[r], v);
@@ -546,7 +581,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm128x(GemmBatch gb, int nrep)
 // basic block and hipcc interleaves the next tile's global loads with the MFMAs.
 // blockIdx.x = row tile: work-groups that share an A row-panel land on the same XCD (b % 8)
 // whenever the row-tile count is a multiple of 8.
-template <int SK, int AMODE, bool CHAIN = false>   // AMODE 1: A merged on the fly from the k_img_pool tiles; CHAIN: see GemmProb::w2
+template <int SK, int AMODE, bool CHAIN = false, bool LN = false>   // AMODE 1: A merged on the fly from the k_img_pool tiles; CHAIN: see
+                                                                    // GemmProb::w2; LN: as in k_gemm64
 __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
 {
     const GemmProb pr = gb.p[blockIdx.z];
@@ -574,7 +610,9 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
     size_t g0 = 0, g1 = 0, g2 = 0, g3 = 0, e0 = 0, e1 = 0, e2 = 0, e3 = 0;
     float fc0[4] = {0.f, 0.f, 0.f, 0.f}, fc1[4] = {0.f, 0.f, 0.f, 0.f}, fct[4] = {0.f, 0.f, 0.f, 0.f};
     float *cts = lds + (size_t)SK * (4 * 32 * LDT);         // [32] a_h(0) of the tile's rows (AMODE 1)
-    float *lnst = cts + 32;                                 // [32][2] mean, rstd of the tile's rows (LayerNorm consumer)
+    float *lnst = cts + 32 + wv * 64;                       // [32][2] mean, rstd of the tile's rows (LayerNorm consumer), per wave
+    const bool ln = LN && pr.lnp_in != nullptr;             // work-group uniform
+    float mu4[4] = {0.0f, 0.0f, 0.0f, 0.0f};                // means of this lane's four staging rows (0: nothing to centre)
     if (AMODE == 1) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -642,6 +680,7 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
     do {                                                                                  \
         float *A_s = base + (buf_) * (2 * 32 * LDT) + r0 * LDT + kq, *W_s = A_s + 32 * LDT; \
         if (AMODE == 1) { PTX_MERGE(S, 0); PTX_MERGE(S, 1); PTX_MERGE(S, 2); PTX_MERGE(S, 3); } \
+        if (LN) { sub4(a##S##0, mu4[0]); sub4(a##S##1, mu4[1]); sub4(a##S##2, mu4[2]); sub4(a##S##3, mu4[3]); } \
         *reinterpret_cast<float4 *>(A_s) = a##S##0;                                       \
         *reinterpret_cast<float4 *>(A_s + 8 * LDT) = a##S##1;                             \
         *reinterpret_cast<float4 *>(A_s + 16 * LDT) = a##S##2;                            \
@@ -667,14 +706,14 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
     // each would be a dependent round trip -- and the row-scaled addend was one PER OUTPUT ROW, sixteen in sequence, because a
     // load behind the previous row's store cannot be hoisted above it (r03)
     const int n = col0 + li;
-    float bias = 0.0f, lns = 0.0f, lnc = 0.0f, resv[16], adv[16], rsv[16];
+    float bias = 0.0f, lnc = 0.0f, resv[16], adv[16], rsv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { resv[r] = 0.0f; adv[r] = 0.0f; rsv[r] = 0.0f; }
     const bool has_ad = AMODE == 1 || pr.rs != nullptr;      // work-group uniform
     if (wv == 0) {
         const int nc = min(n, pr.N - 1);
         if (pr.bias) bias = pr.bias[nc];
-        if (pr.lnp_in != nullptr) { lns = pr.ln_s[nc]; lnc = pr.ln_c[nc]; }
+        if (ln) lnc = pr.ln_c[nc];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * hh, pr.R - 1);
@@ -695,11 +734,16 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
         // three stages: step j in LDS[cur], step j+1 in LDS[cur^1], step j+2 in flight (registers)
         PTX_FETCH(A, 0);
         PTX_FETCH(B, 1);
-        // LayerNorm-consumer row statistics (wave 0 only, which also reads them): requested behind the first two tiles
-        if (pr.lnp_in != nullptr && wv == 0 && lane < 32) {
-            float mu, rs;
-            ln_row_stats(pr, min(row0 + lane, pr.R - 1), mu, rs);
-            lnst[2 * lane] = mu; lnst[2 * lane + 1] = rs;
+        // LayerNorm-consumer row statistics, requested behind the first two tiles: every K slice centres the rows it stages, so
+        // every wave works them out for itself (its own LDS words: a wave's LDS operations execute in order, no barrier)
+        if (ln) {
+            if (lane < 32) {
+                float mu, rs;
+                ln_row_stats(pr, min(row0 + lane, pr.R - 1), mu, rs);
+                lnst[2 * lane] = mu; lnst[2 * lane + 1] = rs;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mu4[i] = lnst[2 * (r0 + 8 * i)];
         }
         // (a fourth stage -- a third register set, fetches three MFMA phases ahead -- for the pooled-A o-projection, whose K
         //  steps take 3.1 k cycles for 1 k of MFMA time next to the clustering stream's tail: 20.6 vs 21.8 us in the trace, no
@@ -745,7 +789,7 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
         for (int r = 0; r < 16; ++r) {
             const int rl = (r & 3) + 8 * (r >> 2) + 4 * hh, row = row0 + rl;
             float v = acc[r] + bias;
-            if (pr.lnp_in != nullptr) v = fmaf(lnst[2 * rl + 1], fmaf(-lnst[2 * rl], lns, acc[r]), lnc);
+            if (ln) v = fmaf(lnst[2 * rl + 1], acc[r], lnc);
             if (pr.epi == EPI_GELU) v = gelu_erf(v);
             const bool ok = ncol && row < pr.R;
             if (ok) {
@@ -817,14 +861,14 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
     }
 }
 
-template <int SK, int AMODE, bool CHAIN = false>
+template <int SK, int AMODE, bool CHAIN = false, bool LN = false>
 static int launch_gemm32(const GemmBatch &gb, int rmax, int nmax, hipStream_t st)
 {
-    const size_t lds = sizeof(float) * (SK * 4 * 32 * LDT + 32 + 64);
+    const size_t lds = sizeof(float) * (SK * 4 * 32 * LDT + 32 + 64 * SK);
     if (lds > 64 * 1024)
-        PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm32<SK, AMODE, CHAIN>),
+        PTX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gemm32<SK, AMODE, CHAIN, LN>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_gemm32<SK, AMODE, CHAIN>), dim3(cdiv(rmax, 32), cdiv(nmax, 32), gb.n), dim3(SK * 64), lds, st, gb);
+    hipLaunchKernelGGL((k_gemm32<SK, AMODE, CHAIN, LN>), dim3(cdiv(rmax, 32), cdiv(nmax, 32), gb.n), dim3(SK * 64), lds, st, gb);
     return PTX_OK;
 }
 
@@ -842,6 +886,7 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
     PTX_REQUIRE(gb.n >= 1 && gb.n <= kMaxGroups, "gemm: %d groups", gb.n);
     int rmax = 0, nmax = 0, kmin = 1 << 30, kmax = 0;
     long tiles32 = 0;
+    bool any_ln = false;                // a LayerNorm consumer among the groups: the kernel variants that centre the A rows
     for (int g = 0; g < gb.n; ++g) {
         const GemmProb &p = gb.p[g];
         PTX_REQUIRE((p.A || p.pg) && p.W && p.C, "gemm: null operand in group %d", g);
@@ -856,8 +901,10 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
                       reinterpret_cast<uintptr_t>(p.pe)) & 15) == 0,
                     "gemm: operands of group %d are not 16-byte aligned", g);
         PTX_REQUIRE(p.rs == nullptr || p.ad != nullptr, "gemm: row scale without addend");
-        PTX_REQUIRE(p.lnp_in == nullptr || (p.ln_s && p.ln_c && p.ln_parts >= 1 && p.ln_C >= 1 && p.bias == nullptr),
+        PTX_REQUIRE(p.lnp_in == nullptr || (p.ln_c && p.ln_parts >= 1 && p.ln_parts <= 16 && p.ln_C == 32 * p.ln_parts &&
+                                            p.K == p.ln_C && p.pg == nullptr && p.bias == nullptr),
                     "gemm: bad LayerNorm-consumer description in group %d", g);
+        any_ln = any_ln || p.lnp_in != nullptr;
         rmax = p.R > rmax ? p.R : rmax;
         nmax = p.N > nmax ? p.N : nmax;
         kmin = p.K < kmin ? p.K : kmin;
@@ -866,7 +913,7 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
     }
     if (gb.p[0].w2 != nullptr) {
         PTX_REQUIRE(gb.n == 1 && gb.p[0].pg == nullptr && gb.p[0].c2 && gb.p[0].n2 >= 1 && gb.p[0].chain_tiles >= 1 &&
-                    gb.p[0].chain_tiles * 32 <= gb.p[0].N && gb.p[0].K >= 4 * BK && gb.p[0].lnp_out == nullptr,
+                    gb.p[0].chain_tiles * 32 <= gb.p[0].N && gb.p[0].K >= 4 * BK && gb.p[0].lnp_out == nullptr && !any_ln,
                     "gemm: bad chained-product description");
         PTX_TRY((launch_gemm32<4, 0, true>(gb, rmax, nmax, st)));
         PTX_LAUNCHED("k_gemm");
@@ -888,8 +935,13 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
     if (use128) {
         const dim3 grid(cdiv(rmax, 128), cdiv(nmax, 128), gb.n);
         const int nrep = kmin / (32 * PTX_G128_NM);
-        if (compute_dtype == 1) hipLaunchKernelGGL((k_gemm128x<PTX_G128_NM, 1>), grid, dim3(256), 0, st, gb, nrep);
-        else                    hipLaunchKernelGGL((k_gemm128x<PTX_G128_NM, 3>), grid, dim3(256), 0, st, gb, nrep);
+        if (compute_dtype == 1) {
+            if (any_ln) hipLaunchKernelGGL((k_gemm128x<PTX_G128_NM, 1, true>), grid, dim3(256), 0, st, gb, nrep);
+            else        hipLaunchKernelGGL((k_gemm128x<PTX_G128_NM, 1>), grid, dim3(256), 0, st, gb, nrep);
+        } else {
+            if (any_ln) hipLaunchKernelGGL((k_gemm128x<PTX_G128_NM, 3, true>), grid, dim3(256), 0, st, gb, nrep);
+            else        hipLaunchKernelGGL((k_gemm128x<PTX_G128_NM, 3>), grid, dim3(256), 0, st, gb, nrep);
+        }
         PTX_LAUNCHED("k_gemm128x");
         return PTX_OK;
     }
@@ -897,7 +949,12 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
         // reduced-precision mode: plain bf16 operands, fp32 accumulation, the 64 x 64-tile kernel at every size
         const dim3 grid(cdiv(rmax, 64), cdiv(nmax, 64), gb.n);
         const int nkg = kmin / 128;
-        if (nkg == 1) hipLaunchKernelGGL((k_gemm64x<1, 1, 1>), grid, dim3(256), 0, st, gb);
+        // (a LayerNorm consumer has K = ln_C <= 512: nkg 1, 2, 4; K = 384 is PTX_EINVAL in this mode like every other nkg not listed)
+        if (any_ln && nkg == 1) hipLaunchKernelGGL((k_gemm64x<1, 1, 1, true>), grid, dim3(256), 0, st, gb);
+        else if (any_ln && nkg == 2) hipLaunchKernelGGL((k_gemm64x<2, 1, 1, true>), grid, dim3(256), 0, st, gb);
+        else if (any_ln && nkg == 4) hipLaunchKernelGGL((k_gemm64x<4, 1, 1, true>), grid, dim3(256), 0, st, gb);
+        else if (any_ln) { set_error("gemm: LayerNorm consumer with K=%d in bf16 mode", kmin); return PTX_EINVAL; }
+        else if (nkg == 1) hipLaunchKernelGGL((k_gemm64x<1, 1, 1>), grid, dim3(256), 0, st, gb);
         else if (nkg == 2) hipLaunchKernelGGL((k_gemm64x<2, 1, 1>), grid, dim3(256), 0, st, gb);
         else if (nkg == 4) hipLaunchKernelGGL((k_gemm64x<4, 1, 1>), grid, dim3(256), 0, st, gb);
         else if (nkg == 8) hipLaunchKernelGGL((k_gemm64x<8, 1, 1>), grid, dim3(256), 0, st, gb);
@@ -913,7 +970,12 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
         // enough tiles to fill the chip: 64x64 tiles re-use each staged operand twice as often
         const dim3 grid(cdiv(rmax, 64), cdiv(nmax, 64), gb.n);
         const int nkg = (kmin == kmax && kmin % 128 == 0) ? kmin / 128 : 0;
-        if (nkg == 1) hipLaunchKernelGGL((k_gemm64x<1, 1>), grid, dim3(256), 0, st, gb);
+        // (a LayerNorm consumer has K = ln_C <= 512: nkg 1, 2, 4 on the split kernel, anything else on the fp32 instruction)
+        if (any_ln && nkg == 1) hipLaunchKernelGGL((k_gemm64x<1, 1, 3, true>), grid, dim3(256), 0, st, gb);
+        else if (any_ln && nkg == 2) hipLaunchKernelGGL((k_gemm64x<2, 1, 3, true>), grid, dim3(256), 0, st, gb);
+        else if (any_ln && nkg == 4) hipLaunchKernelGGL((k_gemm64x<4, 1, 3, true>), grid, dim3(256), 0, st, gb);
+        else if (any_ln) hipLaunchKernelGGL(k_gemm64<true>, grid, dim3(256), 0, st, gb);
+        else if (nkg == 1) hipLaunchKernelGGL((k_gemm64x<1, 1>), grid, dim3(256), 0, st, gb);
         else if (nkg == 2) hipLaunchKernelGGL((k_gemm64x<2, 1>), grid, dim3(256), 0, st, gb);
         else if (nkg == 4) hipLaunchKernelGGL((k_gemm64x<4, 1>), grid, dim3(256), 0, st, gb);
         else if (nkg == 8) hipLaunchKernelGGL((k_gemm64x<8, 1>), grid, dim3(256), 0, st, gb);
@@ -921,13 +983,17 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
         else if (nkg == 12) hipLaunchKernelGGL((k_gemm64x<4, 3>), grid, dim3(256), 0, st, gb);
         else if (nkg == 16) hipLaunchKernelGGL((k_gemm64x<8, 2>), grid, dim3(256), 0, st, gb);       // embed_dim 512: hidden = 2048
         else if (nkg == 32) hipLaunchKernelGGL((k_gemm64x<8, 4>), grid, dim3(256), 0, st, gb);
-        else hipLaunchKernelGGL(k_gemm64, grid, dim3(256), 0, st, gb);      // fp32 matrix instruction, any K
+        else hipLaunchKernelGGL(k_gemm64<false>, grid, dim3(256), 0, st, gb);      // fp32 matrix instruction, any K
     } else {
         // latency regime: aim for >= 4 waves per SIMD (4096 waves) by slicing K inside the work-group
         const int nk = cdiv(kmin, BK);
         int sk = 1;
         while (sk < 4 && tiles32 * sk < 4096 && nk >= 4 * sk) sk *= 2;
-        if (sk == 1) PTX_TRY((launch_gemm32<1, 0>(gb, rmax, nmax, st)));
+        if (any_ln) {
+            if (sk == 1) PTX_TRY((launch_gemm32<1, 0, false, true>(gb, rmax, nmax, st)));
+            else if (sk == 2) PTX_TRY((launch_gemm32<2, 0, false, true>(gb, rmax, nmax, st)));
+            else PTX_TRY((launch_gemm32<4, 0, false, true>(gb, rmax, nmax, st)));
+        } else if (sk == 1) PTX_TRY((launch_gemm32<1, 0>(gb, rmax, nmax, st)));
         else if (sk == 2) PTX_TRY((launch_gemm32<2, 0>(gb, rmax, nmax, st)));
         else PTX_TRY((launch_gemm32<4, 0>(gb, rmax, nmax, st)));
     }

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(kMlpWaves * 64) __attribute__((amdgpu_waves_per_eu(
         for (int t = 0; t < 8; ++t) lp[t] = pp[t];
     }
     const int j = sl * kMlpSlice + 32 * wv + li;                    // this lane's hidden unit in phase 1
-    const float s_j = p.fc1_s[j], c_j = p.fc1_c[j];
+    const float c_j = p.fc1_c[j];
     const u32x4 *W1 = reinterpret_cast<const u32x4 *>(p.w1p), *W2 = reinterpret_cast<const u32x4 *>(p.w2p);
     const int t1 = sl * (kMlpSlice / 32) + wv;                      // row tile of fc1's weight: 32 hidden units
     auto load_b = [&](const u32x4 *W, int t, int steps, int step, u32x4 (&b)[3]) {
@@ -124,19 +124,25 @@ __global__ __launch_bounds__(kMlpWaves * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
     for (int s = 0; s < kAhead; ++s) load_b(W1, t1, 16, s, bq[s]);
 
-    // ---- the x1 tile -> three bf16 planes (A operand of phase 1); row statistics
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int e = tid + 512 * i, row = e >> 6, k = (e & 63) * 4;
-        stash_parts<NP>(Xp + mlp_a_off(0, k >> 4, (k >> 3) & 1, row) + (k & 4) * 2, kMlpPlane, xv[i]);
-    }
+    // ---- row statistics from the producer's (sum, M2 about the tile mean) partials, combined as in gemm.hip's ln_row_stats
     if (tid < 32) {
-        float s1 = 0.0f, s2 = 0.0f;
+        float s1 = 0.0f, s2 = 0.0f, between = 0.0f;
 #pragma unroll
         for (int t = 0; t < 8; ++t) { s1 += lp[t].x; s2 += lp[t].y; }
         const float mu = s1 * (1.0f / 256.0f);
-        const float var = fmaxf(fmaf(-mu, mu, s2 * (1.0f / 256.0f)), 0.0f);
-        s_mu[tid] = mu; s_rs[tid] = 1.0f / sqrtf(var + mb.ln_eps);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) { const float d = fmaf(-32.0f, mu, lp[t].x); between = fmaf(d, d, between); }
+        s_mu[tid] = mu; s_rs[tid] = 1.0f / sqrtf(fmaf(between, 1.0f / 32.0f, s2) * (1.0f / 256.0f) + mb.ln_eps);
+    }
+    __syncthreads();
+    // ---- the x1 tile, centred (x - mean: the product is then of the size of the answer also for rows with |mean| >> sigma)
+    //      -> three bf16 planes (A operand of phase 1)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + 512 * i, row = e >> 6, k = (e & 63) * 4;
+        const float mu = s_mu[row];                                 // wave-uniform row
+        const float4 xc = make_float4(xv[i].x - mu, xv[i].y - mu, xv[i].z - mu, xv[i].w - mu);
+        stash_parts<NP>(Xp + mlp_a_off(0, k >> 4, (k >> 3) & 1, row) + (k & 4) * 2, kMlpPlane, xc);
     }
     __syncthreads();
 
@@ -166,7 +172,7 @@ __global__ __launch_bounds__(kMlpWaves * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = mlp_acc_row(r, hh);
-            h[r] = gelu_erf(fmaf(s_rs[row], fmaf(-s_mu[row], s_j, acc[r]), c_j));
+            h[r] = gelu_erf(fmaf(s_rs[row], acc[r], c_j));
         }
         if (LITE) __syncthreads();                                  // every wave is done reading the x1 planes H overwrites
         // column j of H is k = 32 wv + li of phase 2: step 2 wv + (li >> 4), half (li >> 3) & 1, position li & 7
@@ -300,7 +306,7 @@ int launch_mlp(const MlpBatch &mb, hipStream_t st)
     int rmax = 0;
     for (int g = 0; g < mb.n; ++g) {
         const MlpProb &p = mb.p[g];
-        PTX_REQUIRE(p.x1 && p.lnp && p.w1p && p.w2p && p.fc1_s && p.fc1_c && p.b2 && p.x2 && p.R >= 1, "fused mlp: null operand in group %d", g);
+        PTX_REQUIRE(p.x1 && p.lnp && p.w1p && p.w2p && p.fc1_c && p.b2 && p.x2 && p.R >= 1, "fused mlp: null operand in group %d", g);
         PTX_REQUIRE(p.R == mb.p[0].R, "fused mlp: the groups must have the same number of rows");
         rmax = p.R;
     }

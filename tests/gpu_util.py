@@ -126,3 +126,65 @@ class Stages:
                                                self.stream), "ptx_affine_compact")
         n = counts.cpu().tolist()
         return [out[b, :n[b]] for b in range(points.shape[0])]
+
+
+# ---- the LayerNorm -> Linear seam as operators (ptx_linear_ln_partials / ptx_ln_linear) and the plain ptx_linear ----------
+GUARD_WORD = 0x5a5a5a5a
+
+
+def _ptr(x):
+    return None if x is None else x.data_ptr()
+
+
+def linear(x, w, b=None, res=None, gelu=0):
+    lib = _abi.lib()
+    R, K = x.shape
+    N = w.shape[0]
+    y = torch.empty((R, N), dtype=torch.float32, device=x.device)
+    _abi.check(lib.ptx_linear(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(res), y.data_ptr(), R, N, K, gelu,
+                              torch.cuda.current_stream().cuda_stream), "ptx_linear")
+    return y
+
+
+def linear_ln_partials(x, w, b=None, res=None, guard_floats=1024):
+    """Producer: y = x w^T + b (+ res) and the per-row, per-32-column-tile LayerNorm partials of y.  Returns (y, lnp (R, parts, 2),
+    guard): the partials buffer is NaN on entry and is followed by `guard_floats` sentinel words, returned as the int32 view
+    `guard` (every word must still be GUARD_WORD afterwards)."""
+    lib = _abi.lib()
+    R, K = x.shape
+    N = w.shape[0]
+    parts = (N + 31) // 32
+    y = torch.empty((R, N), dtype=torch.float32, device=x.device)
+    buf = torch.full((R * parts * 2 + guard_floats,), float("nan"), dtype=torch.float32, device=x.device)
+    guard = buf[R * parts * 2:].view(torch.int32)
+    guard.fill_(GUARD_WORD)
+    _abi.check(lib.ptx_linear_ln_partials(x.data_ptr(), w.data_ptr(), _ptr(b), _ptr(res), y.data_ptr(), buf.data_ptr(), R, N, K,
+                                          torch.cuda.current_stream().cuda_stream), "ptx_linear_ln_partials")
+    return y, buf[:R * parts * 2].view(R, parts, 2), guard
+
+
+def ln_linear(x, lnp, w, gamma, beta, b=None, eps=1e-5, gelu=0):
+    """Consumer: Linear(LayerNorm(x)) [-> GELU] from the raw rows and the producer's partials."""
+    lib = _abi.lib()
+    R, C = x.shape
+    N = w.shape[0]
+    nbytes = lib.ptx_ln_linear_scratch_bytes(N, C)
+    scratch = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+    y = torch.empty((R, N), dtype=torch.float32, device=x.device)
+    _abi.check(lib.ptx_ln_linear(x.data_ptr(), lnp.data_ptr(), w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(b), eps, gelu,
+                                 y.data_ptr(), scratch.data_ptr(), nbytes, R, N, C, torch.cuda.current_stream().cuda_stream),
+               "ptx_ln_linear")
+    return y
+
+
+class gemm_policy:
+    """with gemm_policy(1): ...   -- ptx_gemm_policy for the duration of the block (0: never 128 x 128 tiles, 1: whenever legal)."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        self.prev = _abi.lib().ptx_gemm_policy(self.value)
+
+    def __exit__(self, *exc):
+        _abi.lib().ptx_gemm_policy(self.prev)

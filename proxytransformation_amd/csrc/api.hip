@@ -26,7 +26,7 @@ void set_error(const char *fmt, ...)
 // One launch site of the forward can be bracketed by HIP events recorded on the stream the kernel
 // is launched on; ptx_timing_read() returns launches and summed milliseconds.  Off by default.
 // img_pass2 / img_pass3 are the launch sites after the mean pass: k_img_pool (no third launch) for bf16 / fp16
-// features of the path's shape, k_img_scores / k_img_gather for fp32, k_img_scores16 / k_img_gather16 otherwise.
+// features of the path's shape, k_img_pool32 for fp32 features of that shape, k_img_scores / k_img_gather otherwise.
 // (k_gemm_nt[we]: from ~4000 images per call on and at head_dim 64; k_ln_rows[norm_img]: debug / stage API; k_attn32[...]: head_dim 64,
 //  more than 256 proxies, few (scene, head) pairs -- every site is live on some shape; the gate sites are the one-wave fork / join
 //  launches of the stream gates.)
@@ -465,7 +465,7 @@ static int gate_probe(PtxContext *c, hipStream_t st)
     return PTX_OK;
 }
 
-static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *prep, const void *img_any,
+static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *prep, const void *img,
                          float *img_proxy, void *ws, hipStream_t st, int phase = 0, bool need_ln = true,
                          int i0 = 0, int ni = -1, uint32_t *gate = nullptr, uint32_t gate_seq = 0)
 {
@@ -478,8 +478,7 @@ static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *pr
     float *obuf = at<float>(ws, L.obuf) + (size_t)i0 * C, *cbuf = at<float>(ws, L.cbuf) + (size_t)i0 * C;
     if (img_proxy) img_proxy += (size_t)i0 * C;
     const int dt = s.img_dtype;
-    img_any = static_cast<const char *>(img_any) + (size_t)i0 * s.in_dim * s.hw * (dt == 0 ? 4 : 2);
-    const float *img = static_cast<const float *>(img_any);
+    img = static_cast<const char *>(img) + (size_t)i0 * s.in_dim * s.hw * (dt == 0 ? 4 : 2);
     float *Gs = nullptr, *E = nullptr, *ML = nullptr;
     const int EW = P.KT2p - s.in_dim;
     const bool pooled32 = img_pool32_supported(dt, s.in_dim, s.hw, s.heads);        // r05: fp32 features in two passes, not three
@@ -488,10 +487,7 @@ static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *pr
         img_pool_layout(at<float>(ws, L.pool), nall, s.in_dim, EW, &Gs, &E, &ML);
         Gs += (size_t)i0 * 2 * s.heads * s.in_dim; E += (size_t)i0 * s.heads * EW; ML += (size_t)i0 * s.heads * 5;
     }
-    if (phase != 2) {
-        if (dt == 0) PTX_TIMED(KID_IMG_MEAN, st, launch_img_mean(img, nimg, s.in_dim, s.hw, fm, st, gate, gate_seq));
-        else PTX_TIMED(KID_IMG_MEAN, st, launch_img_mean16(img_any, dt, nimg, s.in_dim, s.hw, fm, st, gate, gate_seq));
-    }
+    if (phase != 2) PTX_TIMED(KID_IMG_MEAN, st, launch_img_mean(img, dt, nimg, s.in_dim, s.hw, fm, st, gate, gate_seq));
     if (phase == 1) return PTX_OK;
     // head_dim 32: a 32-column tile of the qkv0 GEMM IS one head's q, and the work-group that finishes it goes on to that
     // head's [w_h | e_h] = q_h T1_h^T (GemmProb::w2): one launch (and one boundary) less on the image chain
@@ -520,18 +516,15 @@ static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *pr
         }
     }
     if (pooled32) {
-        PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool32(img, we, qkv0, nimg, s.in_dim, s.hw, C, P.KT1, EW, attn_scale(hd), Gs, E, ML, st));
-    } else if (dt == 0) {
-        PTX_TIMED(KID_IMG_SCORES, st, launch_img_scores(img, we, qkv0, nimg, s.in_dim, s.hw, s.heads, C, P.KT1,
-                                                        P.KT2p, attn_scale(hd), gbuf, st));
-        PTX_TIMED(KID_IMG_GATHER, st, launch_img_gather(img, nimg, s.in_dim, s.hw, s.heads, P.KT2p, gbuf, st));
+        PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool32(static_cast<const float *>(img), we, qkv0, nimg, s.in_dim, s.hw, C, P.KT1, EW,
+                                                        attn_scale(hd), Gs, E, ML, st));
     } else if (pooled) {
-        PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool(img_any, dt, we, qkv0, nimg, s.in_dim, s.hw, C, P.KT1,
+        PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool(img, dt, we, qkv0, nimg, s.in_dim, s.hw, C, P.KT1,
                                                       EW, attn_scale(hd), Gs, E, ML, st));
     } else {
-        PTX_TIMED(KID_IMG_SCORES, st, launch_img_scores16(img_any, dt, we, qkv0, nimg, s.in_dim, s.hw, s.heads, C,
-                                                          P.KT1, P.KT2p, attn_scale(hd), gbuf, st));
-        PTX_TIMED(KID_IMG_GATHER, st, launch_img_gather16(img_any, dt, nimg, s.in_dim, s.hw, s.heads, P.KT2p, gbuf, st));
+        PTX_TIMED(KID_IMG_SCORES, st, launch_img_scores(img, dt, we, qkv0, nimg, s.in_dim, s.hw, s.heads, C, P.KT1,
+                                                        P.KT2p, attn_scale(hd), gbuf, st));
+        PTX_TIMED(KID_IMG_GATHER, st, launch_img_gather(img, dt, nimg, s.in_dim, s.hw, s.heads, P.KT2p, gbuf, st));
     }
     for (int h0 = 0; h0 < s.heads; h0 += kMaxGroups) {   // per head: o_h = [g_h | a_h] T2_h^T + a_h(0) v0_h + bv_h
         GemmBatch g{}; g.n = std::min(kMaxGroups, s.heads - h0);

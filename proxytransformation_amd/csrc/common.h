@@ -415,20 +415,13 @@ int launch_affine(const PtxShape &s, const ScenePts &points, uint32_t *tag, cons
                   const uint32_t *poison = nullptr);
 
 // ---- image proxy (imgproxy.hip) ------------------------------------------------------------
-int launch_img_mean(const float *img, int nimg, int in_dim, int hw, float *fm, hipStream_t st,
+// img: the features in their storage type dt (PtxShape.img_dtype: 0 fp32, 1 bf16, 2 fp16)
+int launch_img_mean(const void *img, int dt, int nimg, int in_dim, int hw, float *fm, hipStream_t st,
                     uint32_t *gate = nullptr, uint32_t gate_seq = 0);
-int launch_img_scores(const float *img, const float *we, const float *qkv0, int nimg, int in_dim,
-                      int hw, int heads, int C, int KT1, int KT2p, float scale, float *gbuf,
+int launch_img_scores(const void *img, int dt, const float *we, const float *qkv0, int nimg, int in_dim,
+                      int hw, int heads, int C, int KT1, int KT2p, float scale, float *gbuf, hipStream_t st);
+int launch_img_gather(const void *img, int dt, int nimg, int in_dim, int hw, int heads, int KT2p, float *gbuf,
                       hipStream_t st);
-int launch_img_gather(const float *img, int nimg, int in_dim, int hw, int heads, int KT2p,
-                      float *gbuf, hipStream_t st);
-
-int launch_img_mean16(const void *img, int dt, int nimg, int in_dim, int hw, float *fm, hipStream_t st,
-                      uint32_t *gate = nullptr, uint32_t gate_seq = 0);
-int launch_img_scores16(const void *img, int dt, const float *we, const float *qkv0, int nimg, int in_dim,
-                        int hw, int heads, int C, int KT1, int KT2p, float scale, float *gbuf, hipStream_t st);
-int launch_img_gather16(const void *img, int dt, int nimg, int in_dim, int hw, int heads, int KT2p, float *gbuf,
-                        hipStream_t st);
 // imgpool.hip: single-pass attention pooling of bf16 / fp16 features (scores + softmax numerators + weighted sums)
 bool img_pool_supported(int dt, int in_dim, int hw, int heads);
 size_t img_pool_bytes(int nimg, int in_dim, int EW);

@@ -28,12 +28,10 @@
 #include <hip/hip_ext.h>
 
 #include "common.h"
+#include "imgstore.h"
 
 namespace ptx {
 
-typedef unsigned int u4u2 __attribute__((ext_vector_type(4), aligned(2)));    // 16-B load at 2-B alignment
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kPoolHeads = 8;

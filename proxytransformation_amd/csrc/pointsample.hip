@@ -10,18 +10,9 @@
 // workspace); k_point_sample then runs one wave per point: lanes = views for the projection (ballot of the views that
 // hit a pixel), lanes = channels for the gather (256 B contiguous per view and 64 channels).
 #include "common.h"
+#include "imgstore.h"
 
 namespace ptx {
-
-__device__ __forceinline__ float ps_load(const void *base, size_t off, int dt)
-{
-    if (dt == 0) return static_cast<const float *>(base)[off];
-    const unsigned short u = static_cast<const unsigned short *>(base)[off];
-    if (dt == 1) return __uint_as_float((unsigned int)u << 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &u, 2);
-    return (float)h;
-}
 
 // (V, C, HW) -> (V, HW, C), 32 x 32 tiles through LDS
 __global__ __launch_bounds__(256) void k_feat_transpose(const void *__restrict__ in, int dt, int C, int HW, float *__restrict__ out)
@@ -32,7 +23,7 @@ __global__ __launch_bounds__(256) void k_feat_transpose(const void *__restrict__
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int c = c0 + ty + 8 * r, p = p0 + tx;
-        tile[ty + 8 * r][tx] = (c < C && p < HW) ? ps_load(in, ((size_t)v * C + c) * HW + p, dt) : 0.0f;
+        tile[ty + 8 * r][tx] = (c < C && p < HW) ? img_load(in, ((size_t)v * C + c) * HW + p, dt) : 0.0f;
     }
     __syncthreads();
 #pragma unroll

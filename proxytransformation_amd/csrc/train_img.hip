@@ -22,19 +22,10 @@
 #include <cstring>
 
 #include "common.h"
+#include "imgstore.h"
 
 namespace ptx {
 
-template <int DT>
-__device__ __forceinline__ float ti_load(const void *base, size_t off)
-{
-    if (DT == 0) return static_cast<const float *>(base)[off];
-    const unsigned short u = static_cast<const unsigned short *>(base)[off];
-    if (DT == 1) return __uint_as_float((unsigned int)u << 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &u, 2);
-    return (float)h;
-}
 template <int DT>
 __device__ __forceinline__ void ti_store(void *base, size_t off, float v)
 {
@@ -62,7 +53,7 @@ __global__ __launch_bounds__(256) void k_ti_mean(const void *__restrict__ x, lon
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     float s = 0.0f;
-    for (int p = lane; p < hw; p += 64) s += ti_load<DT>(x, (size_t)row * hw + p);
+    for (int p = lane; p < hw; p += 64) s += img_load<DT>(x, (size_t)row * hw + p);
     s = wave_sum(s);
     if (lane == 0) out[row] = s / (float)hw;
 }
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(512) void k_ti_pool(TiPool a)
             for (int c = c0; c < c1; c += 16) {
                 float xv[16];
 #pragma unroll
-                for (int u = 0; u < 16; ++u) xv[u] = ti_load<DT>(a.x, xbase + (size_t)min(c + u, c1 - 1) * hw + p);
+                for (int u = 0; u < 16; ++u) xv[u] = img_load<DT>(a.x, xbase + (size_t)min(c + u, c1 - 1) * hw + p);
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
                     if (c + u < c1) {
@@ -192,7 +183,7 @@ __global__ __launch_bounds__(512) void k_ti_pool(TiPool a)
 #pragma unroll
                 for (int s = 0; s < kTiSlots; ++s) {
                     const int p = lane + 64 * s;
-                    xv[u][s] = ti_load<DT>(a.x, xbase + (size_t)min(c + u, Cin - 1) * hw + min(p, hw - 1));
+                    xv[u][s] = img_load<DT>(a.x, xbase + (size_t)min(c + u, Cin - 1) * hw + min(p, hw - 1));
                 }
             float v[UN * 8];
 #pragma unroll

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "imgstore.h"
 
 namespace ptx {
 
@@ -31,26 +32,6 @@ struct BGemmArgs {
     int ksplit; long c_sk;  // K cut into ksplit slices, slice s writes its partial product at C + s * c_sk (the caller
                             // sums the slices with ptx_op_colsum: fixed order, and the chip is busy when M x N is small)
 };
-
-template <int DT>
-__device__ __forceinline__ float load_t(const void *base, long off)
-{
-    if (DT == 0) return static_cast<const float *>(base)[off];
-    const unsigned short u = static_cast<const unsigned short *>(base)[off];
-    if (DT == 1) return __uint_as_float((unsigned int)u << 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &u, 2);
-    return (float)h;
-}
-__device__ __forceinline__ float load_a(const void *base, long off, int dt)
-{
-    if (dt == 0) return static_cast<const float *>(base)[off];
-    const unsigned short u = static_cast<const unsigned short *>(base)[off];
-    if (dt == 1) return __uint_as_float((unsigned int)u << 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &u, 2);
-    return (float)h;
-}
 
 constexpr int TBK = 32;
 // ADT / BDT: storage types of the operands, compile-time: a run-time type test inside the fetch makes every load its own
@@ -102,7 +83,7 @@ __global__ __launch_bounds__(256) void k_bgemm(BGemmArgs g)
             const long bi = bcol[e] + (long)min(k0 + bk[e], kend - 1) * g.b_rs;
             // raw values only: the out-of-range elements are zeroed when the tile is stashed, two steps later -- a select
             // right here would make the wave wait for each load as it is issued
-            ra[e] = load_t<ADT>(g.A, ai); rb[e] = load_t<BDT>(g.B, bi);
+            ra[e] = img_load<ADT>(g.A, ai); rb[e] = img_load<BDT>(g.B, bi);
         }
     };
     auto step = [&](int k0, float (&ra)[E], float (&rb)[E]) {

@@ -13,7 +13,7 @@ def build(name, files):
         if not f.endswith(".hip"): continue
         if f in files:
             src = open(os.path.join(C, f)).read()
-            if f == "imgproxy16.hip":       # only the mean pass
+            if f == "imgproxy.hip":       # only the mean pass
                 a = src.index("void k_img_mean16("); b = src.index("\n}\n", a)
                 src = src[:a] + plain(src[a:b]) + src[b:]
             else:
@@ -28,4 +28,4 @@ def build(name, files):
             objs.append(os.path.join(C, f[:-4] + ".o"))
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(out, "lib_%s.so" % name)] + objs)
     print("built", name)
-build("poolld", {"imgpool.hip"}); build("meanld", {"imgproxy16.hip"}); build("bothld", {"imgpool.hip", "imgproxy16.hip"})
+build("poolld", {"imgpool.hip"}); build("meanld", {"imgproxy.hip"}); build("bothld", {"imgpool.hip", "imgproxy.hip"})

@@ -440,6 +440,21 @@ PTX_API int ptx_point_sample(const float *points, int N, const void *feats, int 
                      const float *proj, const float *pre, float scale_w, float scale_h, float crop_w, float crop_h, int flip,
                      float ori_w, float pad_h, float pad_w, int bilinear, float *out, int32_t *valid_num, void *workspace,
                      size_t ws_bytes, void *stream);
+/* The backward of ptx_point_sample with respect to the feature maps (ABI 13, by addition).  The forward is linear in them, so
+ *   dfeats[v, c, y, x] = sum over the (point n, view v) pairs whose sample touches that pixel of  w * (dout[n, c] / valid_num[n]),
+ * w = 1 (nearest) or the neighbour's bilinear weight as the forward forms it; only points with valid_num[n] > 0 contribute, through
+ * every view whose sample is inside the map (valid or not, like the forward).  dout (N,C) fp32; valid_num (N): what the forward
+ * wrote; dfeats (V,C,H,W) in storage type feat_dtype: EVERY element is written exactly once (zeros where nothing lands; no
+ * memset by the caller), the sum is kept in fp32 in ascending point order and rounded once on the store -- no float atomics,
+ * bitwise reproducible.  The index is rebuilt from points / proj / pre / the image transform (the arguments of the forward);
+ * nothing of the forward needs saving but valid_num.  The points get no gradient.  workspace: ptx_point_sample_bwd_workspace_bytes()
+ * bytes, sized for the worst case N * V (* 4 neighbours) list entries; 0 when a size is outside the supported range.  All checks
+ * are on the host, before anything is enqueued: PTX_EINVAL / PTX_ENOSPACE with a message. */
+PTX_API size_t ptx_point_sample_bwd_workspace_bytes(int N, int V, int H, int W, int bilinear);
+PTX_API int ptx_point_sample_bwd(const float *points, int N, const float *dout, const int32_t *valid_num, int V, int C, int H, int W,
+                         const float *proj, const float *pre, float scale_w, float scale_h, float crop_w, float crop_h, int flip,
+                         float ori_w, float pad_h, float pad_w, int bilinear, void *dfeats, int feat_dtype, void *workspace,
+                         size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------ train-mode operators
  * The differentiable half of the path in train mode -- batch-statistics BatchNorm2d / BatchNorm1d (PRE:74, 114,

@@ -2,6 +2,7 @@
 // Every kernel that reads img_feat widens to fp32 on load and does all arithmetic in fp32, so the storage type is
 // one load and one conversion per kernel: this header owns both, in the three forms the kernels use --
 //   img_load            one element as float (storage type as a template argument, or as a run-time value)
+//   img_store           one float rounded to the storage type (the gradients of the features)
 //   ImgStore<DT>::px4   4 consecutive pixels of a row, one streaming load at ELEMENT alignment, widened to float[4]
 //   ImgStore<DT>::px8   8 consecutive pixels of a row, default cache policy, widened to float[8]
 // A row (one channel of one image) is hw elements long and hw may be odd (15 x 15 = 225), so a row starts at element
@@ -29,6 +30,20 @@ __device__ __forceinline__ float img_load(const void *base, size_t off, int dt)
 }
 template <int DT>
 __device__ __forceinline__ float img_load(const void *base, size_t off) { return img_load(base, off, DT); }
+
+// one element stored in storage type DT, rounded once from fp32 (bf16: to nearest even, like tensor.to(torch.bfloat16))
+template <int DT>
+__device__ __forceinline__ void img_store(void *base, size_t off, float v)
+{
+    if (DT == 0) { static_cast<float *>(base)[off] = v; return; }
+    if (DT == 1) {
+        unsigned int u = __float_as_uint(v);
+        if ((u & 0x7f800000u) != 0x7f800000u) u += 0x7fffu + ((u >> 16) & 1u);
+        static_cast<unsigned short *>(base)[off] = (unsigned short)(u >> 16);
+        return;
+    }
+    static_cast<unsigned short *>(base)[off] = __builtin_bit_cast(unsigned short, (_Float16)v);
+}
 
 template <int DT>   // 1 = bf16, 2 = fp16; fp32 below
 struct ImgStore {

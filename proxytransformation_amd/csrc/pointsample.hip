@@ -44,19 +44,60 @@ struct PsArgs {
 
 constexpr int kPsMaxQ = 8;      // C <= 512
 
+// the reverse 3D augmentation, composed by the host into one affine (pre == NULL: none)
+__device__ __forceinline__ void ps_pre(const float *A, float &x, float &y, float &z)
+{
+    if (!A) return;
+    const float nx = fmaf(A[2], z, fmaf(A[1], y, A[0] * x)) + A[3];
+    const float ny = fmaf(A[6], z, fmaf(A[5], y, A[4] * x)) + A[7];
+    const float nz = fmaf(A[10], z, fmaf(A[9], y, A[8] * x)) + A[11];
+    x = nx; y = ny; z = nz;
+}
+
+// Where point (x, y, z) lands in view v.  nearest: pix = y * W + x of the sampled pixel; bilinear: (x0, y0) = the north-west
+// neighbour (possibly outside the map) and the weights of the +1 neighbours.  inb: the view contributes a sample; valid: it counts
+// in the divisor.  The forward and the backward's index (k_psb_index) both call this: one statement of the rounded steps.
+struct PsHit { bool inb, valid; int pix, x0, y0; float wx1, wy1; };
+__device__ __forceinline__ PsHit ps_project(const PsArgs &a, float x, float y, float z, int v)
+{
+    PsHit h{false, false, 0, 0, 0, 0.0f, 0.0f};
+    const float *P = a.proj + (size_t)v * 16;
+    // q = [x y z 1] P^T (structures/bbox_3d/utils.py:322-327), one rounding per step, in this order
+    float q[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        q[r] = __fadd_rn(fmaf(z, P[4 * r + 2], fmaf(y, P[4 * r + 1], __fmul_rn(x, P[4 * r]))), P[4 * r + 3]);
+    const float zc = fmaxf(q[2], 1e-3f);
+    float cx = __fsub_rn(__fmul_rn(__fdiv_rn(q[0], zc), a.sx), a.cx);        // scale -> crop (point_fusion.py:266-267)
+    const float cy = __fsub_rn(__fmul_rn(__fdiv_rn(q[1], zc), a.sy), a.cy);
+    if (a.flip) cx = __fsub_rn(a.ori_w, cx);                                  // horizontal flip (:276)
+    const float nx = __fsub_rn(__fmul_rn(__fdiv_rn(cx, a.pad_w), 2.0f), 1.0f);
+    const float ny = __fsub_rn(__fmul_rn(__fdiv_rn(cy, a.pad_h), 2.0f), 1.0f);
+    // grid_sample, align_corners=True (unnormalise: ((g + 1) / 2) * (size - 1)), zeros padding
+    const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(nx, 1.0f), 2.0f), (float)(a.W - 1));
+    const float iy = __fmul_rn(__fdiv_rn(__fadd_rn(ny, 1.0f), 2.0f), (float)(a.H - 1));
+    if (!a.bilinear) {                                  // nearest: round half to even
+        const float fx = rintf(ix), fy = rintf(iy);
+        h.inb = fx >= 0.0f && fx <= (float)(a.W - 1) && fy >= 0.0f && fy <= (float)(a.H - 1);
+        if (h.inb) h.pix = (int)fy * a.W + (int)fx;
+    } else {                                            // the four neighbours, those outside the map count as 0
+        const float x0 = floorf(ix), y0 = floorf(iy);
+        h.wx1 = __fsub_rn(ix, x0); h.wy1 = __fsub_rn(iy, y0);
+        // a point whose four neighbours are all outside contributes nothing (also covers inf / nan coordinates)
+        h.inb = x0 >= -1.0f && x0 <= (float)(a.W - 1) && y0 >= -1.0f && y0 <= (float)(a.H - 1);
+        if (h.inb) { h.x0 = (int)x0; h.y0 = (int)y0; }
+    }
+    h.valid = cx < a.pad_w && cx > 0.0f && cy < a.pad_h && cy > 0.0f && q[2] > 0.0f;     // :300-301
+    return h;
+}
+
 __global__ __launch_bounds__(256) void k_point_sample(PsArgs a)
 {
     const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (n >= a.N) return;
     const int lane = lane_id();
     float x = a.points[(size_t)n * 3], y = a.points[(size_t)n * 3 + 1], z = a.points[(size_t)n * 3 + 2];
-    if (a.pre) {        // reverse 3D augmentation, composed by the host into one affine
-        const float *A = a.pre;
-        const float nx = fmaf(A[2], z, fmaf(A[1], y, A[0] * x)) + A[3];
-        const float ny = fmaf(A[6], z, fmaf(A[5], y, A[4] * x)) + A[7];
-        const float nz = fmaf(A[10], z, fmaf(A[9], y, A[8] * x)) + A[11];
-        x = nx; y = ny; z = nz;
-    }
+    ps_pre(a.pre, x, y, z);
     float acc[kPsMaxQ];
 #pragma unroll
     for (int q = 0; q < kPsMaxQ; ++q) acc[q] = 0.0f;
@@ -64,39 +105,11 @@ __global__ __launch_bounds__(256) void k_point_sample(PsArgs a)
     const int HW = a.H * a.W;
     for (int v0 = 0; v0 < a.V; v0 += 64) {
         const int v = v0 + lane;
-        bool inb = false, valid = false;
-        int pix = 0;
-        float wx1 = 0.0f, wy1 = 0.0f;          // bilinear: weights of the +1 neighbours; pix = (y0 * W + x0), possibly outside
-        int cx0 = 0, cy0 = 0;
-        if (v < a.V) {
-            const float *P = a.proj + (size_t)v * 16;
-            // q = [x y z 1] P^T (structures/bbox_3d/utils.py:322-327), one rounding per step, in this order
-            float q[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-                q[r] = __fadd_rn(fmaf(z, P[4 * r + 2], fmaf(y, P[4 * r + 1], __fmul_rn(x, P[4 * r]))), P[4 * r + 3]);
-            const float zc = fmaxf(q[2], 1e-3f);
-            float cx = __fsub_rn(__fmul_rn(__fdiv_rn(q[0], zc), a.sx), a.cx);        // scale -> crop (point_fusion.py:266-267)
-            const float cy = __fsub_rn(__fmul_rn(__fdiv_rn(q[1], zc), a.sy), a.cy);
-            if (a.flip) cx = __fsub_rn(a.ori_w, cx);                                  // horizontal flip (:276)
-            const float nx = __fsub_rn(__fmul_rn(__fdiv_rn(cx, a.pad_w), 2.0f), 1.0f);
-            const float ny = __fsub_rn(__fmul_rn(__fdiv_rn(cy, a.pad_h), 2.0f), 1.0f);
-            // grid_sample, align_corners=True (unnormalise: ((g + 1) / 2) * (size - 1)), zeros padding
-            const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(nx, 1.0f), 2.0f), (float)(a.W - 1));
-            const float iy = __fmul_rn(__fdiv_rn(__fadd_rn(ny, 1.0f), 2.0f), (float)(a.H - 1));
-            if (!a.bilinear) {                                  // nearest: round half to even
-                const float fx = rintf(ix), fy = rintf(iy);
-                inb = fx >= 0.0f && fx <= (float)(a.W - 1) && fy >= 0.0f && fy <= (float)(a.H - 1);
-                if (inb) pix = (int)fy * a.W + (int)fx;
-            } else {                                            // the four neighbours, those outside the map count as 0
-                const float x0 = floorf(ix), y0 = floorf(iy);
-                wx1 = __fsub_rn(ix, x0); wy1 = __fsub_rn(iy, y0);
-                // a point whose four neighbours are all outside contributes nothing (also covers inf / nan coordinates)
-                inb = x0 >= -1.0f && x0 <= (float)(a.W - 1) && y0 >= -1.0f && y0 <= (float)(a.H - 1);
-                if (inb) { cx0 = (int)x0; cy0 = (int)y0; }
-            }
-            valid = cx < a.pad_w && cx > 0.0f && cy < a.pad_h && cy > 0.0f && q[2] > 0.0f;     // :300-301
-        }
+        PsHit h{};
+        if (v < a.V) h = ps_project(a, x, y, z, v);
+        const bool inb = h.inb, valid = h.valid;
+        const int pix = h.pix, cx0 = h.x0, cy0 = h.y0;
+        const float wx1 = h.wx1, wy1 = h.wy1;
         nvalid += __popcll(__ballot(valid));
         unsigned long long hit = __ballot(inb);
         while (hit) {                                           // views in ascending order (the reference sums dim 0)
@@ -143,6 +156,202 @@ __global__ __launch_bounds__(256) void k_point_sample(PsArgs a)
         if (c < a.C) a.out[(size_t)n * a.C + c] = nvalid > 0 ? __fdiv_rn(acc[q], den) : 0.0f;
     }
     if (a.valid_num && lane == 0) a.valid_num[n] = nvalid;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- backward
+// out = A f is linear in the feature maps, so dfeat = A^T dout:  dfeat[v, c, y, x] = sum over the (point, view) pairs that
+// land on that pixel of  w * (dout[n, c] / valid_num[n])  (the reference's own graph: the division's backward, then
+// grid_sample's).  No float atomics: an inverted index per (view, pixel) is built from the geometry alone -- integer counts
+// (k_psb_index<false>), a scan (k_psb_scan, k_psb_scan_top), a fill (k_psb_index<true>) -- every list is put in ascending point
+// order (k_psb_order; a point reaches a pixel of a view through at most one neighbour), and k_point_sample_grad writes every
+// element of the channels-first gradient exactly once, the sum of its list in that order (zeros where the list is empty).
+constexpr int kPsbScan = 2048;          // elements per work-group of the scan: 256 threads x 8
+
+struct PsbIndex {
+    int32_t *cnt;           // (D + 1) hits per pixel, D = V * H * W: counted, then counted back down to 0 by the fill
+    int32_t *off;           // (D + 1) exclusive scan of cnt inside its chunk of kPsbScan elements
+    int32_t *bsum;          // exclusive scan of the chunk totals: list d starts at off[d] + bsum[d / kPsbScan]
+    int2 *raw, *sorted;     // (n, bits of w) in arrival order / in ascending n
+};
+__device__ __forceinline__ int psb_start(const PsbIndex &ix, int d) { return ix.off[d] + ix.bsum[d / kPsbScan]; }
+
+template <bool FILL>
+__device__ __forceinline__ void psb_emit(const PsbIndex &ix, int d, int n, float w)
+{
+    if (!FILL) { atomicAdd(&ix.cnt[d], 1); return; }
+    const int slot = atomicSub(&ix.cnt[d], 1) - 1;
+    ix.raw[psb_start(ix, d) + slot] = make_int2(n, __float_as_int(w));
+}
+
+// one thread per (point, view); a.valid_num: the forward's divisor (points with none contribute nothing)
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_psb_index(PsArgs a, PsbIndex ix)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int n = (int)(i / a.V), v = (int)(i % a.V);
+    if (n >= a.N || a.valid_num[n] <= 0) return;
+    float x = a.points[(size_t)n * 3], y = a.points[(size_t)n * 3 + 1], z = a.points[(size_t)n * 3 + 2];
+    ps_pre(a.pre, x, y, z);
+    const PsHit h = ps_project(a, x, y, z, v);
+    if (!h.inb) return;
+    const int d0 = v * a.H * a.W;
+    if (!a.bilinear) { psb_emit<FILL>(ix, d0 + h.pix, n, 1.0f); return; }
+    const float gx = __fsub_rn(1.0f, h.wx1), gy = __fsub_rn(1.0f, h.wy1);
+    const float w[4] = {__fmul_rn(gx, gy), __fmul_rn(h.wx1, gy), __fmul_rn(gx, h.wy1), __fmul_rn(h.wx1, h.wy1)};   // as the forward
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                               // nw, ne, sw, se
+        const int xx = h.x0 + (k & 1), yy = h.y0 + (k >> 1);
+        if (xx < 0 || xx >= a.W || yy < 0 || yy >= a.H) continue;
+        psb_emit<FILL>(ix, d0 + yy * a.W + xx, n, w[k]);
+    }
+}
+
+// exclusive scan of the work-group's 256 values; wsum: 4 ints of LDS
+__device__ __forceinline__ int psb_block_scan(int t, int *wsum, int &total)
+{
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    int inc = t;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { if (i < w) before += wsum[i]; total += wsum[i]; }
+    __syncthreads();
+    return before + inc - t;
+}
+
+__global__ __launch_bounds__(256) void k_psb_scan(const int32_t *__restrict__ cnt, int n, int32_t *__restrict__ off, int32_t *__restrict__ bsum)
+{
+    __shared__ int wsum[4];
+    const int base = blockIdx.x * kPsbScan + threadIdx.x * 8;
+    int c[8], t = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { c[j] = base + j < n ? cnt[base + j] : 0; t += c[j]; }
+    int total;
+    int run = psb_block_scan(t, wsum, total);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (base + j < n) off[base + j] = run;
+        run += c[j];
+    }
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// the chunk totals, in place, by one work-group
+__global__ __launch_bounds__(256) void k_psb_scan_top(int32_t *__restrict__ bsum, int nb)
+{
+    __shared__ int wsum[4];
+    int carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += 256) {
+        const int b = b0 + threadIdx.x;
+        const int t = b < nb ? bsum[b] : 0;
+        int total;
+        const int ex = psb_block_scan(t, wsum, total);
+        if (b < nb) bsum[b] = carry + ex;
+        carry += total;
+    }
+}
+
+// raw -> sorted: every list in ascending point order (the keys of a list are distinct), by counting the smaller keys.  One lane
+// per pixel for lists of up to 32 entries (the detector's clouds: at most 7); the wave shares a longer list, lane = entry.
+__global__ __launch_bounds__(256) void k_psb_order(PsbIndex ix, int D)
+{
+    const int d = blockIdx.x * 256 + threadIdx.x, lane = lane_id();
+    int start = 0, len = 0;
+    if (d < D) { start = psb_start(ix, d); len = psb_start(ix, d + 1) - start; }
+    if (len <= 32) {
+        for (int i = 0; i < len; ++i) {
+            const int2 e = ix.raw[start + i];
+            int rank = 0;
+            for (int j = 0; j < len; ++j) rank += ix.raw[start + j].x < e.x;
+            ix.sorted[start + rank] = e;
+        }
+    }
+    unsigned long long big = __ballot(len > 32);
+    while (big) {
+        const int l = __ffsll((long long)big) - 1;
+        big &= big - 1;
+        const int s = __builtin_amdgcn_readlane(start, l), m = __builtin_amdgcn_readlane(len, l);
+        for (int i = lane; i < m; i += 64) {
+            const int2 e = ix.raw[s + i];
+            int rank = 0;
+            for (int j = 0; j < m; ++j) rank += ix.raw[s + j].x < e.x;
+            ix.sorted[s + rank] = e;
+        }
+    }
+}
+
+// dfeat (V, C, H*W) in storage type DT.  A work-group owns 64 pixels x 64 channels of one view.  Summing: a wave takes 16 of the
+// pixels, lanes = channels, so a dout row is read as 256 contiguous bytes; the sums cross over through LDS and are stored with
+// lanes = pixels, 64 consecutive elements of a channel row per store.
+struct PsbGrad {
+    PsbIndex ix; const float *dout; const int32_t *valid_num; void *dfeat;
+    int C, HW, ptiles;      // ptiles = ceil(HW / 64)
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void k_point_sample_grad(PsbGrad g)
+{
+    __shared__ float tile[64][65];
+    const int v = blockIdx.x / g.ptiles, p0 = (blockIdx.x % g.ptiles) * 64, c0 = blockIdx.y * 64;
+    const int lane = lane_id(), w = threadIdx.x >> 6;
+    int start = 0, len = 0;
+    if (p0 + lane < g.HW) {
+        const int d = v * g.HW + p0 + lane;
+        start = psb_start(g.ix, d);
+        len = psb_start(g.ix, d + 1) - start;
+    }
+    const int c = c0 + lane;
+    for (int i = 0; i < 16; ++i) {
+        const int p = w * 16 + i;
+        const int s = __builtin_amdgcn_readlane(start, p), m = __builtin_amdgcn_readlane(len, p);
+        float acc = 0.0f;
+        for (int e0 = 0; e0 < m; e0 += 64) {
+            const int cnt = min(64, m - e0);
+            int en = 0;
+            float ew = 0.0f, ed = 1.0f;
+            if (lane < cnt) {
+                const int2 e = g.ix.sorted[s + e0 + lane];
+                en = e.x; ew = __int_as_float(e.y); ed = (float)g.valid_num[en];
+            }
+            for (int j = 0; j < cnt; ++j) {
+                const int n = __builtin_amdgcn_readlane(en, j);
+                const float wj = PTX_LANE_F(ew, j), dj = PTX_LANE_F(ed, j);
+                if (c < g.C) acc = __fadd_rn(acc, __fmul_rn(wj, __fdiv_rn(g.dout[(size_t)n * g.C + c], dj)));
+            }
+        }
+        tile[lane][p] = acc;
+    }
+    __syncthreads();
+    const int p = p0 + lane;
+#pragma unroll 4
+    for (int r = 0; r < 16; ++r) {
+        const int cc = w * 16 + r;
+        if (c0 + cc < g.C && p < g.HW) img_store<DT>(g.dfeat, ((size_t)v * g.C + c0 + cc) * g.HW + p, tile[cc][lane]);
+    }
+}
+
+struct PsbLayout { size_t cnt, off, bsum, raw, sorted, total; int D, nb; long long E; };
+// false: a size outside the 32-bit index range of the kernels
+static bool psb_layout(int N, int V, int H, int W, int bilinear, PsbLayout &L)
+{
+    const long long D = (long long)V * H * W, E = (long long)N * V * (bilinear ? 4 : 1);
+    if (D + 1 > INT32_MAX - kPsbScan || E > INT32_MAX - 256) return false;
+    L.D = (int)D; L.E = E; L.nb = cdiv(L.D + 1, kPsbScan);
+    size_t o = 0;
+    L.cnt = o;    o += align_up((size_t)(D + 1) * 4, 256);
+    L.off = o;    o += align_up((size_t)(D + 1) * 4, 256);
+    L.bsum = o;   o += align_up((size_t)L.nb * 4, 256);
+    L.raw = o;    o += align_up((size_t)E * 8, 256);
+    L.sorted = o; o += align_up((size_t)E * 8, 256);
+    L.total = o;
+    return true;
 }
 
 }  // namespace ptx
@@ -201,6 +410,55 @@ int ptx_point_sample(const float *points, int N, const void *feats, int feat_dty
     PsArgs a{points, N, featT, V, C, H, W, proj, pre, scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w, out, valid_num, bilinear ? 1 : 0};
     hipLaunchKernelGGL(k_point_sample, dim3(cdiv(N, 4)), dim3(256), 0, st, a);
     PTX_LAUNCHED("k_point_sample");
+    return PTX_OK;
+}
+
+/* Bytes of ptx_point_sample_bwd's workspace: the (view, pixel) lists sized for every (point, view[, neighbour]) pair. */
+size_t ptx_point_sample_bwd_workspace_bytes(int N, int V, int H, int W, int bilinear)
+{
+    PsbLayout L;
+    if (N < 1 || V < 1 || H < 1 || W < 1 || !psb_layout(N, V, H, W, bilinear, L)) return 0;
+    return L.total;
+}
+
+int ptx_point_sample_bwd(const float *points, int N, const float *dout, const int32_t *valid_num, int V, int C, int H, int W,
+                         const float *proj, const float *pre, float scale_w, float scale_h, float crop_w, float crop_h, int flip,
+                         float ori_w, float pad_h, float pad_w, int bilinear, void *dfeats, int feat_dtype, void *workspace,
+                         size_t ws_bytes, void *stream)
+{
+    PTX_REQUIRE(points && dout && valid_num && proj && dfeats && workspace, "ptx_point_sample_bwd: null argument");
+    PTX_REQUIRE(N >= 1 && V >= 1 && C >= 1 && C <= 64 * kPsMaxQ && H >= 1 && W >= 1 && feat_dtype >= 0 && feat_dtype <= 2 &&
+                pad_h > 0.0f && pad_w > 0.0f, "ptx_point_sample_bwd: N=%d V=%d C=%d (<= %d) H=%d W=%d dtype=%d pad=(%g, %g)", N, V, C,
+                64 * kPsMaxQ, H, W, feat_dtype, (double)pad_h, (double)pad_w);
+    PsbLayout L;
+    const int ptiles = cdiv(H * W, 64);
+    PTX_REQUIRE(psb_layout(N, V, H, W, bilinear, L) && (long long)V * ptiles <= INT32_MAX,
+                "ptx_point_sample_bwd: N=%d V=%d H=%d W=%d: more (point, view) pairs or pixels than 32-bit indices hold", N, V, H, W);
+    if (ws_bytes < L.total) { set_error("ptx_point_sample_bwd: workspace too small: %zu < %zu bytes", ws_bytes, L.total); return PTX_ENOSPACE; }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    PsbIndex ix{reinterpret_cast<int32_t *>(ws + L.cnt), reinterpret_cast<int32_t *>(ws + L.off), reinterpret_cast<int32_t *>(ws + L.bsum),
+                reinterpret_cast<int2 *>(ws + L.raw), reinterpret_cast<int2 *>(ws + L.sorted)};
+    PsArgs a{points, N, nullptr, V, C, H, W, proj, pre, scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w, nullptr,
+             const_cast<int32_t *>(valid_num), bilinear ? 1 : 0};
+    const int pair_blocks = (int)(((long long)N * V + 255) / 256);
+    PTX_HIP(hipMemsetAsync(ix.cnt, 0, (size_t)(L.D + 1) * 4, st));
+    hipLaunchKernelGGL(k_psb_index<false>, dim3(pair_blocks), dim3(256), 0, st, a, ix);
+    PTX_LAUNCHED("k_psb_index<count>");
+    hipLaunchKernelGGL(k_psb_scan, dim3(L.nb), dim3(256), 0, st, ix.cnt, L.D + 1, ix.off, ix.bsum);
+    PTX_LAUNCHED("k_psb_scan");
+    hipLaunchKernelGGL(k_psb_scan_top, dim3(1), dim3(256), 0, st, ix.bsum, L.nb);
+    PTX_LAUNCHED("k_psb_scan_top");
+    hipLaunchKernelGGL(k_psb_index<true>, dim3(pair_blocks), dim3(256), 0, st, a, ix);
+    PTX_LAUNCHED("k_psb_index<fill>");
+    hipLaunchKernelGGL(k_psb_order, dim3(cdiv(L.D, 256)), dim3(256), 0, st, ix, L.D);
+    PTX_LAUNCHED("k_psb_order");
+    PsbGrad g{ix, dout, valid_num, dfeats, C, H * W, ptiles};
+    const dim3 grid(V * ptiles, cdiv(C, 64));
+    if (feat_dtype == 0) hipLaunchKernelGGL(k_point_sample_grad<0>, grid, dim3(256), 0, st, g);
+    else if (feat_dtype == 1) hipLaunchKernelGGL(k_point_sample_grad<1>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(k_point_sample_grad<2>, grid, dim3(256), 0, st, g);
+    PTX_LAUNCHED("k_point_sample_grad");
     return PTX_OK;
 }
 

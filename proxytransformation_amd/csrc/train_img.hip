@@ -27,20 +27,7 @@
 namespace ptx {
 
 template <int DT>
-__device__ __forceinline__ void ti_store(void *base, size_t off, float v)
-{
-    if (DT == 0) { static_cast<float *>(base)[off] = v; return; }
-    if (DT == 1) {                                           // round to nearest even, like tensor.to(torch.bfloat16)
-        unsigned int u = __float_as_uint(v);
-        if ((u & 0x7f800000u) != 0x7f800000u) u += 0x7fffu + ((u >> 16) & 1u);
-        static_cast<unsigned short *>(base)[off] = (unsigned short)(u >> 16);
-        return;
-    }
-    const _Float16 h = (_Float16)v;
-    unsigned short u;
-    __builtin_memcpy(&u, &h, 2);
-    static_cast<unsigned short *>(base)[off] = u;
-}
+__device__ __forceinline__ void ti_store(void *base, size_t off, float v) { img_store<DT>(base, off, v); }
 
 constexpr int kTiHeads = 8;          // heads per image (PRE:305: num_heads = 8); the kernels below are written for exactly 8
 constexpr int kTiSlots = 4;          // pixels per lane in the pooling passes: hw <= 256

@@ -77,7 +77,13 @@ def batch_point_sample(img_meta: Optional[dict], img_features: torch.Tensor, poi
     ``apply_3d_transformation`` (point_fusion.py:20-107) is composed from ``img_meta['transformation_3d_flow']``
     (``reverse_3d_flow``; the training pipeline's GlobalRotScaleTrans records 'R', 'S', 'T') unless an explicit
     ``pre_transform`` (3,4) is given.  ``prepared``: the workspace ``prepare_features(img_features)`` returned (the channels-last copy
-    made earlier, e.g. on another stream): the call then only samples."""
+    made earlier, e.g. on another stream): the call then only samples.
+
+    Training: with grad mode on and ``img_features.requires_grad`` the result carries a ``grad_fn`` whose backward is HIP as well
+    (``ptx_point_sample_bwd``: no float atomics, bitwise reproducible) and returns the gradient in the shape and dtype of
+    ``img_features`` (with ``prepared=`` too: the gradient goes to the ``img_features`` argument).  Otherwise the call is the plain
+    forward and the result has no ``grad_fn``.  The points stay detached: in the detector they are integer voxel coordinates times
+    the voxel size, and a bilinear gradient with respect to them is out of scope."""
     if padding_mode != "zeros" or not align_corners or not valid_flag:
         raise NotImplementedError("HIP path: padding_mode='zeros', align_corners=True, valid_flag=True "
                                   "(the call at sparse_featfusion_grounder_preshape.py:428-444)")
@@ -93,6 +99,21 @@ def batch_point_sample(img_meta: Optional[dict], img_features: torch.Tensor, poi
     proj = proj_mat.detach().to(torch.float32).contiguous()
     if proj.shape != (V, 4, 4) or pts.dim() != 2 or pts.shape[1] != 3:
         raise RuntimeError(f"expected points (N,3) and proj_mat ({V},4,4), got {tuple(pts.shape)}, {tuple(proj.shape)}")
+    dev = pts.device
+    sw, sh = _pair(img_scale_factor, dev)
+    cw, ch = _pair(img_crop_offset, dev)
+    pre = None if pre_transform is None else pre_transform.detach().to(device=dev, dtype=torch.float32).contiguous()
+    scal = (sw, sh, cw, ch, 1 if img_flip else 0, float(img_shape[1]), float(img_pad_shape[0]), float(img_pad_shape[1]),
+            1 if aligned else 0)
+    if torch.is_grad_enabled() and feats.requires_grad:
+        return _PointSampleFn.apply(feats, prepared, pts, proj, pre, scal)
+    return _sample(feats, prepared, pts, proj, pre, scal, None)
+
+
+def _sample(feats, prepared, pts, proj, pre, scal, valid_num):
+    """The ``ptx_point_sample`` call of ``batch_point_sample``: arguments already checked and converted; ``scal`` = the image-transform
+    scalars and the bilinear flag in the order of the C signature; valid_num (N) int32 or None."""
+    V, C, H, W = feats.shape
     N = pts.shape[0]
     dev = pts.device
     out = torch.empty((N, C), dtype=torch.float32, device=dev)
@@ -101,23 +122,55 @@ def batch_point_sample(img_meta: Optional[dict], img_features: torch.Tensor, poi
     lib = _abi.lib()
     nbytes = lib.ptx_point_sample_workspace_bytes(V, C, H, W)
     if nbytes == 0:
-        raise RuntimeError(f"unsupported feature shape {tuple(img_features.shape)} (C <= 512)")
+        raise RuntimeError(f"unsupported feature shape {tuple(feats.shape)} (C <= 512)")
     if prepared is not None:
         if prepared.numel() < nbytes or prepared.device != dev:
             raise RuntimeError("prepared: not the workspace of prepare_features() for these feature maps")
         ws, feats_ptr = prepared, None
     else:
         ws, feats_ptr = torch.empty((nbytes,), dtype=torch.uint8, device=dev), feats.data_ptr()
-    sw, sh = _pair(img_scale_factor, dev)
-    cw, ch = _pair(img_crop_offset, dev)
-    pre = None if pre_transform is None else pre_transform.detach().to(device=dev, dtype=torch.float32).contiguous()
     _abi.check(lib.ptx_point_sample(pts.data_ptr(), N, feats_ptr, _DT[feats.dtype], V, C, H, W, proj.data_ptr(),
-                                    None if pre is None else pre.data_ptr(), sw, sh, cw, ch, 1 if img_flip else 0,
-                                    float(img_shape[1]), float(img_pad_shape[0]), float(img_pad_shape[1]), 1 if aligned else 0,
-                                    out.data_ptr(),
-                                    None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                                    None if pre is None else pre.data_ptr(), *scal, out.data_ptr(),
+                                    None if valid_num is None else valid_num.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    torch.cuda.current_stream(dev).cuda_stream),
                "ptx_point_sample")
     return out
+
+
+class _PointSampleFn(torch.autograd.Function):
+    """``batch_point_sample`` as an autograd node: the gradient reaches the feature maps (``ptx_point_sample_bwd``), nothing else.
+    The sampling is linear in the features, so the backward needs the geometry only: the points, the matrices, the pre-transform,
+    the scalars and the forward's ``valid_num`` are saved -- not the feature maps."""
+
+    @staticmethod
+    def forward(ctx, feats, prepared, pts, proj, pre, scal):
+        valid_num = torch.empty((pts.shape[0],), dtype=torch.int32, device=pts.device)
+        out = _sample(feats, prepared, pts, proj, pre, scal, valid_num)
+        ctx.save_for_backward(pts, proj, pre, valid_num)
+        ctx.scal, ctx.feat_shape, ctx.feat_dtype = scal, tuple(feats.shape), feats.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        pts, proj, pre, valid_num = ctx.saved_tensors
+        V, C, H, W = ctx.feat_shape
+        N, dev = pts.shape[0], pts.device
+        if N == 0:
+            return torch.zeros(ctx.feat_shape, dtype=ctx.feat_dtype, device=dev), None, None, None, None, None
+        dfeats = torch.empty(ctx.feat_shape, dtype=ctx.feat_dtype, device=dev)     # every element is written by the kernel
+        dout = dout.to(torch.float32).contiguous()
+        lib = _abi.lib()
+        bilinear = ctx.scal[-1]
+        nbytes = lib.ptx_point_sample_bwd_workspace_bytes(N, V, H, W, bilinear)
+        if nbytes == 0:
+            raise RuntimeError(f"point-sample backward: N={N} V={V} H={H} W={W} is outside the 32-bit index range")
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _abi.check(lib.ptx_point_sample_bwd(pts.data_ptr(), N, dout.data_ptr(), valid_num.data_ptr(), V, C, H, W, proj.data_ptr(),
+                                            None if pre is None else pre.data_ptr(), *ctx.scal, dfeats.data_ptr(),
+                                            _DT[ctx.feat_dtype], ws.data_ptr(), ws.numel(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "ptx_point_sample_bwd")
+        return dfeats, None, None, None, None, None
 
 
 def prepare_features(img_features: torch.Tensor) -> torch.Tensor:

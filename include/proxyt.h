@@ -410,6 +410,21 @@ PTX_API int ptx_voxelize(const float *points, const int32_t *counts, int B, int 
 PTX_API int ptx_voxelize_ex(const float *points, const int32_t *counts, int B, int Ncap, float voxel_size, int32_t *coords,
                     float *feats, int32_t *inverse, int32_t *nvox_overflow, int32_t *scene_end, void *workspace, size_t ws_bytes,
                     void *stream);
+/* ABI 13, by addition.  ptx_voxelize_ex + `rep` (B*Ncap int32 capacity; NULL = ptx_voxelize_ex): rep[r] = the flat padded index
+ * b * Ncap + i of the point whose coordinates are feats[r] -- `features = p[unique_index]` of the quantisation (DET:388-397 with
+ * use_xyz_feat, CFG:43), i.e. the index autograd hands row r's gradient back to.  One more store per row in the emit pass; coords,
+ * feats, inverse, scene_end and the published counts are bit-identical to ptx_voxelize_ex on the same input. */
+PTX_API int ptx_voxelize_rep(const float *points, const int32_t *counts, int B, int Ncap, float voxel_size, int32_t *coords,
+                     float *feats, int32_t *inverse, int32_t *rep, int32_t *nvox_overflow, int32_t *scene_end, void *workspace,
+                     size_t ws_bytes, void *stream);
+/* ABI 13, by addition.  The backward of the features of DET:388-397 (`features = p[unique_index]`, a gather of whole rows) with
+ * respect to the points: dfeats (nvox,3) fp32; inverse (B,Ncap), rep and counts (B, device) as ptx_voxelize_rep wrote / read them;
+ * dpoints (B,Ncap,3) fp32.  Point (b,i), i < counts[b], receives dfeats[inverse[b,i]] if rep[inverse[b,i]] == b * Ncap + i and exact
+ * zeros otherwise (the other points of a voxel).  One per-point pass on `stream`: every element of dpoints below the counts is
+ * written exactly once, zeros included (rows past the counts are unspecified) -- no memset, no float atomics, no workspace, no host
+ * wait, bitwise reproducible.  The coordinates (floor) get no gradient.  dfeats may be NULL when nvox == 0. */
+PTX_API int ptx_voxel_features_bwd(const float *dfeats, int nvox, const int32_t *inverse, const int32_t *rep, const int32_t *counts,
+                           int B, int Ncap, float *dpoints, void *stream);
 /* ABI 12.  The coordinates of a COARSER MinkowskiEngine level over voxel rows the calls above produced -- what a strided layer of the
  * detector's sparse backbone does to its coordinate map (backbones/mink_resnet.py:57-78: tensor strides 8 / 16 / 32 / 64), which is all
  * the image-feature sampling behind it needs of that backbone (DET:429-430 `x[level].decomposed_coordinates[idx] * voxel_size`):

@@ -174,6 +174,8 @@ SIGNATURES.update({
     "ptx_voxel_workspace_bytes": (_Z, [_I, _I]),
     "ptx_voxelize": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _Z, _P]),
     "ptx_voxelize_ex": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_voxelize_rep": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_voxel_features_bwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "ptx_voxel_coarsen": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _Z, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),

@@ -33,6 +33,7 @@ struct VoxArgs {
     // (scene, x, y, z), scene b's rows [in_end[b-1], in_end[b]) -- and the voxel of a row is its coordinate >> shift (floor division
     // by the power-of-two stride); the emitted row carries floor(c / s) * s and the "feature" that coordinate times voxel_size
     const int32_t *coords_in; int shift; int32_t in_end[64];
+    int32_t *rep_out;                      // optional (ptx_voxelize_rep): flat padded index b * Ncap + i of the point each row keeps
 };
 
 __device__ __forceinline__ int vox_count(const VoxArgs &a, int b)
@@ -187,6 +188,7 @@ __global__ __launch_bounds__(256) void k_vox_emit(VoxArgs a)
                 f[0] = p[0]; f[1] = p[1]; f[2] = p[2];
             }
             a.row_of_slot[slot[r]] = row;
+            if (a.rep_out != nullptr) a.rep_out[row] = gi;  // the point this row's features are: min(first, ~owner), known above
         }
         run += s_cnt[r][0] + s_cnt[r][1] + s_cnt[r][2] + s_cnt[r][3];
     }
@@ -209,6 +211,51 @@ __global__ __launch_bounds__(256) void k_vox_inverse(VoxArgs a)
     if (i >= a.Ncap) return;
     const int gi = b * a.Ncap + i;
     a.inverse[gi] = i < vox_count(a, b) ? a.row_of_slot[a.slot_of[gi]] : -1;
+}
+
+// backward of the features (ptx_voxel_features_bwd): features = points[rep] is a gather of whole rows, so its transpose hands
+// dfeats[r] to point rep[r] and exact zeros to every other point of the voxel.  One per-point pass: P consecutive points of one
+// scene per thread, every live element of dpoints written exactly once (zeros included) -- no memset, no atomics, no workspace.
+// P = 4 (Ncap a multiple of 4, 16-byte aligned inverse / dpoints): the four rows of `inverse` come with one 16-byte load and the
+// 12 floats leave as three 16-byte stores; P = 1: any capacity / alignment.  dfeats rows are 12 bytes apart: dword loads, in
+// ascending row order along the lanes (rows are emitted in (scene, point) order).
+template <int P>
+__global__ __launch_bounds__(256) void k_vox_feat_bwd(const float *__restrict__ dfeats, int nvox, const int32_t *__restrict__ inverse,
+                                                      const int32_t *__restrict__ rep, const int32_t *__restrict__ counts, int Ncap,
+                                                      float *__restrict__ dpoints)
+{
+    const int b = blockIdx.y, i0 = (blockIdx.x * 256 + threadIdx.x) * P;
+    const int nb = min(counts[b], Ncap);
+    if (i0 >= nb) return;                                   // (P = 4: Ncap % 4 == 0, so i0 + 3 < Ncap)
+    const int g0 = b * Ncap + i0;
+    int row[P];
+    if constexpr (P == 4) {
+        const int4 r4 = *reinterpret_cast<const int4 *>(inverse + g0);
+        row[0] = r4.x; row[1] = r4.y; row[2] = r4.z; row[3] = r4.w;
+    } else {
+        row[0] = inverse[g0];
+    }
+    float g[3 * P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int r = row[j];
+        // a point past its scene's count, a row outside the table (never from ptx_voxelize_rep) and a duplicate all get zeros
+        const bool mine = i0 + j < nb && r >= 0 && r < nvox && rep[r] == g0 + j;
+        g[3 * j + 0] = g[3 * j + 1] = g[3 * j + 2] = 0.0f;
+        if (mine) {
+            const float *d = dfeats + (size_t)r * 3;
+            g[3 * j + 0] = d[0]; g[3 * j + 1] = d[1]; g[3 * j + 2] = d[2];
+        }
+    }
+    float *o = dpoints + (size_t)g0 * 3;
+    if constexpr (P == 4) {
+        float4 *o4 = reinterpret_cast<float4 *>(o);
+        o4[0] = make_float4(g[0], g[1], g[2], g[3]);
+        o4[1] = make_float4(g[4], g[5], g[6], g[7]);
+        o4[2] = make_float4(g[8], g[9], g[10], g[11]);
+    } else {
+        o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
+    }
 }
 
 struct VoxLayout { size_t zero_begin, keys, owner, tile_word, overflow, zero_bytes, first, slot_of, row_of_slot, total; unsigned int slots; };
@@ -242,6 +289,37 @@ size_t ptx_voxel_workspace_bytes(int B, int Ncap)
     return vox_layout(B, Ncap).total;
 }
 
+// the body of ptx_voxelize / _ex / _rep (rep: optional); ``who`` names the entry in the error text
+static int vox_run(const char *who, const float *points, const int32_t *counts, int B, int Ncap, float voxel_size, int32_t *coords,
+                   float *feats, int32_t *inverse, int32_t *rep, int32_t *nvox_overflow, int32_t *scene_end, void *workspace,
+                   size_t ws_bytes, void *stream)
+{
+    PTX_REQUIRE(points && counts && coords && feats && nvox_overflow && workspace, "%s: null argument", who);
+    PTX_REQUIRE(B >= 1 && B <= 64 && Ncap >= 1 && (long)B * Ncap <= (1l << 30) && voxel_size > 0.0f,
+                "%s: B=%d Ncap=%d voxel_size=%g", who, B, Ncap, voxel_size);
+    const VoxLayout L = vox_layout(B, Ncap);
+    if (ws_bytes < L.total) { set_error("%s: workspace too small: %zu < %zu bytes", who, ws_bytes, L.total); return PTX_ENOSPACE; }
+    PTX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    VoxArgs a{points, counts, B, Ncap, voxel_size,
+              reinterpret_cast<unsigned long long *>(ws + L.keys), reinterpret_cast<uint32_t *>(ws + L.owner),
+              reinterpret_cast<int32_t *>(ws + L.first), reinterpret_cast<int32_t *>(ws + L.slot_of), reinterpret_cast<int32_t *>(ws + L.row_of_slot),
+              reinterpret_cast<unsigned long long *>(ws + L.tile_word), L.slots - 1, coords, feats, inverse,
+              reinterpret_cast<int32_t *>(ws + L.overflow), nvox_overflow, scene_end, nullptr, 0, {}, rep};
+    PTX_HIP(hipMemsetAsync(ws + L.zero_begin, 0, L.zero_bytes, st));
+    const dim3 per_point(cdiv(Ncap, 256), B), per_tile(cdiv(Ncap, kTilePts), B);
+    hipLaunchKernelGGL(k_vox_insert, per_point, dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_vox_insert");
+    hipLaunchKernelGGL(k_vox_emit, per_tile, dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_vox_emit");
+    if (inverse) {
+        hipLaunchKernelGGL(k_vox_inverse, per_point, dim3(256), 0, st, a);
+        PTX_LAUNCHED("k_vox_inverse");
+    }
+    return PTX_OK;
+}
+
 int ptx_voxelize(const float *points, const int32_t *counts, int B, int Ncap, float voxel_size, int32_t *coords,
                  float *feats, int32_t *inverse, int32_t *nvox_overflow, void *workspace, size_t ws_bytes, void *stream)
 {
@@ -253,29 +331,34 @@ int ptx_voxelize_ex(const float *points, const int32_t *counts, int B, int Ncap,
                     float *feats, int32_t *inverse, int32_t *nvox_overflow, int32_t *scene_end, void *workspace, size_t ws_bytes,
                     void *stream)
 {
-    PTX_REQUIRE(points && counts && coords && feats && nvox_overflow && workspace, "ptx_voxelize: null argument");
-    PTX_REQUIRE(B >= 1 && B <= 64 && Ncap >= 1 && (long)B * Ncap <= (1l << 30) && voxel_size > 0.0f,
-                "ptx_voxelize: B=%d Ncap=%d voxel_size=%g", B, Ncap, voxel_size);
-    const VoxLayout L = vox_layout(B, Ncap);
-    if (ws_bytes < L.total) { set_error("ptx_voxelize: workspace too small: %zu < %zu bytes", ws_bytes, L.total); return PTX_ENOSPACE; }
-    PTX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "ptx_voxelize: workspace must be 256-byte aligned");
+    return vox_run("ptx_voxelize", points, counts, B, Ncap, voxel_size, coords, feats, inverse, nullptr, nvox_overflow, scene_end,
+                   workspace, ws_bytes, stream);
+}
+
+int ptx_voxelize_rep(const float *points, const int32_t *counts, int B, int Ncap, float voxel_size, int32_t *coords,
+                     float *feats, int32_t *inverse, int32_t *rep, int32_t *nvox_overflow, int32_t *scene_end, void *workspace,
+                     size_t ws_bytes, void *stream)
+{
+    return vox_run("ptx_voxelize_rep", points, counts, B, Ncap, voxel_size, coords, feats, inverse, rep, nvox_overflow, scene_end,
+                   workspace, ws_bytes, stream);
+}
+
+int ptx_voxel_features_bwd(const float *dfeats, int nvox, const int32_t *inverse, const int32_t *rep, const int32_t *counts, int B,
+                           int Ncap, float *dpoints, void *stream)
+{
+    PTX_REQUIRE(inverse && rep && counts && dpoints && (dfeats || nvox == 0), "ptx_voxel_features_bwd: null argument");
+    PTX_REQUIRE(B >= 1 && B <= 64 && Ncap >= 1 && (long)B * Ncap <= (1l << 30) && nvox >= 0 && (long)nvox <= (long)B * Ncap,
+                "ptx_voxel_features_bwd: B=%d Ncap=%d nvox=%d", B, Ncap, nvox);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
-    VoxArgs a{points, counts, B, Ncap, voxel_size,
-              reinterpret_cast<unsigned long long *>(ws + L.keys), reinterpret_cast<uint32_t *>(ws + L.owner),
-              reinterpret_cast<int32_t *>(ws + L.first), reinterpret_cast<int32_t *>(ws + L.slot_of), reinterpret_cast<int32_t *>(ws + L.row_of_slot),
-              reinterpret_cast<unsigned long long *>(ws + L.tile_word), L.slots - 1, coords, feats, inverse,
-              reinterpret_cast<int32_t *>(ws + L.overflow), nvox_overflow, scene_end, nullptr, 0, {}};
-    PTX_HIP(hipMemsetAsync(ws + L.zero_begin, 0, L.zero_bytes, st));
-    const dim3 per_point(cdiv(Ncap, 256), B), per_tile(cdiv(Ncap, kTilePts), B);
-    hipLaunchKernelGGL(k_vox_insert, per_point, dim3(256), 0, st, a);
-    PTX_LAUNCHED("k_vox_insert");
-    hipLaunchKernelGGL(k_vox_emit, per_tile, dim3(256), 0, st, a);
-    PTX_LAUNCHED("k_vox_emit");
-    if (inverse) {
-        hipLaunchKernelGGL(k_vox_inverse, per_point, dim3(256), 0, st, a);
-        PTX_LAUNCHED("k_vox_inverse");
+    const bool wide = Ncap % 4 == 0 && ((reinterpret_cast<uintptr_t>(inverse) | reinterpret_cast<uintptr_t>(dpoints)) & 15) == 0;
+    if (wide) {
+        hipLaunchKernelGGL(k_vox_feat_bwd<4>, dim3(cdiv(Ncap / 4, 256), B), dim3(256), 0, st, dfeats, nvox, inverse, rep, counts, Ncap,
+                           dpoints);
+    } else {
+        hipLaunchKernelGGL(k_vox_feat_bwd<1>, dim3(cdiv(Ncap, 256), B), dim3(256), 0, st, dfeats, nvox, inverse, rep, counts, Ncap,
+                           dpoints);
     }
+    PTX_LAUNCHED("k_vox_feat_bwd");
     return PTX_OK;
 }
 
@@ -301,7 +384,7 @@ int ptx_voxel_coarsen(const int32_t *coords_in, const int32_t *in_scene_end, int
               reinterpret_cast<unsigned long long *>(ws + L.keys), reinterpret_cast<uint32_t *>(ws + L.owner),
               reinterpret_cast<int32_t *>(ws + L.first), reinterpret_cast<int32_t *>(ws + L.slot_of), reinterpret_cast<int32_t *>(ws + L.row_of_slot),
               reinterpret_cast<unsigned long long *>(ws + L.tile_word), L.slots - 1, coords, points, nullptr,
-              reinterpret_cast<int32_t *>(ws + L.overflow), nvox_overflow, scene_end, coords_in, 0, {}};
+              reinterpret_cast<int32_t *>(ws + L.overflow), nvox_overflow, scene_end, coords_in, 0, {}, nullptr};
     while ((1 << a.shift) < stride) ++a.shift;
     for (int b = 0; b < B; ++b) a.in_end[b] = in_scene_end[b];
     PTX_HIP(hipMemsetAsync(ws + L.zero_begin, 0, L.zero_bytes, st));

@@ -857,7 +857,6 @@ class ProxyTransformationNormReverse(nn.Module):
                 ("simple_encoder.mlp.1", self.simple_encoder.mlp[1]),
                 ("text_trans_norm", self.text_trans_norm), ("img_trans_norm", self.img_trans_norm))
 
-    @torch.no_grad()
     def quantize(self, outs: List[torch.Tensor], voxel_size: float = 0.01, return_inverse: bool = False,
                  return_scene_rows: bool = False):
         """What the reference's detector does with this module's output next (detectors/
@@ -869,7 +868,29 @@ class ProxyTransformationNormReverse(nn.Module):
         publishes through pinned memory (the tensors' contents are stream-ordered like any torch result).
 
         ``return_scene_rows=True`` appends ``ends`` (list of B ints): the rows of scene b are ``[ends[b-1], ends[b])`` -- what
-        ``x.decomposed_coordinates`` (DET:391-392, 429-430) splits by; published through the same pinned words as the count."""
+        ``x.decomposed_coordinates`` (DET:391-392, 429-430) splits by; published through the same pinned words as the count.
+
+        With grad mode on and a tensor of ``outs`` requiring grad (the train-mode outputs), ``features`` carries a ``grad_fn``:
+        ``features = p[unique_index]`` (DET:388-397) hands each row's gradient back to the point the row kept and zeros to the other
+        points of its voxel (``ptx_voxel_features_bwd``), one ``(n_b,3)`` gradient per scene.  The coordinates (``floor``) get none.
+        The values are bit-identical to the plain call's and the host waits for the same one word."""
+        if torch.is_grad_enabled() and any(o.requires_grad for o in outs):
+            state = {}
+            feats = _VoxelFeatures.apply(self, state, float(voxel_size), *outs)
+            coords, inverse, n, ends = state["res"]
+        else:
+            with torch.no_grad():
+                coords, feats, inverse, n, ends = self._quantize(outs, voxel_size, return_inverse)[:5]
+        res = (coords, feats)
+        if return_inverse:
+            res += ([inverse[b, : n[b]] for b in range(len(outs))],)
+        if return_scene_rows:
+            res += (ends,)
+        return res
+
+    def _quantize(self, outs, voxel_size, want_inverse, want_rep=False):
+        """The quantisation kernels behind ``quantize`` (no autograd here): ``(coords, feats, inverse (B,Ncap) | None, n, ends, rep,
+        counts)`` -- ``rep`` / ``counts`` (what the backward of the features reads) only with ``want_rep``."""
         lib = _abi.lib()
         B = len(outs)
         dev = outs[0].device
@@ -903,11 +924,18 @@ class ProxyTransformationNormReverse(nn.Module):
         counts.copy_(q["counts_h"][:B], non_blocking=True)       # the staging buffer is free again once `info` is published
         coords = torch.empty((B * Ncap, 4), dtype=torch.int32, device=dev)
         feats = torch.empty((B * Ncap, 3), dtype=torch.float32, device=dev)
-        inverse = torch.empty((B, Ncap), dtype=torch.int32, device=dev) if return_inverse else None
+        inverse = torch.empty((B, Ncap), dtype=torch.int32, device=dev) if want_inverse else None
+        rep = torch.empty((B * Ncap,), dtype=torch.int32, device=dev) if want_rep else None
         q["info_np"][:] = -1
-        _abi.check(lib.ptx_voxelize_ex(buf.data_ptr(), counts.data_ptr(), B, Ncap, float(voxel_size), coords.data_ptr(),
-                                       feats.data_ptr(), _ptr(inverse), q["info"].data_ptr(), q["info"].data_ptr() + 8,
-                                       q["ws"].data_ptr(), q["ws"].numel(), tstream.cuda_stream), "ptx_voxelize")
+        if want_rep:
+            _abi.check(lib.ptx_voxelize_rep(buf.data_ptr(), counts.data_ptr(), B, Ncap, float(voxel_size), coords.data_ptr(),
+                                            feats.data_ptr(), _ptr(inverse), rep.data_ptr(), q["info"].data_ptr(),
+                                            q["info"].data_ptr() + 8, q["ws"].data_ptr(), q["ws"].numel(), tstream.cuda_stream),
+                       "ptx_voxelize_rep")
+        else:
+            _abi.check(lib.ptx_voxelize_ex(buf.data_ptr(), counts.data_ptr(), B, Ncap, float(voxel_size), coords.data_ptr(),
+                                           feats.data_ptr(), _ptr(inverse), q["info"].data_ptr(), q["info"].data_ptr() + 8,
+                                           q["ws"].data_ptr(), q["ws"].numel(), tstream.cuda_stream), "ptx_voxelize")
         if lib.ptx_wait_counts(q["info"].data_ptr(), 2 + B, _COUNTS_TIMEOUT_US) != 0:
             tstream.synchronize()
         nvox, overflow = (int(x) for x in q["info_np"][:2])
@@ -921,12 +949,7 @@ class ProxyTransformationNormReverse(nn.Module):
         #  here: a consumer on another stream has to wait for this stream, as for any torch tensor)
         if overflow:
             raise RuntimeError(f"quantize: {overflow} points fall outside +-2^18 voxels of size {voxel_size}")
-        res = (coords[:nvox], feats[:nvox])
-        if return_inverse:
-            res += ([inverse[b, : n[b]] for b in range(B)],)
-        if return_scene_rows:
-            res += (ends,)
-        return res
+        return coords[:nvox], feats[:nvox], inverse, n, ends, rep, counts
 
     @torch.no_grad()
     def forward_debug(self, points, text_dict, img_feat, bbox=None):
@@ -934,3 +957,31 @@ class ProxyTransformationNormReverse(nn.Module):
         outs, dbg = self._run(points, text_dict, img_feat, debug=True, bbox=bbox)
         dbg["outputs"] = outs
         return dbg
+
+
+class _VoxelFeatures(torch.autograd.Function):
+    """``features`` of ``quantize`` as a function of ``*outs`` (DET:388-397: ``features = p[unique_index]``).  The node owns what its
+    backward reads -- ``inverse``, ``rep`` and the device counts are allocated per call, none is a view of the lane's scratch -- so
+    later ``quantize`` calls or training steps do not disturb it.  ``coords`` / ``inverse`` / ``ends`` leave through ``state``."""
+
+    @staticmethod
+    def forward(ctx, mod, state, voxel_size, *outs):
+        coords, feats, inverse, n, ends, rep, counts = mod._quantize(outs, voxel_size, True, want_rep=True)
+        state["res"] = (coords, inverse, n, ends)
+        ctx.save_for_backward(inverse, rep, counts)
+        ctx.n = n
+        return feats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dfeats):
+        inverse, rep, counts = ctx.saved_tensors
+        B, Ncap = inverse.shape
+        dfeats = dfeats.to(torch.float32).contiguous()
+        dpoints = torch.empty((B, Ncap, 3), dtype=torch.float32, device=inverse.device)
+        stream = torch.cuda.current_stream(inverse.device).cuda_stream
+        _abi.check(_abi.lib().ptx_voxel_features_bwd(_ptr(dfeats) if dfeats.numel() else None, dfeats.shape[0], inverse.data_ptr(),
+                                                     rep.data_ptr(), counts.data_ptr(), B, Ncap, dpoints.data_ptr(), stream),
+                   "ptx_voxel_features_bwd")
+        grads = [dpoints[b, : ctx.n[b]] if need else None for b, need in enumerate(ctx.needs_input_grad[3:])]
+        return (None, None, None, *grads)

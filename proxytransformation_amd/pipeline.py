@@ -127,12 +127,19 @@ class GroundingFeaturePrefix:
     ``img_crop_offset``, ``img_shape``, the 3D flow record) for the sampling.  ``img_features``: the 2D backbone's levels, each
     (B,V,C_l,H_l,W_l); the LAST one feeds the neck (DET:385).  ``sampler``: where the ingest's two ``PointSample`` draws are made
     (``MultiViewIngest``): "host" (np.random, the reference's stream; the host waits for each scene's per-view counts) or "device"
-    (ptx_ingest_draw; ``seed=`` / ``rng`` / a scene's ``draw_seed`` give the keys, no host wait in the ingest)."""
+    (ptx_ingest_draw; ``seed=`` / ``rng`` / a scene's ``draw_seed`` give the keys, no host wait in the ingest).
+
+    ``differentiable=True`` (training the detector through the prefix; the module must be in ``.train()``): the neck, ``quantize`` and
+    the sampling run in the caller's grad mode, so ``PrefixOutput.points`` / ``.features`` / ``.points_imgfeats`` carry ``grad_fn``s that
+    reach the neck's parameters, the text features and every level of ``img_features`` (the last level receives the sum of the
+    neck's gradient and its own sampling's).  The ingest and the level coordinates (integers, inputs) stay under ``no_grad``.
+    Default ``False``: the whole call runs under ``no_grad`` as before."""
 
     def __init__(self, preshape, n_points: int = 100000, voxel_size: float = 0.01,
                  level_strides: Sequence[int] = MINK_RESNET_STRIDES, coord_type: str = "DEPTH", overlap_feature_layout: bool = True,
-                 sampler: str = "host"):
+                 sampler: str = "host", differentiable: bool = False):
         self.preshape = preshape
+        self.differentiable = bool(differentiable)
         self.ingest = MultiViewIngest(n_points, sampler=sampler)
         self.voxel_size = float(voxel_size)
         self.level_strides = tuple(int(s) for s in level_strides)
@@ -145,9 +152,11 @@ class GroundingFeaturePrefix:
         self.overlap_feature_layout = overlap_feature_layout
         self._side = None
 
-    def _upload_matrices(self, scenes, dev, st):
+    def _upload_matrices(self, scenes, dev, st, own=False):
         """Projection matrices (V,4,4) and the reverse 3D augmentation flow (3,4) of every scene through ONE pinned staging buffer and
-        ONE asynchronous copy: a ``.to(device)`` from pageable memory would block the host behind everything queued on the stream."""
+        ONE asynchronous copy: a ``.to(device)`` from pageable memory would block the host behind everything queued on the stream.
+        ``own``: the returned tensors are views of a device buffer of this call's own instead of the per-stream twin, which the next
+        call overwrites -- the sampling's autograd nodes save them until their backward."""
         projs = [projection_matrices(sc["depth2img"]) for sc in scenes]
         flows = [reverse_3d_flow(sc.get("img_meta") or {}, self.coord_type) for sc in scenes]
         n = sum(p.size for p in projs) + 12 * len(scenes)
@@ -158,26 +167,36 @@ class GroundingFeaturePrefix:
             stg["np"] = stg["host"].numpy()
         if stg["done"] is not None and not stg["done"].query():
             stg["done"].synchronize()                  # the previous call's copy out of the staging buffer (long done)
+        dst = torch.empty((n,), dtype=torch.float32, device=dev) if own else stg["dev"]
         o, proj_t, flow_t = 0, [], []
         for p, f in zip(projs, flows):
             stg["np"][o:o + p.size] = p.reshape(-1)
-            proj_t.append(stg["dev"][o:o + p.size].view(p.shape))
+            proj_t.append(dst[o:o + p.size].view(p.shape))
             o += p.size
             if f is not None:
                 stg["np"][o:o + 12] = f.numpy().reshape(-1)
-                flow_t.append(stg["dev"][o:o + 12].view(3, 4))
+                flow_t.append(dst[o:o + 12].view(3, 4))
             else:
                 flow_t.append(None)
             o += 12
-        stg["dev"][:o].copy_(stg["host"][:o], non_blocking=True)
+        dst[:o].copy_(stg["host"][:o], non_blocking=True)
         stg["done"] = torch.cuda.Event()
         stg["done"].record(st)
         return proj_t, flow_t
 
-    @torch.no_grad()
     def __call__(self, scenes: Sequence[dict], text_dict: dict, img_features: Sequence[torch.Tensor],
                  img_pad_shape: Sequence[int] = (480, 480), rng=np.random, time_stages: bool = False,
                  seed: Optional[int] = None) -> PrefixOutput:
+        if self.differentiable and not self.preshape.training:
+            raise RuntimeError("GroundingFeaturePrefix(differentiable=True): the module is in eval mode, whose outputs carry no grad_fn "
+                               "(the eval path is inference-only HIP); call .train() to differentiate")
+        # differentiable: the three stages that gradients pass through run in the caller's grad mode, everything else under no_grad
+        mode = torch.is_grad_enabled()
+        grad = (lambda: torch.set_grad_enabled(mode)) if self.differentiable else torch.no_grad
+        with torch.no_grad():
+            return self._chain(grad, scenes, text_dict, img_features, img_pad_shape, rng, time_stages, seed)
+
+    def _chain(self, grad, scenes, text_dict, img_features, img_pad_shape, rng, time_stages, seed) -> PrefixOutput:
         if len(img_features) != len(self.level_strides):
             raise ValueError(f"{len(self.level_strides)} levels of image features expected, got {len(img_features)}")
         dev = img_features[-1].device
@@ -200,12 +219,16 @@ class GroundingFeaturePrefix:
                 flat = prepare_features_many([img_features[li][b] for b in range(len(scenes)) for li in range(nl)])
             flat[0].record_stream(st)                        # ONE allocation under the side stream, consumed on the caller's
             prepared = [flat[b * nl:(b + 1) * nl] for b in range(len(scenes))]
-        proj_t, flow_t = self._upload_matrices(scenes, dev, st)
+        with grad():
+            saved = torch.is_grad_enabled()                  # the sampling's nodes will save the matrices: give them this call's own
+        proj_t, flow_t = self._upload_matrices(scenes, dev, st, own=saved)
         batch = self.ingest(scenes, rng=rng, seed=seed)                                    # N4
         mark("ingest")
-        outs = self.preshape(batch.points, text_dict, img_features[-1], bbox=batch.bbox)   # the path, DET:385
+        with grad():
+            outs = self.preshape(batch.points, text_dict, img_features[-1], bbox=batch.bbox)   # the path, DET:385
         mark("preshape")
-        coords, feats, ends = self.preshape.quantize(outs, self.voxel_size, return_scene_rows=True)   # N2, DET:388-397
+        with grad():
+            coords, feats, ends = self.preshape.quantize(outs, self.voxel_size, return_scene_rows=True)   # N2, DET:388-397
         mark("quantize")
         res = PrefixOutput(ingested=batch, points=outs, coordinates=coords, features=feats, scene_rows=ends)
         cur_c, cur_e = coords, ends
@@ -224,12 +247,13 @@ class GroundingFeaturePrefix:
             proj = proj_t[b]
             per_level = []
             for li in range(len(self.level_strides)):
-                per_level.append(batch_point_sample(
-                    meta, img_features[li][b], res.level_points[li][b], proj, self.coord_type,
-                    img_scale_factor=meta.get("scale_factor", (1.0, 1.0))[:2] if "scale_factor" in meta else 1.0,
-                    img_crop_offset=meta.get("img_crop_offset", 0.0), img_flip=bool(meta.get("flip", False)),
-                    img_pad_shape=tuple(img_pad_shape), img_shape=tuple(meta.get("img_shape", img_pad_shape))[:2],
-                    aligned=False, pre_transform=flow_t[b], prepared=None if prepared is None else prepared[b][li]))
+                with grad():
+                    per_level.append(batch_point_sample(
+                        meta, img_features[li][b], res.level_points[li][b], proj, self.coord_type,
+                        img_scale_factor=meta.get("scale_factor", (1.0, 1.0))[:2] if "scale_factor" in meta else 1.0,
+                        img_crop_offset=meta.get("img_crop_offset", 0.0), img_flip=bool(meta.get("flip", False)),
+                        img_pad_shape=tuple(img_pad_shape), img_shape=tuple(meta.get("img_shape", img_pad_shape))[:2],
+                        aligned=False, pre_transform=flow_t[b], prepared=None if prepared is None else prepared[b][li]))
             res.points_imgfeats.append(per_level)
         mark("point_sample")
         assert len(res.points_imgfeats) == B

@@ -436,6 +436,46 @@ PTX_API int ptx_voxel_coarsen(const int32_t *coords_in, const int32_t *in_scene_
                       int32_t *coords, float *points, int32_t *nvox_overflow, int32_t *scene_end, void *workspace, size_t ws_bytes,
                       void *stream);
 
+/* ------------------------------------------------------------------ sparse 3D convolution on the voxel rows (ABI 13, by addition)
+ * The primitive of `x = self.backbone_3d(x)` (DET:398; backbones/mink_resnet.py:58-63 conv1 = MinkowskiConvolution(3, 64, kernel_size=3,
+ * stride=2), mink_resnet.py:67-69 MinkowskiMaxPooling(kernel_size=2, stride=2), mink_resnet.py:103-109 the 1x1 stride-2 downsample,
+ * mink_resnet.py:111-119 the BasicBlocks' 3x3x3 convolutions): kernel maps over the rows the calls above produce, and a fused gather-GEMM convolution and max-pool that consume
+ * them.  Inference only.  Assembling the backbone, MinkowskiInstanceNorm (mink_resnet.py:64), the backward pass and neck_3d are not here.
+ *
+ * Kernel map.  coords_in (n_in,4) int32 rows (scene, x, y, z) of a level of tensor stride `tensor_stride` (a power of two; every
+ * coordinate a multiple of it), scene b's rows [in_scene_end[b-1], in_scene_end[b]) with in_scene_end a [host] array of B ints (read
+ * during the call).  Output rows: stride 1 -- the input rows (coords_out is not written and may be NULL); stride 2 -- the distinct
+ * floor(c / (2 tensor_stride)) * (2 tensor_stride) per scene in first-occurrence order, written to coords_out (n_in rows capacity) by
+ * ptx_voxel_coarsen itself (same rows, same order).  Offsets: odd kernel_size {-(k/2) .. k/2} * tensor_stride per axis around the output
+ * coordinate, even kernel_size {0 .. k-1} * tensor_stride; never across scenes; offset index j = (dz * k + dy) * k + dx counted from the
+ * lowest offset, x fastest (MinkowskiEngine's region iterator as we read it: parity unpinned against ME itself).  nbr (n_in * k^3 int32
+ * capacity): nbr[o * k^3 + j] = the input row at (output row o's coordinate + offset j), or -1.
+ * count_words: 2 int32 = {output rows, rows whose coordinate >> log2(stride of the table) left +-2^18}; out_scene_end: B int32 ends of
+ * the output rows per scene; both device memory or device-mapped pinned host memory preset to -1, published with system scope (poll
+ * with ptx_wait_counts; no device synchronise); rows == PTX_VOX_BROKEN as for ptx_voxelize.  The rows and nbr are ordered on `stream`.
+ * workspace: ptx_sparse_kernel_map_workspace_bytes(B, ncap >= the largest scene's rows) bytes, 256-byte aligned (two hash tables of
+ * ptx_voxel_workspace_bytes each: the coarsening's and the index of the input rows, whose value is the row).  B <= 64.  Host checks
+ * (PTX_EINVAL / PTX_ENOSPACE with a message) come before anything is enqueued. */
+PTX_API size_t ptx_sparse_kernel_map_workspace_bytes(int B, int ncap);
+PTX_API int ptx_sparse_kernel_map(const int32_t *coords_in, const int32_t *in_scene_end, int B, int tensor_stride, int kernel_size, int stride,
+                          int32_t *coords_out, int32_t *out_scene_end, int32_t *nbr, int32_t *count_words, void *workspace,
+                          size_t ws_bytes, void *stream);
+/* out (n_out,Cout) fp32:  out[o] = sum_j feats[nbr[o * kvol + j]] @ weight[j]  over the neighbours that are present (a row without any
+ * is zero), then, each part optional (NULL / 0):  + bias[c];  * scale[c] + shift[c] (an eval MinkowskiBatchNorm folded by the caller,
+ * mink_resnet.py:109);  + residual[o,c];  ReLU.  feats (n_in,Cin) fp32, weight (kvol,Cin,Cout) fp32 -- the layout of
+ * ME.MinkowskiConvolution's `kernel` parameter --, bias / scale / shift (Cout), residual (n_out,Cout); kvol 1, 8 or 27.  One launch of
+ * 64-row x 64-channel tiles on the exact-fp32 matrix instruction; blocked summation (per offset and 64 input channels, then over those
+ * blocks) in a fixed order, no float atomics: bitwise reproducible.
+ * Cout: a multiple of 64 up to 512; Cin: a multiple of 16 up to 512, or 3 with kvol 27 (the stem, mink_resnet.py:58-63: one K = 81
+ * panel).  Anything else is PTX_EINVAL with the numbers in the message, before anything is enqueued.  `out` must not alias feats. */
+PTX_API int ptx_sparse_conv3d(const float *feats, int n_in, const int32_t *nbr, int n_out, int kvol, const float *weight, int Cin, int Cout,
+                      const float *bias, const float *scale, const float *shift, const float *residual, int relu, float *out,
+                      void *stream);
+/* out (n_out,C) fp32 = max over the present neighbours of feats[nbr[o * kvol + j]] (MinkowskiMaxPooling, mink_resnet.py:67-69; with
+ * kernel_size 2, stride 2 every output row has one; a row without any is -inf).  C: a multiple of 4.  nbr must come from
+ * ptx_sparse_kernel_map over feats' rows (indices are not range-checked). */
+PTX_API int ptx_sparse_max_pool3d(const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, void *stream);
+
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/
  * sparse_featfusion_grounder_preshape.py:428-444 (nearest, zeros padding, align_corners=True, valid_flag=True; bilinear != 0:

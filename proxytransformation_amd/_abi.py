@@ -177,6 +177,10 @@ SIGNATURES.update({
     "ptx_voxelize_rep": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "ptx_voxel_features_bwd": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P]),
     "ptx_voxel_coarsen": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_sparse_kernel_map_workspace_bytes": (_Z, [_I, _I]),
+    "ptx_sparse_kernel_map": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_sparse_conv3d": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "ptx_sparse_max_pool3d": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),

@@ -12,10 +12,11 @@
 
 #include "common.h"
 #include "split3.h"
+#include "mfma64.h"
 
 namespace ptx {
 
-constexpr int BK = 32, LDT = BK + 4;   // 144-B LDS rows: 16-B aligned, b128 fragment reads conflict-free
+// BK = 32, LDT = BK + 4 (144-B LDS rows: 16-B aligned, b128 fragment reads conflict-free) and the fragment step: mfma64.h
 
 // ---- three-way bf16 operand split (the "x3" kernels): split3.h
 // the value is "re-defined" here: arithmetic on a prefetched register cannot be hoisted above this point (hipcc moves
@@ -104,18 +105,6 @@ __device__ __forceinline__ void ln_tile_partials(const GemmProb &pr, const float
         *reinterpret_cast<float4 *>(&Ws[buf_][sr][kq]) = w##S##0;                          \
         *reinterpret_cast<float4 *>(&Ws[buf_][sr + 32][kq]) = w##S##1;                     \
     } while (0)
-#define PTX_G64_COMPUTE(buf_)                                                              \
-    do {                                                                                   \
-        _Pragma("unroll") for (int kk = 0; kk < BK / 8; ++kk) {                            \
-            const float4 a4 = *reinterpret_cast<const float4 *>(&As[buf_][wr * 32 + li][kk * 8 + hh * 4]); \
-            const float4 b4 = *reinterpret_cast<const float4 *>(&Ws[buf_][wc * 32 + li][kk * 8 + hh * 4]); \
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);          \
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);          \
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);          \
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);          \
-        }                                                                                  \
-    } while (0)
-
 template <bool LN>      // LN: some group of the launch is a LayerNorm consumer (its A rows are centred in the stash)
 __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
 {
@@ -197,7 +186,6 @@ __global__ __launch_bounds__(256) void k_gemm64(GemmBatch gb)
 }
 #undef PTX_G64_FETCH
 #undef PTX_G64_STASH
-#undef PTX_G64_COMPUTE
 
 // (Measured on the way, r02: 2048x1024x1024 takes 49.4 us with the fp32 instruction -- 55 % of the matrix pipe, and neither
 // four register stages, nor removing the stash or the barrier moves it much: the phases of a step do not overlap

@@ -18,57 +18,10 @@
 //                 and only waits for lower-numbered tiles, which were dispatched earlier: no order assumption beyond
 //                 that), rows emitted in order; the last tile publishes the row count / overflow count to the host
 #include "common.h"
+#include "voxel.h"
 
 namespace ptx {
 
-constexpr int kVoxBias = 1 << 18;          // voxel indices in [-2^18, 2^18): +-2.6 km at 1 cm
-
-struct VoxArgs {
-    const float *points; const int32_t *counts; int B, Ncap; float voxel_size;
-    unsigned long long *keys; uint32_t *owner; int32_t *first; int32_t *slot_of; int32_t *row_of_slot; unsigned long long *tile_word;
-    unsigned int mask;
-    int32_t *coords; float *feats; int32_t *inverse; int32_t *overflow; int32_t *nvox_overflow;
-    int32_t *scene_end;                    // optional (ptx_voxelize_ex): rows written up to and including scene b
-    // coarsening mode (ptx_voxel_coarsen): the "points" are the integer voxel rows of a finer level -- coords_in (rows,4) int32
-    // (scene, x, y, z), scene b's rows [in_end[b-1], in_end[b]) -- and the voxel of a row is its coordinate >> shift (floor division
-    // by the power-of-two stride); the emitted row carries floor(c / s) * s and the "feature" that coordinate times voxel_size
-    const int32_t *coords_in; int shift; int32_t in_end[64];
-    int32_t *rep_out;                      // optional (ptx_voxelize_rep): flat padded index b * Ncap + i of the point each row keeps
-};
-
-__device__ __forceinline__ int vox_count(const VoxArgs &a, int b)
-{
-    return a.coords_in == nullptr ? a.counts[b] : a.in_end[b] - (b > 0 ? a.in_end[b - 1] : 0);
-}
-
-__device__ __forceinline__ bool vox_key(const VoxArgs &a, int b, int i, int (&v)[3], unsigned long long &key)
-{
-    bool ok = true;
-    if (a.coords_in != nullptr) {
-        const int32_t *c = a.coords_in + ((size_t)(b > 0 ? a.in_end[b - 1] : 0) + i) * 4;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            v[d] = c[1 + d] >> a.shift;                                   // arithmetic shift = floor division by the stride
-            ok = ok && v[d] >= -kVoxBias && v[d] < kVoxBias;
-        }
-    } else {
-        const float *p = a.points + ((size_t)b * a.Ncap + i) * 3;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            v[d] = (int)floorf(__fdiv_rn(p[d], a.voxel_size));            // torch: floor(p / voxel_size), fp32
-            ok = ok && v[d] >= -kVoxBias && v[d] < kVoxBias;
-        }
-    }
-    key = ((unsigned long long)b << 57) | ((unsigned long long)(v[0] + kVoxBias) << 38) |
-          ((unsigned long long)(v[1] + kVoxBias) << 19) | (unsigned long long)(v[2] + kVoxBias);
-    return ok;
-}
-
-__device__ __forceinline__ unsigned int vox_hash(unsigned long long k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned int)k;
-}
 
 // pass 1: every valid point claims (or finds) the slot of its voxel.  ONE device-scope atomic per point in the common case
 // (r04: CAS + atomicMax per point were 46 us for 399k points -- the table is shared by the whole chip, its atomics execute at
@@ -258,23 +211,22 @@ __global__ __launch_bounds__(256) void k_vox_feat_bwd(const float *__restrict__ 
     }
 }
 
-struct VoxLayout { size_t zero_begin, keys, owner, tile_word, overflow, zero_bytes, first, slot_of, row_of_slot, total; unsigned int slots; };
-static VoxLayout vox_layout(int B, int Ncap)
+
+// index mode (voxel.h): the insert pass alone, on the integer rows of a level at coordinate >> shift.  Rows of a level are distinct, so
+// every row claims a slot and `first` is its index; duplicates, if a caller hands some in, resolve to whichever claimed the slot.
+int vox_index_rows(const int32_t *coords_in, const int32_t *in_scene_end, int B, int ncap, int shift, char *ws, hipStream_t st)
 {
-    VoxLayout L{};
-    const size_t total = (size_t)B * Ncap;
-    unsigned int slots = 1024;
-    while ((size_t)slots < 2 * total) slots <<= 1;
-    L.slots = slots;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes, 256); return r; };
-    L.zero_begin = o;                                       // cleared by ONE memset per call
-    L.keys = take((size_t)slots * 8); L.owner = take((size_t)slots * 4);
-    L.tile_word = take((size_t)B * cdiv(Ncap, kTilePts) * 8); L.overflow = take(8);
-    L.zero_bytes = o - L.zero_begin;
-    L.first = take((size_t)slots * 4); L.slot_of = take(total * 4); L.row_of_slot = take((size_t)slots * 4);
-    L.total = o;
-    return L;
+    const VoxLayout L = vox_layout(B, ncap);
+    VoxArgs a{nullptr, nullptr, B, ncap, 1.0f,
+              reinterpret_cast<unsigned long long *>(ws + L.keys), reinterpret_cast<uint32_t *>(ws + L.owner),
+              reinterpret_cast<int32_t *>(ws + L.first), reinterpret_cast<int32_t *>(ws + L.slot_of), reinterpret_cast<int32_t *>(ws + L.row_of_slot),
+              reinterpret_cast<unsigned long long *>(ws + L.tile_word), L.slots - 1, nullptr, nullptr, nullptr,
+              reinterpret_cast<int32_t *>(ws + L.overflow), nullptr, nullptr, coords_in, shift, {}, nullptr};
+    for (int b = 0; b < B; ++b) a.in_end[b] = in_scene_end[b];
+    PTX_HIP(hipMemsetAsync(ws + L.zero_begin, 0, L.zero_bytes, st));
+    hipLaunchKernelGGL(k_vox_insert, dim3(cdiv(ncap, 256), B), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_vox_insert");
+    return PTX_OK;
 }
 
 }  // namespace ptx

@@ -440,7 +440,7 @@ PTX_API int ptx_voxel_coarsen(const int32_t *coords_in, const int32_t *in_scene_
  * The primitive of `x = self.backbone_3d(x)` (DET:398; backbones/mink_resnet.py:58-63 conv1 = MinkowskiConvolution(3, 64, kernel_size=3,
  * stride=2), mink_resnet.py:67-69 MinkowskiMaxPooling(kernel_size=2, stride=2), mink_resnet.py:103-109 the 1x1 stride-2 downsample,
  * mink_resnet.py:111-119 the BasicBlocks' 3x3x3 convolutions): kernel maps over the rows the calls above produce, and a fused gather-GEMM convolution and max-pool that consume
- * them.  Inference only.  Assembling the backbone, MinkowskiInstanceNorm (mink_resnet.py:64), the backward pass and neck_3d are not here.
+ * them, and their backward passes.  Assembling the backbone, MinkowskiInstanceNorm (mink_resnet.py:64) and neck_3d are not here.
  *
  * Kernel map.  coords_in (n_in,4) int32 rows (scene, x, y, z) of a level of tensor stride `tensor_stride` (a power of two; every
  * coordinate a multiple of it), scene b's rows [in_scene_end[b-1], in_scene_end[b]) with in_scene_end a [host] array of B ints (read
@@ -475,6 +475,36 @@ PTX_API int ptx_sparse_conv3d(const float *feats, int n_in, const int32_t *nbr, 
  * kernel_size 2, stride 2 every output row has one; a row without any is -inf).  C: a multiple of 4.  nbr must come from
  * ptx_sparse_kernel_map over feats' rows (indices are not range-checked). */
 PTX_API int ptx_sparse_max_pool3d(const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, void *stream);
+/* Backward of the two layers (ABI 13, by addition) -- the coordinate manager run backwards.  No float atomics: every output is bitwise
+ * reproducible launch to launch; everything is ordered on `stream`, no host wait; host checks come before anything is enqueued.
+ *
+ * Transposed map: nbr_t (n_in,kvol) int32, nbr_t[i * kvol + j] = the output row o with nbr[o * kvol + j] == i, else -1 (for a fixed (i, j)
+ * at most one exists: its coordinate is coord_i - offset_j).  Entries of nbr < 0 or >= n_in are skipped.  One fill + one launch. */
+PTX_API int ptx_sparse_kernel_map_transpose(const int32_t *nbr, int n_out, int kvol, int n_in, int32_t *nbr_t, void *stream);
+/* Gradients of ptx_sparse_conv3d, given g = d loss / d out (n_out,Cout).  With out the forward's result (read only when relu) and
+ * gz = g * [out > 0] * scale (either factor only when present):
+ *   dresidual (n_out,Cout) = g * [out > 0];   dbias (Cout) = sum_o gz[o] (256-row tiles, then the tiles, both in a fixed blocked order);
+ *   dfeats (n_in,Cin): dfeats[i] = sum_j gz[nbr_t[i * kvol + j]] @ weight[j]^T  (the forward kernel over the transposed map);
+ *   dweight (kvol,Cin,Cout): dweight[j] = sum_o feats[nbr[o * kvol + j]]^T @ gz[o], split over row chunks: 64-pair steps on the exact-fp32
+ *   matrix instruction, each from zero and added to the chunk's running sum, the chunks' partials added in ascending order.
+ * Each of dresidual / dbias / dfeats / dweight is optional (NULL: not computed, and its work is not done).  gz (n_out,Cout) is scratch
+ * the call writes; it is needed when (relu or scale) and (dfeats or dweight).  scale / shift get no gradient (a folded frozen BatchNorm).
+ * Cout: a multiple of 64 up to 512; Cin: a multiple of 64 up to 512, or 3 with kvol 27 (the stem); kvol 1, 8 or 27; anything else is
+ * PTX_EINVAL with the numbers.  workspace: ptx_sparse_conv3d_bwd_workspace_bytes(n_out, kvol, Cin, Cout) bytes (0: unsupported), 16-byte
+ * aligned; needed for dbias and dweight.  All float buffers 16-byte aligned; the outputs must not alias the inputs. */
+PTX_API size_t ptx_sparse_conv3d_bwd_workspace_bytes(int n_out, int kvol, int Cin, int Cout);
+PTX_API int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, int relu, const float *feats, int n_in,
+                          const int32_t *nbr, const int32_t *nbr_t, int n_out, int kvol, const float *weight, int Cin, int Cout,
+                          float *gz, float *dresidual, float *dbias, float *dfeats, float *dweight, void *workspace, size_t ws_bytes,
+                          void *stream);
+/* ptx_sparse_max_pool3d plus arg (n_out,C) uint8: the offset index j that supplied the maximum, 255 for a row without neighbours.  Ties
+ * go to the smallest j.  `out` is bit-identical to ptx_sparse_max_pool3d's. */
+PTX_API int ptx_sparse_max_pool3d_arg(const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, uint8_t *arg,
+                              void *stream);
+/* dfeats (n_in,C): dfeats[i,c] = sum over ascending j of [arg[nbr_t[i * kvol + j], c] == j] * g[nbr_t[i * kvol + j], c]; every element
+ * is written once. */
+PTX_API int ptx_sparse_max_pool3d_bwd(const float *g, const uint8_t *arg, const int32_t *nbr_t, int n_in, int n_out, int kvol, int C,
+                              float *dfeats, void *stream);
 
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/

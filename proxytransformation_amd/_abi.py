@@ -181,6 +181,11 @@ SIGNATURES.update({
     "ptx_sparse_kernel_map": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "ptx_sparse_conv3d": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "ptx_sparse_max_pool3d": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "ptx_sparse_kernel_map_transpose": (_I, [_P, _I, _I, _I, _P, _P]),
+    "ptx_sparse_conv3d_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "ptx_sparse_conv3d_bwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_sparse_max_pool3d_arg": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "ptx_sparse_max_pool3d_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "mfma64.h"
 #include "voxel.h"
+#include "sparse.h"
 
 namespace ptx {
 
@@ -112,8 +113,10 @@ struct SpConvArgs {
 };
 
 // STEM: Cin = 3 (ME.MinkowskiConvolution(3, 64, kernel_size=3, stride=2), mink_resnet.py:57-60): the 27 offsets x 3 channels are one
-// K = 81 panel (weight (27,3,Cout) IS the (81,Cout) matrix), padded with zeros to the two 64-wide steps of the loop below
-template <bool STEM>
+// K = 81 panel (weight (27,3,Cout) IS the (81,Cout) matrix), padded with zeros to the two 64-wide steps of the loop below.
+// WT (the backward's dfeats = sum_j gz[nbr_t[:, j]] @ weight[j]^T, sparse_bwd.hip): the slab is read as (kvol, Cout, Cin) of this launch,
+// i.e. k is contiguous in memory already and goes into LDS as 16-byte pieces like the gathered rows; same arithmetic, same order.
+template <bool STEM, bool WT>
 __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
 {
     __shared__ __attribute__((aligned(16))) float As[2][64][LDT];       // [k / 32][row][k % 32]: a 64-channel piece of 64 gathered rows
@@ -147,6 +150,7 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
     // transposed as four dwords -- the 32 lanes of a write group hold 16 k x 2 n-quads, banks wk + 16 (quad & 1): conflict-free
     const int ar = tid >> 4, kq = (tid & 15) * 4;
     const int wk = lane & 15, wn = (wid * 4 + (lane >> 4)) * 4;
+    static_assert(!(STEM && WT), "the stem's dfeats has a kernel of its own");
     float4 av[4], wv[4];
     float tot[16];                                          // the tile's running sum; a step's product is formed apart and added to it
 #pragma unroll
@@ -181,16 +185,24 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
                 av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (idx >= 0 && c0 + kq < a.Cin) av[i] = *reinterpret_cast<const float4 *>(a.feats + (size_t)idx * a.Cin + c0 + kq);
             }
-            const int k = c0 + wk + 16 * i;                 // row of the (kvol * Cin, Cout) weight matrix, minus j * Cin
-            const bool wok = STEM ? k < 81 : k < a.Cin;
             wv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (wok) wv[i] = *reinterpret_cast<const float4 *>(a.weight + ((size_t)j * a.Cin + k) * a.Cout + col0 + wn);
+            if (WT) {                                       // column col0 + row of the slab, k = c0 + kq .. + 3 contiguous (Cin % 64 == 0)
+                wv[i] = *reinterpret_cast<const float4 *>(a.weight + ((size_t)j * a.Cout + col0 + row) * a.Cin + c0 + kq);
+            } else {
+                const int k = c0 + wk + 16 * i;             // row of the (kvol * Cin, Cout) weight matrix, minus j * Cin
+                const bool wok = STEM ? k < 81 : k < a.Cin;
+                if (wok) wv[i] = *reinterpret_cast<const float4 *>(a.weight + ((size_t)j * a.Cin + k) * a.Cout + col0 + wn);
+            }
         }
     };
     auto stash = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             *reinterpret_cast<float4 *>(&As[kq >> 5][ar + 16 * i][kq & 31]) = av[i];
+            if (WT) {
+                *reinterpret_cast<float4 *>(&Ws[kq >> 5][ar + 16 * i][kq & 31]) = wv[i];
+                continue;
+            }
             const int k = wk + 16 * i;
             Ws[k >> 5][wn + 0][k & 31] = wv[i].x;
             Ws[k >> 5][wn + 1][k & 31] = wv[i].y;
@@ -244,6 +256,17 @@ __global__ __launch_bounds__(256) void k_sparse_max_pool(const float *__restrict
         m.x = fmaxf(m.x, x.x); m.y = fmaxf(m.y, x.y); m.z = fmaxf(m.z, x.z); m.w = fmaxf(m.w, x.w);
     }
     *reinterpret_cast<float4 *>(out + (size_t)o * C + c4 * 4) = m;
+}
+
+// dfeats (n_in, Cin) = sum_j gz[nbr_t[:, j]] @ weight[j]^T: the forward kernel over the transposed map, rows and widths swapped
+int sparse_conv_transposed(const float *gz, int n_out, const int32_t *nbr_t, int n_in, int kvol, const float *weight, int Cin, int Cout,
+                           float *dfeats, hipStream_t st)
+{
+    if (n_in == 0) return PTX_OK;
+    const SpConvArgs a{gz, nbr_t, weight, nullptr, nullptr, nullptr, nullptr, dfeats, n_out, n_in, kvol, Cout, Cin, 0};
+    hipLaunchKernelGGL((k_sparse_conv<false, true>), dim3(cdiv(n_in, 64), Cin / 64), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_sparse_conv (transposed)");
+    return PTX_OK;
 }
 
 }  // namespace ptx
@@ -318,8 +341,8 @@ int ptx_sparse_conv3d(const float *feats, int n_in, const int32_t *nbr, int n_ou
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SpConvArgs a{feats, nbr, weight, bias, scale, shift, residual, out, n_in, n_out, kvol, Cin, Cout, relu};
     const dim3 grid(cdiv(n_out, 64), Cout / 64);
-    if (stem) hipLaunchKernelGGL(k_sparse_conv<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_sparse_conv<false>, grid, dim3(256), 0, st, a);
+    if (stem) hipLaunchKernelGGL((k_sparse_conv<true, false>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_sparse_conv<false, false>), grid, dim3(256), 0, st, a);
     PTX_LAUNCHED("k_sparse_conv");
     return PTX_OK;
 }

@@ -440,7 +440,8 @@ PTX_API int ptx_voxel_coarsen(const int32_t *coords_in, const int32_t *in_scene_
  * The primitive of `x = self.backbone_3d(x)` (DET:398; backbones/mink_resnet.py:58-63 conv1 = MinkowskiConvolution(3, 64, kernel_size=3,
  * stride=2), mink_resnet.py:67-69 MinkowskiMaxPooling(kernel_size=2, stride=2), mink_resnet.py:103-109 the 1x1 stride-2 downsample,
  * mink_resnet.py:111-119 the BasicBlocks' 3x3x3 convolutions): kernel maps over the rows the calls above produce, and a fused gather-GEMM convolution and max-pool that consume
- * them, and their backward passes.  Assembling the backbone, MinkowskiInstanceNorm (mink_resnet.py:64) and neck_3d are not here.
+ * them, and their backward passes.  MinkowskiInstanceNorm (mink_resnet.py:64) and a training MinkowskiBatchNorm: the norm section below; the backbone is
+ * assembled in Python (proxytransformation_amd/backbone.py); neck_3d is not here.
  *
  * Kernel map.  coords_in (n_in,4) int32 rows (scene, x, y, z) of a level of tensor stride `tensor_stride` (a power of two; every
  * coordinate a multiple of it), scene b's rows [in_scene_end[b-1], in_scene_end[b]) with in_scene_end a [host] array of B ints (read
@@ -505,6 +506,35 @@ PTX_API int ptx_sparse_max_pool3d_arg(const float *feats, const int32_t *nbr, in
  * is written once. */
 PTX_API int ptx_sparse_max_pool3d_bwd(const float *g, const uint8_t *arg, const int32_t *nbr_t, int n_in, int n_out, int kvol, int C,
                               float *dfeats, void *stream);
+
+/* ------------------------------------------------------------------ instance norm / training batch norm on the voxel rows (ABI 13, by addition)
+ * MinkowskiInstanceNorm (mink_resnet.py:67: per scene) and a training MinkowskiBatchNorm (one segment over all rows) are the same
+ * kernels: column moments per row segment -> normalise -> affine (+ residual)(+ ReLU), forward and backward.  x (n,C) fp32, C a multiple
+ * of 64 up to 512; seg_end: a [host] array of S ints, 1 <= S <= 64, the ascending ends of the segments' rows with seg_end[S-1] == n
+ * (ptx_sparse_kernel_map's in_scene_end; read during the call; empty segments allowed).  Tiles of 256 rows that never straddle a
+ * segment; per tile (mean, M2 about that mean), merged per segment with Chan's formula in a fixed blocked ascending order -- never
+ * E[x^2] - E[x]^2; no float atomics: two calls on the same inputs give the same bits.  Everything is ordered on `stream`, no host wait;
+ * the checks (PTX_EINVAL / PTX_ENOSPACE with a message) come before anything is enqueued.  All float buffers and the workspace
+ * (ptx_sparse_norm_workspace_bytes(n, S, C) bytes; 0: unsupported size) 16-byte aligned.
+ *
+ * Forward: stats (S,2,C) = per segment and column (mean, rstd = 1 / sqrt(var_biased + eps)), an empty segment (0, 0);
+ * out = relu?(((x - mean) * rstd) * weight + bias (+ residual)), weight / bias (C), residual (n,C), each optional (NULL).  A one-row
+ * segment has variance 0: its output is bias (+ residual).  running_mean / running_var (C), both or neither, only with S == 1 and
+ * n >= 2: updated in place, (1 - momentum) * old + momentum * new with the unbiased variance M2 / (n - 1) (nn.BatchNorm1d's rule). */
+PTX_API size_t ptx_sparse_norm_workspace_bytes(int n, int S, int C);
+PTX_API int ptx_sparse_norm_fwd(const float *x, const int32_t *seg_end, int S, int n, int C, float eps, const float *weight,
+                        const float *bias, const float *residual, int relu, float *running_mean, float *running_var, float momentum,
+                        float *stats, float *out, void *workspace, size_t ws_bytes, void *stream);
+/* The forward's last pass alone, from stats the caller supplies (an eval batch norm: mean = running_mean, rstd from running_var). */
+PTX_API int ptx_sparse_norm_apply(const float *x, const int32_t *seg_end, int S, int n, int C, const float *stats, const float *weight,
+                          const float *bias, const float *residual, int relu, float *out, void *stream);
+/* Backward, given g = d loss / d out (n,C), x and the forward's stats; out: the forward's result when it had a ReLU, else NULL.
+ * gy = g * [out > 0] (g itself without ReLU); xhat = (x - mean) * rstd recomputed;  dresidual (n,C) = gy;  dbias (C) = sum_rows gy;
+ * dweight (C) = sum_rows gy * xhat;  per segment a = mean_s(gy), b = mean_s(gy * xhat);  dx = weight * rstd_s * ((gy - a) - xhat * b).
+ * Every output pointer is optional (NULL: not computed).  The workspace is always needed. */
+PTX_API int ptx_sparse_norm_bwd(const float *g, const float *x, const float *out, const int32_t *seg_end, int S, int n, int C,
+                        const float *stats, const float *weight, float *dx, float *dweight, float *dbias, float *dresidual,
+                        void *workspace, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/

@@ -6,6 +6,7 @@ Only what the path needs lives here:
   surface (embodiedscan/models/necks/preshape_norm_reverse_drop.py:280-469);
 * ``csrc/`` + ``libproxyt_hip.so``           -- hand-written HIP kernels for gfx950 behind
   the C ABI of ``include/proxyt.h`` (bound with ctypes in ``_abi``);
+* ``backbone.MinkResNet``                    -- the sparse 3D backbone (backbones/mink_resnet.py) on the layers of ``sparse``;
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -15,6 +16,7 @@ Importing the package does not need a GPU and does not load the shared library;
 """
 from .registry import MODELS, REGISTRY_BACKEND
 from .module import ProxyTransformationNormReverse
+from .backbone import MinkResNet
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "ProxyTransformationNormReverse"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "MinkResNet", "ProxyTransformationNormReverse"]
 __version__ = "0.1.0"

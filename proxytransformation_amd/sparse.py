@@ -31,9 +31,15 @@ Restated in numpy by ``kernel_map_transpose_host`` / ``sparse_conv3d_bwd_host`` 
 ``differentiable=True`` both layers stay inference-only and say so instead of returning a detached result.  In differentiable mode
 the widths are a MinkResNet's: Cin a multiple of 64 (or the stem's 3), Cout a multiple of 64.
 
-Not here (out of scope): assembling the backbone, ``MinkowskiInstanceNorm`` (a per-scene segment reduction in plain torch), ``neck_3d``,
-double backward, bf16, gradients to ``scale`` / ``shift``.  There is no CPU path for the layers themselves: tensors must be on the GPU
-and the library must be built.
+Norms (``csrc/sparse_norm.hip``): ``sparse_instance_norm`` (``MinkowskiInstanceNorm``: per scene, biased variance, ``INSTANCE_NORM_EPS``
+inside the square root -- OUR READING of ``MinkowskiInstanceNormFunction``, parity unpinned against ME itself) and ``sparse_batch_norm``
+(an ``nn.BatchNorm1d`` on the rows: in training mode one segment over all rows with the running statistics updated by the kernel, in
+eval mode the affine map from the running statistics) are one family of streaming kernels, "column moments per row segment ->
+normalise -> affine (+ residual)(+ ReLU)", forward and backward, restated in numpy by ``sparse_norm_host`` / ``sparse_norm_bwd_host``.
+The same opt-in rule: inference-only unless ``differentiable=True``.  ``backbone.MinkResNet`` assembles all of this.
+
+Not here (out of scope): ``neck_3d``, double backward, bf16, gradients to ``scale`` / ``shift``, SyncBatchNorm across ranks.  There is no
+CPU path for the layers themselves: tensors must be on the GPU and the library must be built.
 """
 from __future__ import annotations
 
@@ -47,8 +53,14 @@ from torch import nn
 
 from . import _abi
 
-__all__ = ["KernelMap", "SparseConv3d", "kernel_map", "kernel_map_host", "kernel_map_transpose_host", "kernel_offsets", "sparse_conv3d",
-           "sparse_conv3d_bwd_host", "sparse_conv3d_host", "sparse_max_pool3d", "sparse_max_pool3d_bwd_host", "sparse_max_pool3d_host"]
+__all__ = ["INSTANCE_NORM_EPS", "KernelMap", "SparseBatchNorm", "SparseConv3d", "SparseInstanceNorm", "bn_fold", "kernel_map",
+           "kernel_map_host", "kernel_map_transpose_host", "kernel_offsets", "sparse_batch_norm", "sparse_conv3d", "sparse_conv3d_bwd_host",
+           "sparse_conv3d_host", "sparse_instance_norm", "sparse_max_pool3d", "sparse_max_pool3d_bwd_host", "sparse_max_pool3d_host",
+           "sparse_norm_bwd_host", "sparse_norm_host", "sparse_segment_norm"]
+
+# MinkowskiInstanceNorm's epsilon, inside the square root: 1 / (var_biased + 1e-8).sqrt() per scene.  The ONE place that fixes it (our
+# reading of MinkowskiInstanceNormFunction; parity unpinned against ME itself)
+INSTANCE_NORM_EPS = 1e-8
 
 
 # ---------------------------------------------------------------------------------------------------------------- host restatement
@@ -190,6 +202,83 @@ def sparse_max_pool3d_bwd_host(g, feats, nbr) -> np.ndarray:
         m = nbr[:, j] >= 0
         dfeats[nbr[m, j]] += np.where(arg[m] == j, g[m], np.zeros((), g.dtype))
     return dfeats
+
+
+def _segments(seg_end: Sequence[int], n: int) -> List[int]:
+    ends = [int(e) for e in seg_end]
+    if not 1 <= len(ends) <= 64:
+        raise ValueError(f"1 to 64 segments, got {len(ends)}")
+    if any(b < a for a, b in zip([0] + ends[:-1], ends)) or ends[-1] != int(n):
+        raise ValueError(f"segment ends must ascend from 0 to the {n} rows, got {ends}")
+    return ends
+
+
+def sparse_norm_host(x, seg_end: Sequence[int], eps: float, weight=None, bias=None, residual=None, relu: bool = False,
+                     return_stats: bool = False, running=None, momentum: float = 0.1):
+    """numpy restatement of the norm kernels' forward in the dtype of ``x``, two-pass: per segment ``[seg_end[s-1], seg_end[s])`` and
+    column ``mean``, biased ``var = mean((x - mean)^2)``, ``rstd = 1 / sqrt(var + eps)``;
+    ``out = relu?(((x - mean) * rstd) * weight + bias (+ residual))``.  ``return_stats``: also ``stats (S, 2, C) = (mean, rstd)``, an
+    empty segment ``(0, 0)``.  ``running = (running_mean, running_var)`` (one segment of at least 2 rows): the two arrays are updated in
+    place as the kernel updates them, ``(1 - momentum) * old + momentum * new`` with the unbiased variance (``nn.BatchNorm1d``'s rule)."""
+    x = np.asarray(x)
+    dt = x.dtype
+    ends = _segments(seg_end, x.shape[0])
+    out = np.empty_like(x)
+    stats = np.zeros((len(ends), 2, x.shape[1]), dt)
+    lo = 0
+    for s, hi in enumerate(ends):
+        if hi > lo:
+            seg = x[lo:hi]
+            mean = seg.mean(axis=0, dtype=dt)
+            var = np.square(seg - mean).mean(axis=0, dtype=dt)
+            rstd = (1 / np.sqrt(var + dt.type(eps))).astype(dt, copy=False)
+            stats[s, 0], stats[s, 1] = mean, rstd
+            out[lo:hi] = (seg - mean) * rstd
+            if running is not None:
+                if len(ends) != 1 or hi < 2:
+                    raise ValueError("running statistics need one segment of at least 2 rows")
+                m = dt.type(momentum)
+                running[0][...] = (1 - m) * running[0] + m * mean
+                running[1][...] = (1 - m) * running[1] + m * (var * dt.type(hi) / dt.type(hi - 1))
+        lo = hi
+    if weight is not None:
+        out = out * np.asarray(weight, dt).reshape(1, -1)
+    if bias is not None:
+        out = out + np.asarray(bias, dt).reshape(1, -1)
+    if residual is not None:
+        out = out + np.asarray(residual, dt)
+    if relu:
+        out = np.maximum(out, 0)
+    out = out.astype(dt, copy=False)
+    return (out, stats) if return_stats else out
+
+
+def sparse_norm_bwd_host(g, x, seg_end: Sequence[int], eps: float, weight=None, out=None, relu: bool = False, stats=None) -> dict:
+    """numpy restatement of the norm kernels' backward in the dtype of ``g``: ``dict(dx, dweight, dbias, dresidual)``.  ``gy = g * [out > 0]``
+    with the ReLU mask taken from the ``out`` it is handed (``g`` itself without ReLU); ``xhat`` from ``x`` and ``stats`` (default: the
+    two-pass statistics of ``x``); ``dresidual = gy``, ``dbias = sum gy``, ``dweight = sum gy * xhat``; per segment ``a = mean gy``,
+    ``b = mean gy * xhat``, ``dx = weight * rstd * (gy - a - xhat * b)``."""
+    g = np.asarray(g)
+    dt = g.dtype
+    x = np.asarray(x, dt)
+    ends = _segments(seg_end, x.shape[0])
+    if stats is None:
+        _, stats = sparse_norm_host(x, ends, eps, return_stats=True)
+    stats = np.asarray(stats, dt)
+    gy = np.where(np.asarray(out) > 0, g, np.zeros((), dt)).astype(dt, copy=False) if relu else g
+    w = np.ones((1, x.shape[1]), dt) if weight is None else np.asarray(weight, dt).reshape(1, -1)
+    dx = np.empty_like(x)
+    xhat = np.empty_like(x)
+    lo = 0
+    for s, hi in enumerate(ends):
+        if hi > lo:
+            xh = (x[lo:hi] - stats[s, 0]) * stats[s, 1]
+            a = gy[lo:hi].mean(axis=0, dtype=dt)
+            b = (gy[lo:hi] * xh).mean(axis=0, dtype=dt)
+            dx[lo:hi] = (w * stats[s, 1]) * (gy[lo:hi] - a - xh * b)
+            xhat[lo:hi] = xh
+        lo = hi
+    return dict(dx=dx.astype(dt, copy=False), dweight=(gy * xhat).sum(axis=0, dtype=dt), dbias=gy.sum(axis=0, dtype=dt), dresidual=gy)
 
 
 # ---------------------------------------------------------------------------------------------------------------- device
@@ -489,6 +578,241 @@ def sparse_max_pool3d(feats: torch.Tensor, kmap: KernelMap, differentiable: bool
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- norms
+_NORM_WS: dict = {}                # stream -> uint8 workspace of ptx_sparse_norm_fwd / _bwd (reused across layers and steps, grown on demand)
+
+
+def _norm_workspace(n: int, S: int, C: int, dev) -> torch.Tensor:
+    nbytes = _abi.lib().ptx_sparse_norm_workspace_bytes(n, S, C)
+    if nbytes == 0:
+        raise ValueError(f"sparse norm: unsupported size, {n} rows x {C} channels in {S} segments (channels: a multiple of 64 up to 512; "
+                         f"1 to 64 segments)")
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    ws = _NORM_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _NORM_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, momentum=0.0):
+    """One call of ``ptx_sparse_norm_fwd`` on the current stream: ``(out, stats)``."""
+    n, C = int(x.shape[0]), int(x.shape[1])
+    S = len(ends)
+    dev = x.device
+    ws = _norm_workspace(n, S, C, dev)
+    out = torch.empty_like(x)
+    stats = torch.empty((S, 2, C), dtype=torch.float32, device=dev)
+    seg = (ctypes.c_int32 * S)(*ends)
+    rm, rv = running if running is not None else (None, None)
+    _abi.check(_abi.lib().ptx_sparse_norm_fwd(x.data_ptr(), seg, S, n, C, float(eps), _ptr(weight), _ptr(bias), _ptr(residual), int(bool(relu)),
+                                              _ptr(rm), _ptr(rv), float(momentum), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_fwd")
+    return out, stats
+
+
+def _norm_apply(x, ends, stats, weight, bias, residual, relu):
+    n, C = int(x.shape[0]), int(x.shape[1])
+    S = len(ends)
+    out = torch.empty_like(x)
+    seg = (ctypes.c_int32 * S)(*ends)
+    _abi.check(_abi.lib().ptx_sparse_norm_apply(x.data_ptr(), seg, S, n, C, stats.data_ptr(), _ptr(weight), _ptr(bias), _ptr(residual),
+                                                int(bool(relu)), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
+               "ptx_sparse_norm_apply")
+    return out
+
+
+class _SparseNormFn(torch.autograd.Function):
+    """x (n,C), weight / bias (any shape of C elements) or None, residual (n,C) or None: fp32, contiguous, on the device; ``running``:
+    ``(running_mean, running_var)`` updated in place by the kernel, or None."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, ends, eps, relu, running, momentum):
+        w = None if weight is None else weight.reshape(-1)
+        out, stats = _norm_forward(x, ends, eps, w, None if bias is None else bias.reshape(-1), residual, relu, running, momentum)
+        ctx.ends, ctx.relu = ends, bool(relu)
+        ctx.shapes = (None if weight is None else tuple(weight.shape), None if bias is None else tuple(bias.shape))
+        ctx.save_for_backward(x, stats, w, out if relu else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, stats, w, out = ctx.saved_tensors
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        dev = x.device
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.to(torch.float32).contiguous()
+        n, C = int(x.shape[0]), int(x.shape[1])
+        S = len(ctx.ends)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+        dx = new(n, C) if need_x else None
+        dw = new(C) if need_w else None
+        db = new(C) if need_b else None
+        dres = None
+        if need_r:                                           # g * [out > 0]: g itself without ReLU
+            dres = new(n, C) if ctx.relu else g
+        if need_x or need_w or need_b or (need_r and ctx.relu):
+            ws = _norm_workspace(n, S, C, dev)
+            seg = (ctypes.c_int32 * S)(*ctx.ends)
+            _abi.check(_abi.lib().ptx_sparse_norm_bwd(g.data_ptr(), x.data_ptr(), _ptr(out), seg, S, n, C, stats.data_ptr(), _ptr(w), _ptr(dx),
+                                                      _ptr(dw), _ptr(db), _ptr(dres) if ctx.relu else None, ws.data_ptr(), ws.numel(),
+                                                      torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_bwd")
+        if dw is not None:
+            dw = dw.reshape(ctx.shapes[0])
+        if db is not None:
+            db = db.reshape(ctx.shapes[1])
+        return dx, dw, db, dres, None, None, None, None, None
+
+
+def _norm_operands(what: str, feats, weight, bias, residual):
+    """The validated, detached fp32 operands of a norm call: ``(x, weight (C) or None, bias (C) or None, residual or None)``."""
+    if not feats.is_cuda:
+        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
+    dev = feats.device
+    x = _f32(feats, what, dev)
+    if x.dim() != 2 or x.shape[1] < 64 or x.shape[1] > 512 or x.shape[1] % 64:
+        raise ValueError(f"{what}: feats (n,C) with C a multiple of 64 up to 512 expected, got {tuple(x.shape)}")
+    C = int(x.shape[1])
+    vecs = []
+    for name, v in (("weight", weight), ("bias", bias)):
+        v = _f32(v, what, dev)
+        if v is not None:
+            v = v.reshape(-1)
+            if v.numel() != C:
+                raise ValueError(f"{what}: {name} must have {C} elements, got {v.numel()}")
+        vecs.append(v)
+    residual = _f32(residual, what, dev)
+    if residual is not None and tuple(residual.shape) != tuple(x.shape):
+        raise ValueError(f"{what}: residual must be {tuple(x.shape)}, got {tuple(residual.shape)}")
+    return x, vecs[0], vecs[1], residual
+
+
+def sparse_segment_norm(feats: torch.Tensor, seg_end: Sequence[int], eps: float, weight: Optional[torch.Tensor] = None,
+                        bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, relu: bool = False,
+                        differentiable: bool = False, return_stats: bool = False):
+    """The norm kernels as they are: per segment ``[seg_end[s-1], seg_end[s])`` of the rows ``feats (n, C)`` fp32 (C a multiple of 64 up to
+    512; 1 to 64 segments, empty ones allowed) and column, ``out = relu?((feats - mean) / sqrt(var_biased + eps) * weight + bias
+    (+ residual))`` -- one call of ``ptx_sparse_norm_fwd`` on the current stream (two reads and one write of the rows).  An empty
+    segment writes nothing; a one-row segment gives ``bias (+ residual)``.  ``return_stats`` (inference only): ``(out, stats (S, 2, C))``
+    with the segments' ``(mean, rstd)``.  Inference-only unless ``differentiable=True``: then, with grad mode on and ``feats`` /
+    ``weight`` / ``bias`` / ``residual`` requiring grad, the same launches are recorded for autograd (``ptx_sparse_norm_bwd``; same
+    output bits)."""
+    if differentiable:
+        train = _wants_grad(feats, weight, bias, residual)
+    else:
+        _inference_only("sparse_segment_norm", feats, weight, bias, residual)
+        train = False
+    x, w, b, res = _norm_operands("sparse_segment_norm", feats, weight, bias, residual)
+    ends = _segments(seg_end, x.shape[0])
+    if not train:
+        out, stats = _norm_forward(x, ends, eps, w, b, res, relu)
+        return (out, stats) if return_stats else out
+    if return_stats:
+        raise ValueError("sparse_segment_norm: return_stats is for inference calls")
+    return _SparseNormFn.apply(_f32_grad(feats), _f32_grad(weight), _f32_grad(bias), _f32_grad(residual), ends, float(eps), bool(relu), None,
+                               0.0)
+
+
+def sparse_instance_norm(feats: torch.Tensor, scene_rows: Sequence[int], weight: Optional[torch.Tensor] = None,
+                         bias: Optional[torch.Tensor] = None, relu: bool = False, differentiable: bool = False) -> torch.Tensor:
+    """``MinkowskiInstanceNorm`` on the rows: ``sparse_segment_norm`` per scene -- ``scene_rows[b]`` = end of scene b's rows -- with the
+    biased variance and ``INSTANCE_NORM_EPS`` inside the square root, ``weight`` / ``bias`` of ``C`` elements in any shape (ME's are
+    ``(1, C)``), an optional fused ReLU.  Inference-only unless ``differentiable=True``."""
+    return sparse_segment_norm(feats, scene_rows, INSTANCE_NORM_EPS, weight, bias, None, relu, differentiable)
+
+
+_BN_CACHE: dict = {}               # id(bn) -> (weak reference, key, {"fold": (scale, shift), "stats": (1,2,C)})
+
+
+def _bn_cached(bn: nn.Module, kind: str):
+    """Vectors derived from an eval BatchNorm's four tensors, cached per module and rebuilt when any tensor's ``_version`` (or storage)
+    changes -- a backbone of 36 BatchNorms must not pay 36 x 5 tiny launches per forward.  Tensors made under ``torch.inference_mode()``
+    carry no version: for them the vectors are rebuilt on every call."""
+    import weakref
+    tensors = (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    if any(t is not None and t.is_inference() for t in tensors):
+        made = {}                                            # an inference tensor has no version counter: nothing to key on, no caching
+    else:
+        key = tuple((None if t is None else (t._version, t.data_ptr(), str(t.device))) for t in tensors) + (float(bn.eps),)
+        hit = _BN_CACHE.get(id(bn))
+        if hit is None or hit[0]() is not bn or hit[1] != key:
+            ident = id(bn)
+            hit = _BN_CACHE[ident] = (weakref.ref(bn, lambda _r, ident=ident: _BN_CACHE.pop(ident, None)), key, {})
+        made = hit[2]
+    if kind not in made:
+        with torch.no_grad():
+            mean, var = bn.running_mean.float(), bn.running_var.float()
+            rstd = torch.rsqrt(var + bn.eps)
+            if kind == "stats":
+                made[kind] = torch.stack([mean, rstd]).unsqueeze(0).contiguous()
+            else:
+                scale = rstd if bn.weight is None else bn.weight.detach().float() * rstd
+                shift = -mean * scale if bn.bias is None else bn.bias.detach().float() - mean * scale
+                made[kind] = (scale.contiguous(), shift.contiguous())
+    return made[kind]
+
+
+def bn_fold(bn: nn.Module):
+    """``(scale, shift)`` of an eval-mode ``nn.BatchNorm1d`` -- ``y = x * scale + shift`` --, the operands of ``sparse_conv3d``'s
+    epilogue; cached per module, rebuilt when the ``_version`` of any of its four tensors changes."""
+    _check_bn(bn)
+    return _bn_cached(bn, "fold")
+
+
+def _check_bn(bn) -> None:
+    if not isinstance(bn, nn.modules.batchnorm._BatchNorm):
+        raise TypeError(f"an nn.BatchNorm1d expected, got {type(bn).__name__}")
+    if not bn.track_running_stats or bn.running_mean is None:
+        raise ValueError("sparse_batch_norm: track_running_stats=False is not supported (the eval path is the affine map from the running "
+                         "statistics)")
+    if bn.momentum is None:
+        raise ValueError("sparse_batch_norm: momentum=None (cumulative moving average) is not supported; give the BatchNorm a momentum")
+
+
+def sparse_batch_norm(feats: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor] = None, relu: bool = False,
+                      differentiable: bool = False) -> torch.Tensor:
+    """``relu?(bn(feats) (+ residual))`` for an ``nn.BatchNorm1d`` on the rows ``feats (n, C)`` (C a multiple of 64 up to 512).
+    ``bn.training``: the batch statistics of one segment over all rows; the kernel updates ``bn.running_mean`` / ``bn.running_var`` in
+    place by ``nn.BatchNorm1d``'s rule (unbiased variance) and ``bn.num_batches_tracked`` is incremented; ``n == 1`` is refused with
+    torch's own ``ValueError``.  Eval: the affine map from the running statistics through the same apply kernel.  Inference-only unless
+    ``differentiable=True``; then the training-mode call is recorded for autograd (gradients to ``feats``, ``bn.weight``, ``bn.bias``,
+    ``residual``).  An eval-mode BatchNorm is a constant affine map: to train through it fold it into ``sparse_conv3d`` (``bn_fold``)."""
+    _check_bn(bn)
+    if differentiable:
+        train = _wants_grad(feats, bn.weight, bn.bias, residual)
+    else:
+        _inference_only("sparse_batch_norm", feats, bn.weight, bn.bias, residual)
+        train = False
+    if feats.dim() == 2 and bn.num_features != feats.shape[1]:
+        raise ValueError(f"sparse_batch_norm: the BatchNorm has {bn.num_features} features, feats has {feats.shape[1]} channels")
+    x, w, b, res = _norm_operands("sparse_batch_norm", feats, bn.weight, bn.bias, residual)
+    n, C = int(x.shape[0]), int(x.shape[1])
+    if not bn.training:
+        if train:
+            raise NotImplementedError("sparse_batch_norm(differentiable=True) in eval mode: a frozen BatchNorm is a constant affine map; fold "
+                                      "it into sparse_conv3d's scale / shift (bn_fold) to train through it, or call bn.train()")
+        return _norm_apply(x, [n], _bn_cached(bn, "stats"), w, b, res, relu)
+    if n <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([n, C])}")
+    running = (bn.running_mean, bn.running_var)
+    if any(t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device for t in running):
+        raise ValueError("sparse_batch_norm: running_mean / running_var must be contiguous fp32 tensors on the device of feats")
+    if train:
+        out = _SparseNormFn.apply(_f32_grad(feats), _f32_grad(bn.weight), _f32_grad(bn.bias), _f32_grad(residual), [n], float(bn.eps),
+                                  bool(relu), running, float(bn.momentum))
+    else:
+        out = _norm_forward(x, [n], float(bn.eps), w, b, res, relu, running, float(bn.momentum))[0]
+    for t in running:                                        # written by the kernel: tell torch (the fold cache watches _version)
+        torch.autograd.graph.increment_version(t)
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return out
+
+
 class SparseConv3d(nn.Module):
     """``ME.MinkowskiConvolution(in_channels, out_channels, kernel_size, stride, bias, dimension=3)`` over a ``KernelMap``.  The
     parameters carry ME's names and shapes -- ``kernel (k^3, Cin, Cout)``, ``bias (1, Cout)`` -- so that a reference checkpoint's
@@ -520,3 +844,34 @@ class SparseConv3d(nn.Module):
 
     def extra_repr(self) -> str:
         return f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, bias={self.bias is not None}"
+
+
+class SparseInstanceNorm(nn.Module):
+    """``ME.MinkowskiInstanceNorm(num_features)``: ``weight (1, C)`` ones and ``bias (1, C)`` zeros, ME's names and shapes.
+    ``forward(feats, scene_rows, relu=False)`` = ``sparse_instance_norm``."""
+
+    def __init__(self, num_features: int, differentiable: bool = False):
+        super().__init__()
+        self.num_features, self.differentiable = int(num_features), bool(differentiable)
+        self.weight = nn.Parameter(torch.ones(1, self.num_features))
+        self.bias = nn.Parameter(torch.zeros(1, self.num_features))
+
+    def forward(self, feats: torch.Tensor, scene_rows: Sequence[int], relu: bool = False) -> torch.Tensor:
+        return sparse_instance_norm(feats, scene_rows, self.weight, self.bias, relu, differentiable=self.differentiable)
+
+    def extra_repr(self) -> str:
+        return f"{self.num_features}"
+
+
+class SparseBatchNorm(nn.Module):
+    """``ME.MinkowskiBatchNorm(num_features, eps, momentum)``: a child ``bn = nn.BatchNorm1d`` as in ME, so the keys are ``bn.weight``,
+    ``bn.bias``, ``bn.running_mean``, ``bn.running_var``, ``bn.num_batches_tracked``.  ``forward(feats, residual=None, relu=False)`` =
+    ``sparse_batch_norm``."""
+
+    def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1, differentiable: bool = False):
+        super().__init__()
+        self.differentiable = bool(differentiable)
+        self.bn = nn.BatchNorm1d(int(num_features), eps=eps, momentum=momentum)
+
+    def forward(self, feats: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+        return sparse_batch_norm(feats, self.bn, residual, relu, differentiable=self.differentiable)

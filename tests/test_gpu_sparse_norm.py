@@ -1,0 +1,232 @@
+"""The norm kernels on the voxel rows (proxytransformation_amd/sparse.py, csrc/sparse_norm.hip): instance norm and training batch norm,
+forward and backward, against the float64 restatement ``sparse_norm_host`` / ``sparse_norm_bwd_host`` under the rule of the
+convolution's tests (``_hold``: at most 8 x the error of the same fp32 chain on the CPU, which itself must be below 1e-5).
+
+Segments of 256, 257, 0, 1 and 1000 rows (1514 in all): a full tile, a tile plus one row, an empty segment, a single row and a
+partial last tile; widths 64 and 512.  The conditioning case puts the columns at +-16 with unit spread: the fp32 two-pass restatement
+errs 2e-6 to 8e-6 of scale there and a tile-wise Chan merge below 1e-6, while E[x^2] - E[x]^2 in fp32 errs 1.6e-4 to 4.3e-4, so the
+bar separates them by more than 20 x."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from proxytransformation_amd import sparse
+from tests.test_gpu_sparse_conv import _hold
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+SEGMENTS = [256, 513, 513, 514, 1514]
+N = SEGMENTS[-1]
+EPS = sparse.INSTANCE_NORM_EPS
+
+
+def t(a):
+    return torch.from_numpy(a).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _data(C, offset):
+    rng = np.random.default_rng(100 + C + offset)
+    x = rng.standard_normal((N, C)).astype(np.float32)
+    if offset:
+        x += (offset * np.where(rng.random(C) < 0.5, -1.0, 1.0)).astype(np.float32)
+    ops = dict(x=x, weight=rng.uniform(0.5, 1.5, C).astype(np.float32), bias=(rng.standard_normal(C) * 0.5).astype(np.float32),
+               residual=rng.standard_normal((N, C)).astype(np.float32), g=rng.standard_normal((N, C)).astype(np.float32))
+    return ops
+
+
+def _refs(ops, ends, eps, use=(), relu=False):
+    r64 = sparse.sparse_norm_host(ops["x"].astype(np.float64), ends, eps, relu=relu, **{u: ops[u].astype(np.float64) for u in use})
+    r32 = sparse.sparse_norm_host(ops["x"], ends, eps, relu=relu, **{u: ops[u] for u in use})
+    assert r32.dtype == np.float32
+    return r32, r64
+
+
+# ------------------------------------------------------------------------------------------------------------------ forward
+@pytest.mark.parametrize("C", [64, 512])
+def test_conditioning_columns_far_from_zero(C):
+    """(a) x = N(0,1) + 16 * (+-1 per column): what E[x^2] - E[x]^2 cannot do in fp32."""
+    ops = _data(C, 16)
+    got, stats = sparse.sparse_segment_norm(t(ops["x"]), SEGMENTS, EPS, return_stats=True)
+    r32, r64 = _refs(ops, SEGMENTS, EPS)
+    _hold(f"norm conditioning C={C}", got.cpu().numpy(), r32, r64)
+    _, s64 = sparse.sparse_norm_host(ops["x"].astype(np.float64), SEGMENTS, EPS, return_stats=True)
+    stats = stats.cpu().numpy()
+    for s in (0, 1, 4):                                      # the statistics themselves, to a few fp32 ulps of their size
+        assert float(np.abs(stats[s, 0] - s64[s, 0]).max()) <= 4e-6 * 16
+        assert float(np.abs(stats[s, 1] / s64[s, 1] - 1).max()) <= 4e-6
+
+
+@pytest.mark.parametrize("C", [64, 512])
+def test_affine_residual_relu_and_the_edge_segments(C):
+    """(b), (e), (f): zero-mean data with weight, bias, residual and ReLU; two calls give equal bits; the empty segment's stats are zero,
+    the one-row segment's output is bias + residual exactly."""
+    ops = _data(C, 0)
+    use = ("weight", "bias", "residual")
+    call = lambda relu: sparse.sparse_segment_norm(t(ops["x"]), SEGMENTS, EPS, t(ops["weight"]), t(ops["bias"]), t(ops["residual"]), relu,  # noqa: E731
+                                                   return_stats=True)
+    got, stats = call(True)
+    again, stats2 = call(True)
+    assert got.dtype == torch.float32 and got.shape == (N, C)
+    assert torch.equal(got, again) and torch.equal(stats, stats2), "two calls on the same inputs differ"
+    r32, r64 = _refs(ops, SEGMENTS, EPS, use, True)
+    _hold(f"norm affine+residual+relu C={C}", got.cpu().numpy(), r32, r64)
+    assert float(got.min()) == 0.0
+    plain, _ = call(False)
+    r32, r64 = _refs(ops, SEGMENTS, EPS, use, False)
+    _hold(f"norm affine+residual C={C}", plain.cpu().numpy(), r32, r64)
+    stats = stats.cpu().numpy()
+    assert stats.shape == (5, 2, C) and np.array_equal(stats[2], np.zeros((2, C), np.float32))
+    assert np.array_equal(plain.cpu().numpy()[513], ops["bias"] + ops["residual"][513])
+    assert np.array_equal(stats[3, 0], ops["x"][513])
+    bare = sparse.sparse_instance_norm(t(ops["x"]), SEGMENTS)
+    r32, r64 = _refs(ops, SEGMENTS, EPS)
+    _hold(f"instance norm C={C}", bare.cpu().numpy(), r32, r64)
+    mod = sparse.SparseInstanceNorm(C).to(DEV)
+    with torch.no_grad():
+        assert torch.equal(mod(t(ops["x"]), SEGMENTS), bare)  # weight 1, bias 0: x * 1 + 0
+
+
+def _bn_pair(C, seed):
+    rng = np.random.default_rng(seed)
+    bn64 = torch.nn.BatchNorm1d(C, eps=1e-5, momentum=0.1).double()
+    with torch.no_grad():
+        bn64.weight.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, C).astype(np.float32)))
+        bn64.bias.copy_(torch.from_numpy((rng.standard_normal(C) * 0.5).astype(np.float32)))
+        bn64.running_mean.copy_(torch.from_numpy((rng.standard_normal(C) * 0.1).astype(np.float32)))
+        bn64.running_var.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, C).astype(np.float32)))
+    bn32 = torch.nn.BatchNorm1d(C, eps=1e-5, momentum=0.1)
+    bn32.load_state_dict({k: v.float() if v.is_floating_point() else v for k, v in bn64.state_dict().items()})
+    gpu = torch.nn.BatchNorm1d(C, eps=1e-5, momentum=0.1)
+    gpu.load_state_dict(bn32.state_dict())
+    return bn64.train(), bn32.train(), gpu.to(DEV).train()
+
+
+@pytest.mark.parametrize("C", [64, 512])
+def test_training_batch_norm_two_steps_against_torch(C):
+    """(c) one segment with the running statistics, two consecutive steps, against nn.BatchNorm1d in float64 on the CPU (yardstick: the
+    same module in float32 on the CPU)."""
+    ops = _data(C, 0)
+    bn64, bn32, gpu = _bn_pair(C, 7)
+    for step, rows in enumerate((slice(0, N), slice(200, 1101))):
+        x = np.ascontiguousarray(ops["x"][rows]) * np.float32(1.5) + np.float32(0.25)
+        with torch.no_grad():
+            ref64 = bn64(torch.from_numpy(x).double()).numpy()
+            ref32 = bn32(torch.from_numpy(x)).numpy()
+            got = sparse.sparse_batch_norm(t(x), gpu)
+        _hold(f"batch norm C={C} step {step} out", got.cpu().numpy(), ref32, ref64)
+        _hold(f"batch norm C={C} step {step} running_mean", gpu.running_mean.cpu().numpy(), bn32.running_mean.numpy(), bn64.running_mean.numpy())
+        _hold(f"batch norm C={C} step {step} running_var", gpu.running_var.cpu().numpy(), bn32.running_var.numpy(), bn64.running_var.numpy())
+        assert int(gpu.num_batches_tracked) == step + 1
+    version = gpu.running_var._version
+    with torch.no_grad():
+        x = t(ops["x"])
+        want = bn32.eval()(torch.from_numpy(ops["x"])).numpy()
+        ref64 = bn64.eval()(torch.from_numpy(ops["x"]).double()).numpy()
+        got = sparse.sparse_batch_norm(x, gpu.eval())           # eval: the affine map from the running statistics
+        _hold(f"batch norm C={C} eval", got.cpu().numpy(), want, ref64)
+        assert gpu.running_var._version == version and int(gpu.num_batches_tracked) == 2
+        scale, shift = sparse.bn_fold(gpu)
+        assert sparse.bn_fold(gpu)[0] is scale                # cached
+        gpu.train()
+        sparse.sparse_batch_norm(x, gpu)
+        assert sparse.bn_fold(gpu.eval())[0] is not scale     # the kernel's update is seen: the fold is rebuilt
+        with pytest.raises(ValueError, match="Expected more than 1 value per channel"):
+            sparse.sparse_batch_norm(x[:1], gpu.train())
+
+
+# ------------------------------------------------------------------------------------------------------------------ backward
+def _hold_grads(name, got, ops, ends, eps, out, relu, weight=True):
+    """``got``: dict of numpy gradients; the ReLU mask of both references is the GPU's ``out``."""
+    kw = dict(out=out, relu=relu)
+    r64 = sparse.sparse_norm_bwd_host(ops["g"].astype(np.float64), ops["x"].astype(np.float64), ends, eps,
+                                      ops["weight"].astype(np.float64) if weight else None, **kw)
+    r32 = sparse.sparse_norm_bwd_host(ops["g"], ops["x"], ends, eps, ops["weight"] if weight else None, **kw)
+    for k, v in got.items():
+        assert v.shape == r64[k].shape and v.dtype == np.float32, k
+        _hold(f"{name} {k}", v, r32[k], r64[k])
+
+
+@pytest.mark.parametrize("C", [64, 512])
+def test_backward_of_the_segment_norm(C):
+    """(d), (e) for (b): dx, dweight, dbias, dresidual; dresidual is bit-equal to where(out > 0, g, 0); two backwards give equal bits."""
+    ops = _data(C, 0)
+
+    def step(relu, wrt):
+        leaves = {k: t(ops[k]).requires_grad_(k in wrt) for k in ("x", "weight", "bias", "residual")}
+        out = sparse.sparse_segment_norm(leaves["x"], SEGMENTS, EPS, leaves["weight"], leaves["bias"], leaves["residual"], relu,
+                                         differentiable=True)
+        out.backward(t(ops["g"]))
+        return out.detach(), {k: v.grad for k, v in leaves.items()}
+
+    every = ("x", "weight", "bias", "residual")
+    out, grads = step(True, every)
+    out2, grads2 = step(True, every)
+    with torch.no_grad():
+        assert torch.equal(out, sparse.sparse_segment_norm(t(ops["x"]), SEGMENTS, EPS, t(ops["weight"]), t(ops["bias"]), t(ops["residual"]), True))
+    assert torch.equal(out, out2) and all(torch.equal(grads[k], grads2[k]) for k in every), "two backwards on the same inputs differ"
+    out_np = out.cpu().numpy()
+    assert 0.2 < float((out_np == 0).mean()) < 0.8
+    assert np.array_equal(grads["residual"].cpu().numpy(), np.where(out_np > 0, ops["g"], np.float32(0)))
+    assert grads["weight"].shape == (C,) and grads["x"].shape == (N, C)
+    got = dict(dx=grads["x"].cpu().numpy(), dweight=grads["weight"].cpu().numpy(), dbias=grads["bias"].cpu().numpy(),
+               dresidual=grads["residual"].cpu().numpy())
+    _hold_grads(f"norm bwd relu C={C}", got, ops, SEGMENTS, EPS, out_np, True)
+    # needs_input_grad is honoured: only what was asked for comes back, with the same bits
+    _, only_x = step(True, ("x",))
+    assert torch.equal(only_x["x"], grads["x"]) and only_x["weight"] is None and only_x["residual"] is None
+    _, only_w = step(True, ("weight", "bias"))
+    assert torch.equal(only_w["weight"], grads["weight"]) and torch.equal(only_w["bias"], grads["bias"]) and only_w["x"] is None
+    # without ReLU: the gradient itself is dresidual
+    out, grads = step(False, every)
+    assert torch.equal(grads["residual"], t(ops["g"]))
+    got = dict(dx=grads["x"].cpu().numpy(), dweight=grads["weight"].cpu().numpy(), dbias=grads["bias"].cpu().numpy())
+    _hold_grads(f"norm bwd C={C}", got, ops, SEGMENTS, EPS, None, False)
+
+
+@pytest.mark.parametrize("C", [64, 512])
+def test_backward_of_the_training_batch_norm(C):
+    """(d) for (c): one segment, through ``sparse_batch_norm`` and the module's own parameters, with residual and ReLU."""
+    ops = _data(C, 0)
+    _, _, gpu = _bn_pair(C, 9)
+    with torch.no_grad():
+        gpu.weight.copy_(t(ops["weight"]))
+    x, res = t(ops["x"]).requires_grad_(), t(ops["residual"]).requires_grad_()
+    out = sparse.sparse_batch_norm(x, gpu, residual=res, relu=True, differentiable=True)
+    out.backward(t(ops["g"]))
+    out_np = out.detach().cpu().numpy()
+    assert np.array_equal(res.grad.cpu().numpy(), np.where(out_np > 0, ops["g"], np.float32(0)))
+    got = dict(dx=x.grad.cpu().numpy(), dweight=gpu.weight.grad.cpu().numpy(), dbias=gpu.bias.grad.cpu().numpy(), dresidual=res.grad.cpu().numpy())
+    _hold_grads(f"batch norm bwd C={C}", got, ops, [N], gpu.eps, out_np, True)
+    assert int(gpu.num_batches_tracked) == 1
+
+
+# ------------------------------------------------------------------------------------------------------------------ surface
+def test_opt_in_surface_and_rejections():
+    """(g)"""
+    x = torch.zeros(8, 64, device=DEV)
+    with pytest.raises(NotImplementedError, match="backward"):
+        sparse.sparse_instance_norm(x.clone().requires_grad_(), [8])
+    with pytest.raises(NotImplementedError, match="backward"):
+        sparse.sparse_segment_norm(x, [8], 1e-5, weight=torch.ones(64, device=DEV, requires_grad=True))
+    with pytest.raises(NotImplementedError, match="backward"):
+        sparse.SparseBatchNorm(64).to(DEV)(x)                # its own parameters require grad
+    with pytest.raises(NotImplementedError, match="eval mode"):
+        sparse.SparseBatchNorm(64, differentiable=True).to(DEV).eval()(x)
+    with torch.no_grad():
+        assert sparse.SparseBatchNorm(64).to(DEV).eval()(x).shape == (8, 64)
+        with pytest.raises(ValueError, match="multiple of 64"):
+            sparse.sparse_instance_norm(torch.zeros(8, 96, device=DEV), [8])
+        with pytest.raises(ValueError, match="segment ends"):
+            sparse.sparse_instance_norm(x, [5, 3])
+        with pytest.raises(ValueError, match="residual must be"):
+            sparse.sparse_segment_norm(x, [8], 1e-5, residual=torch.zeros(8, 128, device=DEV))
+        with pytest.raises(ValueError, match="64 features"):
+            sparse.sparse_batch_norm(torch.zeros(8, 128, device=DEV), torch.nn.BatchNorm1d(64).to(DEV))
+        empty = sparse.sparse_segment_norm(torch.zeros(0, 64, device=DEV), [0, 0], 1e-5, return_stats=True)
+        assert empty[0].shape == (0, 64) and float(empty[1].abs().max()) == 0.0
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        sparse.sparse_instance_norm(torch.zeros(8, 64), [8])

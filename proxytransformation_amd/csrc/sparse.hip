@@ -23,14 +23,10 @@
 //
 // The offset index j (row of `weight`) counts x fastest, then y, then z -- our reading of MinkowskiEngine's region iterator,
 // "parity unpinned" against ME itself, bit-exact against the host restatement (proxytransformation_amd/sparse.py).
-#include "common.h"
-#include "mfma64.h"
 #include "voxel.h"
 #include "sparse.h"
 
 namespace ptx {
-
-constexpr int kSpMaxVol = 27;              // kernel_size <= 3
 
 // ---- kernel map -----------------------------------------------------------------------------------------------------------
 struct KmapArgs {
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
     const int nchunk = STEM ? 2 : (a.Cin + 63) >> 6;
     const int nsteps = STEM ? (s_list[kSpMaxVol] > 0 ? 2 : 0) : s_list[kSpMaxVol] * nchunk;
     // staging.  A: thread (ar + 16 i, kq .. kq + 3), 16 lanes = one 256-B row piece.  W: thread (k = wk + 16 i, n = wn .. wn + 3), written
-    // transposed as four dwords -- the 32 lanes of a write group hold 16 k x 2 n-quads, banks wk + 16 (quad & 1): conflict-free
+    // transposed (stash_t4)
     const int ar = tid >> 4, kq = (tid & 15) * 4;
     const int wk = lane & 15, wn = (wid * 4 + (lane >> 4)) * 4;
     static_assert(!(STEM && WT), "the stem's dfeats has a kernel of its own");
@@ -183,31 +179,24 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
             } else {
                 const int idx = s_nbr[row * kvol + j];
                 av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (idx >= 0 && c0 + kq < a.Cin) av[i] = *reinterpret_cast<const float4 *>(a.feats + (size_t)idx * a.Cin + c0 + kq);
+                if (idx >= 0 && c0 + kq < a.Cin) av[i] = ld4(a.feats + (size_t)idx * a.Cin + c0 + kq);
             }
             wv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (WT) {                                       // column col0 + row of the slab, k = c0 + kq .. + 3 contiguous (Cin % 64 == 0)
-                wv[i] = *reinterpret_cast<const float4 *>(a.weight + ((size_t)j * a.Cout + col0 + row) * a.Cin + c0 + kq);
+                wv[i] = ld4(a.weight + ((size_t)j * a.Cout + col0 + row) * a.Cin + c0 + kq);
             } else {
                 const int k = c0 + wk + 16 * i;             // row of the (kvol * Cin, Cout) weight matrix, minus j * Cin
                 const bool wok = STEM ? k < 81 : k < a.Cin;
-                if (wok) wv[i] = *reinterpret_cast<const float4 *>(a.weight + ((size_t)j * a.Cin + k) * a.Cout + col0 + wn);
+                if (wok) wv[i] = ld4(a.weight + ((size_t)j * a.Cin + k) * a.Cout + col0 + wn);
             }
         }
     };
     auto stash = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            *reinterpret_cast<float4 *>(&As[kq >> 5][ar + 16 * i][kq & 31]) = av[i];
-            if (WT) {
-                *reinterpret_cast<float4 *>(&Ws[kq >> 5][ar + 16 * i][kq & 31]) = wv[i];
-                continue;
-            }
-            const int k = wk + 16 * i;
-            Ws[k >> 5][wn + 0][k & 31] = wv[i].x;
-            Ws[k >> 5][wn + 1][k & 31] = wv[i].y;
-            Ws[k >> 5][wn + 2][k & 31] = wv[i].z;
-            Ws[k >> 5][wn + 3][k & 31] = wv[i].w;
+            st4(&As[kq >> 5][ar + 16 * i][kq & 31], av[i]);
+            if (WT) st4(&Ws[kq >> 5][ar + 16 * i][kq & 31], wv[i]);
+            else stash_t4(Ws, wk + 16 * i, wn, wv[i]);
         }
     };
 
@@ -216,14 +205,8 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
         stash();
         __syncthreads();
         if (s + 1 < nsteps) fetch(s + 1);                   // in flight behind this step's matrix instructions
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-        PTX_G64_COMPUTE(0);
         const int c0 = (STEM ? s : s % nchunk) << 6;
-        if ((STEM ? 84 : a.Cin) - c0 > 32) PTX_G64_COMPUTE(1);          // work-group uniform
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tot[i] += acc[i];
+        PTX_SPARSE_STEP(tot, (STEM ? 84 : a.Cin) - c0 > 32);
         __syncthreads();
     }
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
@@ -241,21 +224,51 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
 }
 
 // ---- max-pool: one thread per (output row, 4 channels) ------------------------------------------------------------------------
+// ARG: also the offset that supplied the maximum: the first present neighbour, replaced only by a strictly larger value -- ties go to
+// the smallest j; 255 for a row without neighbours
+template <bool ARG>
 __global__ __launch_bounds__(256) void k_sparse_max_pool(const float *__restrict__ feats, const int32_t *__restrict__ nbr, int n_out,
-                                                         int kvol, int C, float *__restrict__ out)
+                                                         int kvol, int C, float *__restrict__ out, uint8_t *__restrict__ arg)
 {
     const int c4n = C >> 2;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const int o = (int)(t / c4n), c4 = (int)(t - (long)o * c4n);
     if (o >= n_out) return;
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    uchar4 w = make_uchar4(255, 255, 255, 255);
     for (int j = 0; j < kvol; ++j) {
         const int idx = nbr[(size_t)o * kvol + j];
         if (idx < 0) continue;
         const float4 x = *reinterpret_cast<const float4 *>(feats + (size_t)idx * C + c4 * 4);
+        if (ARG) {
+            if (x.x > m.x || w.x == 255) w.x = (unsigned char)j;
+            if (x.y > m.y || w.y == 255) w.y = (unsigned char)j;
+            if (x.z > m.z || w.z == 255) w.z = (unsigned char)j;
+            if (x.w > m.w || w.w == 255) w.w = (unsigned char)j;
+        }
         m.x = fmaxf(m.x, x.x); m.y = fmaxf(m.y, x.y); m.z = fmaxf(m.z, x.z); m.w = fmaxf(m.w, x.w);
     }
     *reinterpret_cast<float4 *>(out + (size_t)o * C + c4 * 4) = m;
+    if (ARG) *reinterpret_cast<uchar4 *>(arg + (size_t)o * C + c4 * 4) = w;
+}
+
+// both pool entry points: `who` names the one that was called in its messages
+template <bool ARG>
+static int sparse_max_pool(const char *who, const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, uint8_t *arg,
+                           void *stream)
+{
+    PTX_REQUIRE(n_out >= 0 && kvol >= 1 && kvol <= kSpMaxVol && C >= 4 && C % 4 == 0, "%s: n_out=%d kvol=%d C=%d (C: a multiple of 4)", who,
+                n_out, kvol, C);
+    if (n_out == 0) return PTX_OK;
+    PTX_REQUIRE(feats && nbr && out && (arg || !ARG), "%s: null argument", who);
+    PTX_REQUIRE(sp_aligned16({feats, out}) && (reinterpret_cast<uintptr_t>(arg) & 3) == 0, "%s: feats and out must be 16-byte aligned%s", who,
+                ARG ? ", arg 4-byte aligned" : "");
+    PTX_TRY(sp_rows_fit(who, n_out, C));
+    const long threads = (long)n_out * (C / 4);
+    hipLaunchKernelGGL(k_sparse_max_pool<ARG>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), feats, nbr,
+                       n_out, kvol, C, out, arg);
+    PTX_LAUNCHED(ARG ? "k_sparse_max_pool_arg" : "k_sparse_max_pool");
+    return PTX_OK;
 }
 
 // dfeats (n_in, Cin) = sum_j gz[nbr_t[:, j]] @ weight[j]^T: the forward kernel over the transposed map, rows and widths swapped
@@ -301,7 +314,7 @@ int ptx_sparse_kernel_map(const int32_t *coords_in, const int32_t *in_scene_end,
     PTX_REQUIRE((long)B * ncap <= (1l << 30) && (long)n_in * kvol < (1l << 31), "ptx_sparse_kernel_map: %d rows x %d offsets is out of range",
                 n_in, kvol);
     const KmapLayout L = kmap_layout(B, ncap);
-    if (ws_bytes < L.total) { set_error("ptx_sparse_kernel_map: workspace too small: %zu < %zu bytes", ws_bytes, L.total); return PTX_ENOSPACE; }
+    PTX_TRY(sp_workspace_fits("ptx_sparse_kernel_map", ws_bytes, L.total));
     PTX_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "ptx_sparse_kernel_map: workspace must be 256-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     char *ws = static_cast<char *>(workspace);
@@ -331,13 +344,12 @@ int ptx_sparse_conv3d(const float *feats, int n_in, const int32_t *nbr, int n_ou
     PTX_REQUIRE(n_in >= 0 && n_out >= 0 && (kvol == 1 || kvol == 8 || kvol == 27), "ptx_sparse_conv3d: n_in=%d n_out=%d kvol=%d (kvol: 1, 8 or 27)",
                 n_in, n_out, kvol);
     const bool stem = Cin == 3;
-    PTX_REQUIRE(Cout >= 64 && Cout <= 512 && Cout % 64 == 0 && ((stem && kvol == 27) || (Cin >= 16 && Cin <= 512 && Cin % 16 == 0)),
+    PTX_REQUIRE(sp_width_ok(Cout) && ((stem && kvol == 27) || (Cin >= 16 && Cin <= 512 && Cin % 16 == 0)),
                 "ptx_sparse_conv3d: Cin=%d Cout=%d kvol=%d (Cin: 3 with 27 offsets, or a multiple of 16 up to 512; Cout: a multiple of 64 up "
                 "to 512)", Cin, Cout, kvol);
     if (n_out == 0) return PTX_OK;
     PTX_REQUIRE((feats || n_in == 0) && nbr && weight && out, "ptx_sparse_conv3d: null argument");
-    PTX_REQUIRE(((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(weight)) & 15) == 0,
-                "ptx_sparse_conv3d: feats and weight must be 16-byte aligned");
+    PTX_REQUIRE(sp_aligned16({feats, weight}), "ptx_sparse_conv3d: feats and weight must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const SpConvArgs a{feats, nbr, weight, bias, scale, shift, residual, out, n_in, n_out, kvol, Cin, Cout, relu};
     const dim3 grid(cdiv(n_out, 64), Cout / 64);
@@ -349,18 +361,12 @@ int ptx_sparse_conv3d(const float *feats, int n_in, const int32_t *nbr, int n_ou
 
 int ptx_sparse_max_pool3d(const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, void *stream)
 {
-    PTX_REQUIRE(n_out >= 0 && kvol >= 1 && kvol <= kSpMaxVol && C >= 4 && C % 4 == 0, "ptx_sparse_max_pool3d: n_out=%d kvol=%d C=%d (C: a multiple of 4)",
-                n_out, kvol, C);
-    if (n_out == 0) return PTX_OK;
-    PTX_REQUIRE(feats && nbr && out, "ptx_sparse_max_pool3d: null argument");
-    PTX_REQUIRE(((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
-                "ptx_sparse_max_pool3d: feats and out must be 16-byte aligned");
-    const long threads = (long)n_out * (C / 4);
-    PTX_REQUIRE(threads < (1l << 31) * 256, "ptx_sparse_max_pool3d: %d rows x %d channels is out of range", n_out, C);
-    hipLaunchKernelGGL(k_sparse_max_pool, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), feats, nbr,
-                       n_out, kvol, C, out);
-    PTX_LAUNCHED("k_sparse_max_pool");
-    return PTX_OK;
+    return sparse_max_pool<false>("ptx_sparse_max_pool3d", feats, nbr, n_out, kvol, C, out, nullptr, stream);
+}
+
+int ptx_sparse_max_pool3d_arg(const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, uint8_t *arg, void *stream)
+{
+    return sparse_max_pool<true>("ptx_sparse_max_pool3d_arg", feats, nbr, n_out, kvol, C, out, arg, stream);
 }
 
 }  // extern "C"

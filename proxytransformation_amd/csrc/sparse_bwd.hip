@@ -10,23 +10,19 @@
 //       dweight[j] = sum_o feats[nbr[o, j]]^T @ gz[o]     k_sparse_dweight: grid (S row chunks) x (kvol * Cin/64 * Cout/64); a work-group
 //                            compacts the present (o, idx) pairs of its offset, 1024 rows at a time, into an LDS list in ascending o and
 //                            runs dense 64-pair steps on the exact-fp32 matrix instruction (mfma64.h), both operands written to LDS
-//                            transposed (pair index contiguous) with k_sparse_conv's four-dword pattern; the next step's loads are in
+//                            transposed (pair index contiguous; stash_t4 of sparse.h); the next step's loads are in
 //                            flight behind this step's matrix instructions.  Blocked summation like the forward: a step's product from
 //                            zero, then added to the running sum.  S > 1: every work-group writes its 64 x 64 partial into slab
 //                            blockIdx.x of the workspace (a chunk without a pair writes zeros: no memset), k_sparse_slab_sum adds the
 //                            slabs in ascending order.  Cin = 3: k_sparse_dweight_stem, VALU, 64-row blocks from zero.
-//   ptx_sparse_max_pool3d_arg / _bwd  the pool with the offset that supplied the maximum (ties: the smallest j), and its routing.
+//   ptx_sparse_max_pool3d_bwd         routes each gradient to the offset ptx_sparse_max_pool3d_arg (sparse.hip) recorded.
 //
 // No float atomics anywhere: every output is bitwise reproducible.  Everything runs on the caller's stream; no host wait.
-#include "common.h"
-#include "mfma64.h"
 #include "sparse.h"
 
 namespace ptx {
 
-constexpr int kSpMaxVol = 27;
 constexpr int kDwSub = 1024;               // rows compacted into LDS at a time
-constexpr int kEpiRows = 256;              // rows per column-sum tile of the epilogue backward
 
 // ---- transposed kernel map ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sparse_map_transpose(const int32_t *__restrict__ nbr, long total, int kvol, int n_in,
@@ -41,7 +37,7 @@ __global__ __launch_bounds__(256) void k_sparse_map_transpose(const int32_t *__r
 }
 
 // ---- epilogue backward ----------------------------------------------------------------------------------------------------
-// grid (cdiv(n_out, 256), Cout / 64); thread (row slot = tid >> 4, 4 channels = tid & 15); gz / dres / part each optional
+// grid (cdiv(n_out, kSpTile), Cout / 64), the streaming idiom of sparse.h; gz / dres / part each optional
 __global__ __launch_bounds__(256) void k_sparse_epi_bwd(const float *__restrict__ g, const float *__restrict__ out,
                                                         const float *__restrict__ scale, float *__restrict__ gz, float *__restrict__ dres,
                                                         float *__restrict__ part, int n_out, int Cout)
@@ -53,30 +49,22 @@ __global__ __launch_bounds__(256) void k_sparse_epi_bwd(const float *__restrict_
     if (scale) sc = *reinterpret_cast<const float4 *>(scale + col);
     float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 4
-    for (int i = 0; i < kEpiRows / 16; ++i) {
-        const int row = blockIdx.x * kEpiRows + slot + 16 * i;
+    for (int i = 0; i < kSpTile / 16; ++i) {
+        const int row = blockIdx.x * kSpTile + slot + 16 * i;
         if (row >= n_out) break;
         const size_t at = (size_t)row * Cout + col;
-        float4 d = *reinterpret_cast<const float4 *>(g + at);
-        if (out) {
-            const float4 o = *reinterpret_cast<const float4 *>(out + at);
-            d.x = o.x > 0.0f ? d.x : 0.0f; d.y = o.y > 0.0f ? d.y : 0.0f; d.z = o.z > 0.0f ? d.z : 0.0f; d.w = o.w > 0.0f ? d.w : 0.0f;
-        }
-        if (dres) *reinterpret_cast<float4 *>(dres + at) = d;
+        float4 d = ld4(g + at);
+        if (out) relu_mask4(d, ld4(out + at));
+        if (dres) st4(dres + at, d);
         float4 z = d;
-        if (scale) { z.x = d.x * sc.x; z.y = d.y * sc.y; z.z = d.z * sc.z; z.w = d.w * sc.w; }
-        if (gz) *reinterpret_cast<float4 *>(gz + at) = z;
-        sum.x += z.x; sum.y += z.y; sum.z += z.z; sum.w += z.w;
+        if (scale) scale4(z, sc);
+        if (gz) st4(gz + at, z);
+        sum = add4(sum, z);
     }
     if (part == nullptr) return;
-    *reinterpret_cast<float4 *>(&s_sum[slot][c4 * 4]) = sum;
+    st4(&s_sum[slot][c4 * 4], sum);
     __syncthreads();
-    if (tid < 64) {
-        float v = s_sum[0][tid];
-#pragma unroll
-        for (int s = 1; s < 16; ++s) v += s_sum[s][tid];
-        part[(size_t)blockIdx.x * Cout + blockIdx.y * 64 + tid] = v;
-    }
+    if (tid < 64) part[(size_t)blockIdx.x * Cout + blockIdx.y * 64 + tid] = slots16(s_sum, tid);
 }
 
 // dst (C) = the column sums of part (T, C): 16 row slots stride over the tiles, then the slots in ascending order.  grid C / 64
@@ -86,18 +74,10 @@ __global__ __launch_bounds__(256) void k_sparse_colsum(const float *__restrict__
     const int tid = threadIdx.x, c4 = tid & 15, slot = tid >> 4;
     const int col = blockIdx.x * 64 + c4 * 4;
     float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = slot; t < T; t += 16) {
-        const float4 v = *reinterpret_cast<const float4 *>(part + (size_t)t * C + col);
-        sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
-    }
-    *reinterpret_cast<float4 *>(&s_sum[slot][c4 * 4]) = sum;
+    for (int t = slot; t < T; t += 16) acc4(sum, ld4(part + (size_t)t * C + col));
+    st4(&s_sum[slot][c4 * 4], sum);
     __syncthreads();
-    if (tid < 64) {
-        float v = s_sum[0][tid];
-#pragma unroll
-        for (int s = 1; s < 16; ++s) v += s_sum[s][tid];
-        dst[blockIdx.x * 64 + tid] = v;
-    }
+    if (tid < 64) dst[blockIdx.x * 64 + tid] = slots16(s_sum, tid);
 }
 
 // ---- dweight ----------------------------------------------------------------------------------------------------------------
@@ -119,8 +99,7 @@ __global__ __launch_bounds__(256) void k_sparse_dweight(SpDwArgs a)
     const int tile = blockIdx.y;
     const int cout0 = (tile % nct) << 6, cin0 = ((tile / nct) % mct) << 6, j = tile / (nct * mct);
     const int r0 = blockIdx.x * a.R, r1 = min(r0 + a.R, a.n_out);
-    // staging: thread (pair = wk + 16 i, channels wn .. wn + 3) of both operands, written transposed as four dwords (k_sparse_conv's
-    // weight staging: the 32 lanes of a write group hold 16 pairs x 2 channel quads, banks wk + 16 (quad & 1): conflict-free)
+    // staging: thread (pair = wk + 16 i, channels wn .. wn + 3) of both operands, written transposed (stash_t4)
     const int wk = lane & 15, wn = (wid * 4 + (lane >> 4)) * 4;
     float4 av[4], wv[4];
     float tot[16];
@@ -160,23 +139,16 @@ __global__ __launch_bounds__(256) void k_sparse_dweight(SpDwArgs a)
                 av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 wv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (p < cnt) {
-                    av[i] = *reinterpret_cast<const float4 *>(a.feats + (size_t)s_i[p] * a.Cin + cin0 + wn);
-                    wv[i] = *reinterpret_cast<const float4 *>(a.gz + (size_t)s_o[p] * a.Cout + cout0 + wn);
+                    av[i] = ld4(a.feats + (size_t)s_i[p] * a.Cin + cin0 + wn);
+                    wv[i] = ld4(a.gz + (size_t)s_o[p] * a.Cout + cout0 + wn);
                 }
             }
         };
         auto stash = [&]() {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int k = wk + 16 * i;
-                As[k >> 5][wn + 0][k & 31] = av[i].x;
-                As[k >> 5][wn + 1][k & 31] = av[i].y;
-                As[k >> 5][wn + 2][k & 31] = av[i].z;
-                As[k >> 5][wn + 3][k & 31] = av[i].w;
-                Ws[k >> 5][wn + 0][k & 31] = wv[i].x;
-                Ws[k >> 5][wn + 1][k & 31] = wv[i].y;
-                Ws[k >> 5][wn + 2][k & 31] = wv[i].z;
-                Ws[k >> 5][wn + 3][k & 31] = wv[i].w;
+                stash_t4(As, wk + 16 * i, wn, av[i]);
+                stash_t4(Ws, wk + 16 * i, wn, wv[i]);
             }
         };
 
@@ -185,13 +157,7 @@ __global__ __launch_bounds__(256) void k_sparse_dweight(SpDwArgs a)
             stash();
             __syncthreads();
             if (s + 1 < nsteps) fetch(s + 1);               // in flight behind this step's matrix instructions
-            f32x16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-            PTX_G64_COMPUTE(0);
-            if (cnt - s * 64 > 32) PTX_G64_COMPUTE(1);      // work-group uniform
-#pragma unroll
-            for (int i = 0; i < 16; ++i) tot[i] += acc[i];
+            PTX_SPARSE_STEP(tot, cnt - s * 64 > 32);
             __syncthreads();
         }
     }
@@ -254,12 +220,9 @@ __global__ __launch_bounds__(256) void k_sparse_slab_sum(const float *__restrict
 {
     const size_t e = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (e >= L) return;
-    float4 v = *reinterpret_cast<const float4 *>(ws + e);
-    for (int s = 1; s < S; ++s) {
-        const float4 w = *reinterpret_cast<const float4 *>(ws + (size_t)s * L + e);
-        v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
-    }
-    *reinterpret_cast<float4 *>(dst + e) = v;
+    float4 v = ld4(ws + e);
+    for (int s = 1; s < S; ++s) acc4(v, ld4(ws + (size_t)s * L + e));
+    st4(dst + e, v);
 }
 
 // the stem's dfeats (n_in, 3): one wave per input row; the row's kvol transposed neighbours are loaded by the lanes, the present ones
@@ -294,31 +257,6 @@ __global__ __launch_bounds__(256) void k_sparse_dfeats_stem(const float *__restr
 }
 
 // ---- max-pool ---------------------------------------------------------------------------------------------------------------
-// k_sparse_max_pool of sparse.hip plus the offset that supplied the maximum: the first present neighbour, replaced only by a
-// strictly larger value -- ties go to the smallest j; 255 for a row without neighbours
-__global__ __launch_bounds__(256) void k_sparse_max_pool_arg(const float *__restrict__ feats, const int32_t *__restrict__ nbr, int n_out,
-                                                             int kvol, int C, float *__restrict__ out, uint8_t *__restrict__ arg)
-{
-    const int c4n = C >> 2;
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const int o = (int)(t / c4n), c4 = (int)(t - (long)o * c4n);
-    if (o >= n_out) return;
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    uchar4 w = make_uchar4(255, 255, 255, 255);
-    for (int j = 0; j < kvol; ++j) {
-        const int idx = nbr[(size_t)o * kvol + j];
-        if (idx < 0) continue;
-        const float4 x = *reinterpret_cast<const float4 *>(feats + (size_t)idx * C + c4 * 4);
-        if (x.x > m.x || w.x == 255) w.x = (unsigned char)j;
-        if (x.y > m.y || w.y == 255) w.y = (unsigned char)j;
-        if (x.z > m.z || w.z == 255) w.z = (unsigned char)j;
-        if (x.w > m.w || w.w == 255) w.w = (unsigned char)j;
-        m.x = fmaxf(m.x, x.x); m.y = fmaxf(m.y, x.y); m.z = fmaxf(m.z, x.z); m.w = fmaxf(m.w, x.w);
-    }
-    *reinterpret_cast<float4 *>(out + (size_t)o * C + c4 * 4) = m;
-    *reinterpret_cast<uchar4 *>(arg + (size_t)o * C + c4 * 4) = w;
-}
-
 // one thread per (input row, 4 channels): dfeats[i, c] = sum over ascending j of [arg[nbr_t[i, j], c] == j] * g[nbr_t[i, j], c]
 __global__ __launch_bounds__(256) void k_sparse_max_pool_bwd(const float *__restrict__ g, const uint8_t *__restrict__ arg,
                                                              const int32_t *__restrict__ nbr_t, int n_in, int n_out, int kvol, int C,
@@ -333,13 +271,13 @@ __global__ __launch_bounds__(256) void k_sparse_max_pool_bwd(const float *__rest
         const int o = nbr_t[(size_t)i * kvol + j];
         if (o < 0 || o >= n_out) continue;
         const uchar4 w = *reinterpret_cast<const uchar4 *>(arg + (size_t)o * C + c4 * 4);
-        const float4 x = *reinterpret_cast<const float4 *>(g + (size_t)o * C + c4 * 4);
+        const float4 x = *reinterpret_cast<const float4 *>(g + (size_t)o * C + c4 * 4);       // (through ld4 the loop is laid out differently)
         if (w.x == j) d.x += x.x;
         if (w.y == j) d.y += x.y;
         if (w.z == j) d.z += x.z;
         if (w.w == j) d.w += x.w;
     }
-    *reinterpret_cast<float4 *>(dfeats + (size_t)i * C + c4 * 4) = d;
+    st4(dfeats + (size_t)i * C + c4 * 4, d);
 }
 
 // ---- the split of dweight over the rows: a function of the shapes only ------------------------------------------------------
@@ -347,8 +285,7 @@ struct DwPlan { int R, S; size_t slab, dw_bytes, part_bytes, total; };
 static bool bwd_widths_ok(int kvol, int Cin, int Cout)
 {
     const bool stem = Cin == 3 && kvol == 27;
-    return (kvol == 1 || kvol == 8 || kvol == 27) && Cout >= 64 && Cout <= 512 && Cout % 64 == 0 &&
-           (stem || (Cin >= 64 && Cin <= 512 && Cin % 64 == 0));
+    return (kvol == 1 || kvol == 8 || kvol == 27) && sp_width_ok(Cout) && (stem || sp_width_ok(Cin));
 }
 static DwPlan dw_plan(int n_out, int kvol, int Cin, int Cout)
 {
@@ -368,7 +305,7 @@ static DwPlan dw_plan(int n_out, int kvol, int Cin, int Cout)
     P.R = (int)(R < least ? least : R);
     P.S = cdiv(n_out, P.R);
     P.dw_bytes = P.S > 1 ? align_up((size_t)P.S * P.slab * sizeof(float), 256) : 0;
-    P.part_bytes = align_up((size_t)cdiv(n_out > 0 ? n_out : 1, kEpiRows) * Cout * sizeof(float), 256);
+    P.part_bytes = align_up((size_t)cdiv(n_out > 0 ? n_out : 1, kSpTile) * Cout * sizeof(float), 256);
     P.total = P.dw_bytes + P.part_bytes + 256;
     return P;
 }
@@ -416,16 +353,13 @@ int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, 
     PTX_REQUIRE(!(epi && need_z) || gz || n_out == 0, "ptx_sparse_conv3d_bwd: gz is needed with relu / scale when dfeats or dweight is asked for");
     PTX_REQUIRE(!dfeats || ((nbr_t && weight) || n_out == 0 || n_in == 0), "ptx_sparse_conv3d_bwd: dfeats needs nbr_t and weight");
     PTX_REQUIRE(!dweight || ((nbr && feats) || n_out == 0 || n_in == 0), "ptx_sparse_conv3d_bwd: dweight needs nbr and feats");
-    PTX_REQUIRE(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(scale) |
-                  reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(weight) | reinterpret_cast<uintptr_t>(gz) |
-                  reinterpret_cast<uintptr_t>(dresidual) | reinterpret_cast<uintptr_t>(dfeats) | reinterpret_cast<uintptr_t>(dweight) |
-                  reinterpret_cast<uintptr_t>(workspace)) & 15) == 0,
+    PTX_REQUIRE(sp_aligned16({g, out, scale, feats, weight, gz, dresidual, dfeats, dweight, workspace}),
                 "ptx_sparse_conv3d_bwd: every float buffer and the workspace must be 16-byte aligned");
     const DwPlan P = dw_plan(n_out, kvol, Cin, Cout);
     const bool use_ws = dbias != nullptr || (dweight != nullptr && P.S > 1);
     if (use_ws && n_out > 0) {
         PTX_REQUIRE(workspace, "ptx_sparse_conv3d_bwd: workspace is null");
-        if (ws_bytes < P.total) { set_error("ptx_sparse_conv3d_bwd: workspace too small: %zu < %zu bytes", ws_bytes, P.total); return PTX_ENOSPACE; }
+        PTX_TRY(sp_workspace_fits("ptx_sparse_conv3d_bwd", ws_bytes, P.total));
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_out == 0 || n_in == 0) {                          // no pair anywhere
@@ -438,7 +372,7 @@ int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, 
     }
     char *ws = static_cast<char *>(workspace);
     float *part = dbias ? reinterpret_cast<float *>(ws + P.dw_bytes) : nullptr;
-    const int T = cdiv(n_out, kEpiRows);
+    const int T = cdiv(n_out, kSpTile);
     if ((epi && gz) || dbias || dresidual) {
         hipLaunchKernelGGL(k_sparse_epi_bwd, dim3(T, Cout / 64), dim3(256), 0, st, g, relu ? out : nullptr, scale, epi ? gz : nullptr, dresidual,
                            part, n_out, Cout);
@@ -476,22 +410,6 @@ int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, 
     return PTX_OK;
 }
 
-int ptx_sparse_max_pool3d_arg(const float *feats, const int32_t *nbr, int n_out, int kvol, int C, float *out, uint8_t *arg, void *stream)
-{
-    PTX_REQUIRE(n_out >= 0 && kvol >= 1 && kvol <= kSpMaxVol && C >= 4 && C % 4 == 0, "ptx_sparse_max_pool3d_arg: n_out=%d kvol=%d C=%d (C: a multiple of 4)",
-                n_out, kvol, C);
-    if (n_out == 0) return PTX_OK;
-    PTX_REQUIRE(feats && nbr && out && arg, "ptx_sparse_max_pool3d_arg: null argument");
-    PTX_REQUIRE(((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (reinterpret_cast<uintptr_t>(arg) & 3) == 0,
-                "ptx_sparse_max_pool3d_arg: feats and out must be 16-byte aligned, arg 4-byte aligned");
-    const long threads = (long)n_out * (C / 4);
-    PTX_REQUIRE(threads < (1l << 31) * 256, "ptx_sparse_max_pool3d_arg: %d rows x %d channels is out of range", n_out, C);
-    hipLaunchKernelGGL(k_sparse_max_pool_arg, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), feats, nbr,
-                       n_out, kvol, C, out, arg);
-    PTX_LAUNCHED("k_sparse_max_pool_arg");
-    return PTX_OK;
-}
-
 int ptx_sparse_max_pool3d_bwd(const float *g, const uint8_t *arg, const int32_t *nbr_t, int n_in, int n_out, int kvol, int C, float *dfeats,
                               void *stream)
 {
@@ -499,10 +417,10 @@ int ptx_sparse_max_pool3d_bwd(const float *g, const uint8_t *arg, const int32_t 
                 "ptx_sparse_max_pool3d_bwd: n_in=%d n_out=%d kvol=%d C=%d (C: a multiple of 4)", n_in, n_out, kvol, C);
     if (n_in == 0) return PTX_OK;
     PTX_REQUIRE(nbr_t && dfeats && ((g && arg) || n_out == 0), "ptx_sparse_max_pool3d_bwd: null argument");
-    PTX_REQUIRE(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dfeats)) & 15) == 0 && (reinterpret_cast<uintptr_t>(arg) & 3) == 0,
+    PTX_REQUIRE(sp_aligned16({g, dfeats}) && (reinterpret_cast<uintptr_t>(arg) & 3) == 0,
                 "ptx_sparse_max_pool3d_bwd: g and dfeats must be 16-byte aligned, arg 4-byte aligned");
+    PTX_TRY(sp_rows_fit("ptx_sparse_max_pool3d_bwd", n_in, C));
     const long threads = (long)n_in * (C / 4);
-    PTX_REQUIRE(threads < (1l << 31) * 256, "ptx_sparse_max_pool3d_bwd: %d rows x %d channels is out of range", n_in, C);
     hipLaunchKernelGGL(k_sparse_max_pool_bwd, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), g, arg,
                        nbr_t, n_in, n_out, kvol, C, dfeats);
     PTX_LAUNCHED("k_sparse_max_pool_bwd");

@@ -4,8 +4,7 @@
 //
 // Rows x (n, C) fp32, C a multiple of 64 up to 512; segments as a host array of ends (ptx_sparse_kernel_map's in_scene_end).  The rows
 // are cut into tiles of 256 that never straddle a segment; the host passes the tile prefix of every segment in the kernel arguments and
-// a work-group finds its segment from them.  Thread = (row slot = tid >> 4, 4 channels = tid & 15), 16-byte accesses -- the idiom of
-// k_sparse_epi_bwd / k_sparse_colsum (sparse_bwd.hip).
+// a work-group finds its segment from them.  The streaming idiom and its helpers: sparse.h.
 //
 //   forward   k_sparse_norm_stats     per tile and column (mean, M2 about the tile's own mean): the tile's 16 rows per thread stay in
 //                                     registers between the two sums; row slots added in ascending order;
@@ -21,13 +20,10 @@
 //
 // No float atomics, a fixed order everywhere: two calls on the same inputs give the same bits.  The variance is never E[x^2] - E[x]^2.
 // Everything runs on the caller's stream; no host wait.
-#include <initializer_list>
-
-#include "common.h"
+#include "sparse.h"
 
 namespace ptx {
 
-constexpr int kSnRows = 256;               // rows per tile
 constexpr int kSnMaxSeg = 64;
 
 struct SnSegs {
@@ -46,21 +42,9 @@ __device__ __forceinline__ SnTile sn_locate(const SnSegs &sg, int tile)
     const int start = s ? sg.end[s - 1] : 0;
     SnTile t;
     t.seg = s;
-    t.row0 = start + (tile - sg.tile0[s]) * kSnRows;
-    t.cnt = min(kSnRows, sg.end[s] - t.row0);
+    t.row0 = start + (tile - sg.tile0[s]) * kSpTile;
+    t.cnt = min(kSpTile, sg.end[s] - t.row0);
     return t;
-}
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-
-// the 16 row slots of s_red[.][tid] in ascending order (tid < 64)
-__device__ __forceinline__ float sn_slots(const float (*s_red)[64], int tid)
-{
-    float v = s_red[0][tid];
-#pragma unroll
-    for (int s = 1; s < 16; ++s) v += s_red[s][tid];
-    return v;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------
@@ -72,26 +56,26 @@ __global__ __launch_bounds__(256) void k_sparse_norm_stats(const float *__restri
     const int tid = threadIdx.x, c4 = tid & 15, slot = tid >> 4;
     const int col = blockIdx.y * 64 + c4 * 4;
     const SnTile t = sn_locate(sg, blockIdx.x);
-    float4 v[kSnRows / 16];
+    float4 v[kSpTile / 16];
     float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int i = 0; i < kSnRows / 16; ++i) {
+    for (int i = 0; i < kSpTile / 16; ++i) {
         const int r = slot + 16 * i;
         v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (r < t.cnt) v[i] = ld4(x + (size_t)(t.row0 + r) * C + col);
-        sum.x += v[i].x; sum.y += v[i].y; sum.z += v[i].z; sum.w += v[i].w;
+        acc4(sum, v[i]);
     }
     st4(&s_red[slot][c4 * 4], sum);
     __syncthreads();
-    if (tid < 64) s_mean[tid] = sn_slots(s_red, tid) / (float)t.cnt;
+    if (tid < 64) s_mean[tid] = slots16(s_red, tid) / (float)t.cnt;
     __syncthreads();
     const float4 m = ld4(&s_mean[c4 * 4]);
     float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-    for (int i = 0; i < kSnRows / 16; ++i) {
+    for (int i = 0; i < kSpTile / 16; ++i) {
         if (slot + 16 * i < t.cnt) {
-            const float dx = v[i].x - m.x, dy = v[i].y - m.y, dz = v[i].z - m.z, dw = v[i].w - m.w;
-            q.x += dx * dx; q.y += dy * dy; q.z += dz * dz; q.w += dw * dw;
+            const float4 d = sub4(v[i], m);
+            mac4(q, d, d);
         }
     }
     st4(&s_red[slot][c4 * 4], q);                           // (every read of the first sums lies before the second barrier)
@@ -99,7 +83,7 @@ __global__ __launch_bounds__(256) void k_sparse_norm_stats(const float *__restri
     if (tid < 64) {
         float *dst = part + (size_t)blockIdx.x * 2 * C + blockIdx.y * 64 + tid;
         dst[0] = s_mean[tid];
-        dst[C] = sn_slots(s_red, tid);
+        dst[C] = slots16(s_red, tid);
     }
 }
 
@@ -132,7 +116,7 @@ __global__ __launch_bounds__(256) void k_sparse_norm_finalise(const float *__res
     int cn = 0;
     float4 mean = make_float4(0.f, 0.f, 0.f, 0.f), m2 = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t = ta; t < tb; ++t) {
-        const int nb = min(kSnRows, n - t * kSnRows);
+        const int nb = min(kSpTile, n - t * kSpTile);
         const float *src = part + (size_t)(t0 + t) * 2 * C + col;
         const float4 pm = ld4(src), pq = ld4(src + C);
         int k;
@@ -177,19 +161,15 @@ __global__ __launch_bounds__(256) void k_sparse_norm_apply(const float *__restri
     if (weight) w = ld4(weight + col);
     if (bias) b = ld4(bias + col);
 #pragma unroll 4
-    for (int i = 0; i < kSnRows / 16; ++i) {
+    for (int i = 0; i < kSpTile / 16; ++i) {
         const int r = slot + 16 * i;
         if (r >= t.cnt) break;
         const size_t at = (size_t)(t.row0 + r) * C + col;
         const float4 v = ld4(x + at);
-        float4 y;
-        y.x = (v.x - mu.x) * rs.x; y.y = (v.y - mu.y) * rs.y; y.z = (v.z - mu.z) * rs.z; y.w = (v.w - mu.w) * rs.w;
-        if (weight) { y.x *= w.x; y.y *= w.y; y.z *= w.z; y.w *= w.w; }
-        if (bias) { y.x += b.x; y.y += b.y; y.z += b.z; y.w += b.w; }
-        if (residual) {
-            const float4 e = ld4(residual + at);
-            y.x += e.x; y.y += e.y; y.z += e.z; y.w += e.w;
-        }
+        float4 y = mul4(sub4(v, mu), rs);
+        if (weight) scale4(y, w);
+        if (bias) acc4(y, b);
+        if (residual) acc4(y, ld4(residual + at));
         if (relu) { y.x = fmaxf(y.x, 0.0f); y.y = fmaxf(y.y, 0.0f); y.z = fmaxf(y.z, 0.0f); y.w = fmaxf(y.w, 0.0f); }
         st4(out + at, y);
     }
@@ -211,28 +191,24 @@ __global__ __launch_bounds__(256) void k_sparse_norm_bwd_sums(const float *__res
     const float4 mu = ld4(stats + (size_t)t.seg * 2 * C + col), rs = ld4(stats + (size_t)t.seg * 2 * C + C + col);
     float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 4
-    for (int i = 0; i < kSnRows / 16; ++i) {
+    for (int i = 0; i < kSpTile / 16; ++i) {
         const int r = slot + 16 * i;
         if (r >= t.cnt) break;
         const size_t at = (size_t)(t.row0 + r) * C + col;
         float4 d = ld4(g + at);
-        if (out) {
-            const float4 o = ld4(out + at);
-            d.x = o.x > 0.0f ? d.x : 0.0f; d.y = o.y > 0.0f ? d.y : 0.0f; d.z = o.z > 0.0f ? d.z : 0.0f; d.w = o.w > 0.0f ? d.w : 0.0f;
-        }
+        if (out) relu_mask4(d, ld4(out + at));
         if (dres) st4(dres + at, d);
         const float4 v = ld4(x + at);
-        sa.x += d.x; sa.y += d.y; sa.z += d.z; sa.w += d.w;
-        sb.x += d.x * ((v.x - mu.x) * rs.x); sb.y += d.y * ((v.y - mu.y) * rs.y);
-        sb.z += d.z * ((v.z - mu.z) * rs.z); sb.w += d.w * ((v.w - mu.w) * rs.w);
+        sa = add4(sa, d);
+        mac4(sb, d, mul4(sub4(v, mu), rs));
     }
     st4(&s_a[slot][c4 * 4], sa);
     st4(&s_b[slot][c4 * 4], sb);
     __syncthreads();
     if (tid < 64) {
         float *dst = part + (size_t)blockIdx.x * 2 * C + blockIdx.y * 64 + tid;
-        dst[0] = sn_slots(s_a, tid);
-        dst[C] = sn_slots(s_b, tid);
+        dst[0] = slots16(s_a, tid);
+        dst[C] = slots16(s_b, tid);
     }
 }
 
@@ -256,14 +232,14 @@ __global__ __launch_bounds__(256) void k_sparse_norm_bwd_finalise(const float *_
     for (int t = ta; t < tb; ++t) {
         const float *src = part + (size_t)(t0 + t) * 2 * C + col;
         const float4 pa = ld4(src), pb = ld4(src + C);
-        sa.x += pa.x; sa.y += pa.y; sa.z += pa.z; sa.w += pa.w;
-        sb.x += pb.x; sb.y += pb.y; sb.z += pb.z; sb.w += pb.w;
+        acc4(sa, pa);
+        acc4(sb, pb);
     }
     st4(&s_a[slot][c4 * 4], sa);
     st4(&s_b[slot][c4 * 4], sb);
     __syncthreads();
     if (tid < 64) {
-        const float a = sn_slots(s_a, tid), b = sn_slots(s_b, tid);
+        const float a = slots16(s_a, tid), b = slots16(s_b, tid);
         const int c = blockIdx.y * 64 + tid;
         const size_t at = (size_t)s * 2 * C + c;
         seg[at] = n > 0 ? a / (float)n : 0.0f;
@@ -304,12 +280,9 @@ __global__ __launch_bounds__(256) void k_sparse_norm_bwd_apply(const float *__re
     const size_t so = (size_t)t.seg * 2 * C + col;
     const float4 mu = ld4(stats + so), rs = ld4(stats + so + C), a = ld4(seg + so), b = ld4(seg + so + C);
     float4 k = rs;                                          // weight * rstd
-    if (weight) {
-        const float4 w = ld4(weight + col);
-        k.x = w.x * rs.x; k.y = w.y * rs.y; k.z = w.z * rs.z; k.w = w.w * rs.w;
-    }
+    if (weight) k = mul4(ld4(weight + col), rs);
 #pragma unroll 4
-    for (int i = 0; i < kSnRows / 16; ++i) {
+    for (int i = 0; i < kSpTile / 16; ++i) {
         const int r = slot + 16 * i;
         if (r >= t.cnt) break;
         const size_t at = (size_t)(t.row0 + r) * C + col;
@@ -318,30 +291,20 @@ __global__ __launch_bounds__(256) void k_sparse_norm_bwd_apply(const float *__re
             d = ld4(gy + at);
         } else {
             d = ld4(g + at);
-            if (out) {
-                const float4 o = ld4(out + at);
-                d.x = o.x > 0.0f ? d.x : 0.0f; d.y = o.y > 0.0f ? d.y : 0.0f; d.z = o.z > 0.0f ? d.z : 0.0f; d.w = o.w > 0.0f ? d.w : 0.0f;
-            }
+            if (out) relu_mask4(d, ld4(out + at));
         }
         const float4 v = ld4(x + at);
-        float4 y;
-        y.x = k.x * ((d.x - a.x) - ((v.x - mu.x) * rs.x) * b.x);
-        y.y = k.y * ((d.y - a.y) - ((v.y - mu.y) * rs.y) * b.y);
-        y.z = k.z * ((d.z - a.z) - ((v.z - mu.z) * rs.z) * b.z);
-        y.w = k.w * ((d.w - a.w) - ((v.w - mu.w) * rs.w) * b.w);
-        st4(dx + at, y);
+        st4(dx + at, mul4(k, sub4(sub4(d, a), mul4(mul4(sub4(v, mu), rs), b))));
     }
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------
-static bool sn_width_ok(int C) { return C >= 64 && C <= 512 && C % 64 == 0; }
-
 struct SnPlan { size_t part_bytes, seg_bytes, total; };
 // a function of the shapes only: at most n / 256 + S tiles
 static SnPlan sn_plan(int n, int S, int C)
 {
     SnPlan P{};
-    P.part_bytes = align_up(((size_t)n / kSnRows + (size_t)S) * 2 * C * sizeof(float), 256);
+    P.part_bytes = align_up(((size_t)n / kSpTile + (size_t)S) * 2 * C * sizeof(float), 256);
     P.seg_bytes = align_up((size_t)S * 2 * C * sizeof(float), 256);
     P.total = P.part_bytes + 2 * P.seg_bytes + 256;         // the tile partials, the segments' means, the segments' sums
     return P;
@@ -350,7 +313,7 @@ static SnPlan sn_plan(int n, int S, int C)
 // the segment table of a call; PTX_EINVAL with a message when the ends are not a partition of the n rows
 static int sn_segments(const char *who, const int32_t *seg_end, int S, int n, int C, SnSegs &sg)
 {
-    PTX_REQUIRE(n >= 0 && S >= 1 && S <= kSnMaxSeg && sn_width_ok(C), "%s: n=%d S=%d C=%d (S: 1 to 64 segments; C: a multiple of 64 up to 512)",
+    PTX_REQUIRE(n >= 0 && S >= 1 && S <= kSnMaxSeg && sp_width_ok(C), "%s: n=%d S=%d C=%d (S: 1 to 64 segments; C: a multiple of 64 up to 512)",
                 who, n, S, C);
     PTX_REQUIRE(seg_end != nullptr, "%s: seg_end is null", who);
     sg.S = S;
@@ -360,19 +323,12 @@ static int sn_segments(const char *who, const int32_t *seg_end, int S, int n, in
         PTX_REQUIRE(seg_end[s] >= prev && seg_end[s] <= n, "%s: seg_end[%d] = %d after %d with n = %d (ends must ascend up to n)", who, s,
                     seg_end[s], prev, n);
         sg.end[s] = seg_end[s];
-        sg.tile0[s + 1] = sg.tile0[s] + cdiv(seg_end[s] - prev, kSnRows);
+        sg.tile0[s + 1] = sg.tile0[s] + cdiv(seg_end[s] - prev, kSpTile);
         prev = seg_end[s];
     }
     PTX_REQUIRE(prev == n, "%s: seg_end[%d] = %d, but there are n = %d rows", who, S - 1, prev, n);
     for (int s = S; s < kSnMaxSeg; ++s) sg.end[s] = n, sg.tile0[s + 1] = sg.tile0[S];
     return PTX_OK;
-}
-
-static bool sn_aligned(std::initializer_list<const void *> ptrs)
-{
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
-    return (bits & 15) == 0;
 }
 
 }  // namespace ptx
@@ -383,7 +339,7 @@ extern "C" {
 
 size_t ptx_sparse_norm_workspace_bytes(int n, int S, int C)
 {
-    if (n < 0 || S < 1 || S > kSnMaxSeg || !sn_width_ok(C)) return 0;
+    if (n < 0 || S < 1 || S > kSnMaxSeg || !sp_width_ok(C)) return 0;
     return sn_plan(n, S, C).total;
 }
 
@@ -400,13 +356,13 @@ int ptx_sparse_norm_fwd(const float *x, const int32_t *seg_end, int S, int n, in
         PTX_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "ptx_sparse_norm_fwd: momentum = %g is outside [0, 1]", (double)momentum);
     }
     PTX_REQUIRE(stats != nullptr && ((x && out) || n == 0), "ptx_sparse_norm_fwd: null argument (x, out and stats are needed)");
-    PTX_REQUIRE(sn_aligned({x, weight, bias, residual, stats, out, workspace}),
+    PTX_REQUIRE(sp_aligned16({x, weight, bias, residual, stats, out, workspace}),
                 "ptx_sparse_norm_fwd: every float buffer and the workspace must be 16-byte aligned");
     const SnPlan P = sn_plan(n, S, C);
     const int T = sg.tile0[S];
     if (T > 0) {
         PTX_REQUIRE(workspace, "ptx_sparse_norm_fwd: workspace is null");
-        if (ws_bytes < P.total) { set_error("ptx_sparse_norm_fwd: workspace too small: %zu < %zu bytes", ws_bytes, P.total); return PTX_ENOSPACE; }
+        PTX_TRY(sp_workspace_fits("ptx_sparse_norm_fwd", ws_bytes, P.total));
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *part = static_cast<float *>(workspace);
@@ -429,7 +385,7 @@ int ptx_sparse_norm_apply(const float *x, const int32_t *seg_end, int S, int n, 
     SnSegs sg;
     PTX_TRY(sn_segments("ptx_sparse_norm_apply", seg_end, S, n, C, sg));
     PTX_REQUIRE(stats != nullptr && ((x && out) || n == 0), "ptx_sparse_norm_apply: null argument (x, stats and out are needed)");
-    PTX_REQUIRE(sn_aligned({x, weight, bias, residual, stats, out}), "ptx_sparse_norm_apply: every float buffer must be 16-byte aligned");
+    PTX_REQUIRE(sp_aligned16({x, weight, bias, residual, stats, out}), "ptx_sparse_norm_apply: every float buffer must be 16-byte aligned");
     const int T = sg.tile0[S];
     if (T == 0) return PTX_OK;
     hipLaunchKernelGGL(k_sparse_norm_apply, dim3(T, C / 64), dim3(256), 0, static_cast<hipStream_t>(stream), x, sg, C, stats, weight, bias,
@@ -445,11 +401,11 @@ int ptx_sparse_norm_bwd(const float *g, const float *x, const float *out, const 
     SnSegs sg;
     PTX_TRY(sn_segments("ptx_sparse_norm_bwd", seg_end, S, n, C, sg));
     PTX_REQUIRE(stats != nullptr && ((g && x) || n == 0), "ptx_sparse_norm_bwd: null argument (g, x and stats are needed)");
-    PTX_REQUIRE(sn_aligned({g, x, out, stats, weight, dx, dweight, dbias, dresidual, workspace}),
+    PTX_REQUIRE(sp_aligned16({g, x, out, stats, weight, dx, dweight, dbias, dresidual, workspace}),
                 "ptx_sparse_norm_bwd: every float buffer and the workspace must be 16-byte aligned");
     const SnPlan P = sn_plan(n, S, C);
     PTX_REQUIRE(workspace, "ptx_sparse_norm_bwd: workspace is null");
-    if (ws_bytes < P.total) { set_error("ptx_sparse_norm_bwd: workspace too small: %zu < %zu bytes", ws_bytes, P.total); return PTX_ENOSPACE; }
+    PTX_TRY(sp_workspace_fits("ptx_sparse_norm_bwd", ws_bytes, P.total));
     const int T = sg.tile0[S];
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *part = static_cast<float *>(workspace);

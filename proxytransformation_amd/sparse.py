@@ -6,8 +6,8 @@ ResNet (backbones/mink_resnet.py), and MinkowskiEngine has no ROCm build.  What 
 consume it (``sparse_conv3d`` with a bias / folded-BatchNorm / residual / ReLU epilogue, ``sparse_max_pool3d``), which is enough to
 express every ``MinkowskiConvolution`` and the stem's ``MinkowskiMaxPooling`` of an eval-mode MinkResNet-34.
 
-Semantics (pinned by the numpy restatements ``kernel_map_host`` / ``sparse_conv3d_host`` / ``sparse_max_pool3d_host`` below, which the
-kernels are held to bit for bit / to fp32 rounding; they play the role ``ingest.device_choices`` plays for the draws):
+Semantics (pinned by the numpy restatements ``kernel_map_host`` / ``sparse_conv3d_host`` / ``sparse_max_pool3d_host`` of
+``sparse_host.py``, re-exported here, which the kernels are held to bit for bit / to fp32 rounding; they play the role ``ingest.device_choices`` plays for the draws):
 
 * rows ``coords (n,4) int32 = (scene, x, y, z)`` grouped by scene, ``scene_rows[b]`` = end of scene b's rows (what
   ``quantize(..., return_scene_rows=True)`` and ``pipeline.level_coordinates`` return), every coordinate a multiple of the power-of-two
@@ -47,11 +47,13 @@ import ctypes
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
-import numpy as np
 import torch
 from torch import nn
 
 from . import _abi
+from .sparse_host import (_check_geometry, _segments, kernel_map_host, kernel_map_transpose_host, kernel_offsets,     # noqa: F401
+                          sparse_conv3d_bwd_host, sparse_conv3d_host, sparse_max_pool3d_bwd_host, sparse_max_pool3d_host,
+                          sparse_norm_bwd_host, sparse_norm_host)
 
 __all__ = ["INSTANCE_NORM_EPS", "KernelMap", "SparseBatchNorm", "SparseConv3d", "SparseInstanceNorm", "bn_fold", "kernel_map",
            "kernel_map_host", "kernel_map_transpose_host", "kernel_offsets", "sparse_batch_norm", "sparse_conv3d", "sparse_conv3d_bwd_host",
@@ -61,224 +63,6 @@ __all__ = ["INSTANCE_NORM_EPS", "KernelMap", "SparseBatchNorm", "SparseConv3d", 
 # MinkowskiInstanceNorm's epsilon, inside the square root: 1 / (var_biased + 1e-8).sqrt() per scene.  The ONE place that fixes it (our
 # reading of MinkowskiInstanceNormFunction; parity unpinned against ME itself)
 INSTANCE_NORM_EPS = 1e-8
-
-
-# ---------------------------------------------------------------------------------------------------------------- host restatement
-def kernel_offsets(kernel_size: int, tensor_stride: int) -> np.ndarray:
-    """The ``k^3`` offsets ``(dx, dy, dz)`` of a kernel in the order of the weight tensor's rows: x fastest, then y, then z; odd k
-    centred, even k from 0 upwards.  The ONE place that fixes this order (our reading of MinkowskiEngine's region iterator; parity
-    unpinned against ME itself)."""
-    k = int(kernel_size)
-    lo = -(k // 2) if k % 2 else 0
-    r = np.arange(lo, lo + k, dtype=np.int64) * int(tensor_stride)
-    z, y, x = np.meshgrid(r, r, r, indexing="ij")
-    return np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1)
-
-
-def _check_geometry(tensor_stride: int, kernel_size: int, stride: int) -> None:
-    ts = int(tensor_stride)
-    if ts < 1 or ts & (ts - 1) or ts > (1 << 15):
-        raise ValueError(f"tensor_stride must be a power of two up to 2^15, got {tensor_stride}")
-    if int(kernel_size) not in (1, 2, 3) or int(stride) not in (1, 2):
-        raise ValueError(f"kernel_size must be 1, 2 or 3 and stride 1 or 2, got {kernel_size}, {stride}")
-
-
-def kernel_map_host(coords, scene_rows: Sequence[int], tensor_stride: int, kernel_size: int, stride: int):
-    """numpy restatement of ``kernel_map``: ``(coords_out (n_out,4) int32, out_scene_rows, nbr (n_out,k^3) int32)``."""
-    _check_geometry(tensor_stride, kernel_size, stride)
-    c = np.asarray(coords).astype(np.int64).reshape(-1, 4)
-    ts, k = int(tensor_stride), int(kernel_size)
-    offs = kernel_offsets(k, ts)
-    out_rows: List[np.ndarray] = []
-    out_ends: List[int] = []
-    nbrs: List[np.ndarray] = []
-    lo = 0
-    for b, hi in enumerate(int(e) for e in scene_rows):
-        cin = c[lo:hi, 1:]
-        if int(stride) == 1:
-            cout = cin
-        else:                                                    # floor division, first occurrence
-            q = np.floor_divide(cin, 2 * ts) * (2 * ts)
-            _, first = np.unique(q, axis=0, return_index=True)
-            cout = q[np.sort(first)] if len(q) else q
-        index = {tuple(int(v) for v in row): lo + i for i, row in enumerate(cin)}
-        nb = np.full((len(cout), k ** 3), -1, np.int32)
-        for o, row in enumerate(cout):
-            for j, d in enumerate(offs):
-                nb[o, j] = index.get((int(row[0] + d[0]), int(row[1] + d[1]), int(row[2] + d[2])), -1)
-        out_rows.append(np.concatenate([np.full((len(cout), 1), b, np.int64), cout], axis=1))
-        nbrs.append(nb)
-        out_ends.append((out_ends[-1] if out_ends else 0) + len(cout))
-        lo = hi
-    coords_out = np.concatenate(out_rows, axis=0).astype(np.int32) if out_rows else np.zeros((0, 4), np.int32)
-    nbr = np.concatenate(nbrs, axis=0) if nbrs else np.zeros((0, k ** 3), np.int32)
-    return coords_out, out_ends, nbr
-
-
-def sparse_conv3d_host(feats, nbr, weight, bias=None, scale=None, shift=None, residual=None, relu: bool = False) -> np.ndarray:
-    """numpy restatement of ``sparse_conv3d`` in the dtype of ``feats`` (float64: the reference of the tests; float32: the same chain in
-    the kernel's precision, summed in another order)."""
-    feats = np.asarray(feats)
-    dt = feats.dtype
-    nbr = np.asarray(nbr)
-    weight = np.asarray(weight, dt)
-    out = np.zeros((nbr.shape[0], weight.shape[2]), dt)
-    for j in range(nbr.shape[1]):
-        m = nbr[:, j] >= 0
-        if m.any():
-            out[m] += feats[nbr[m, j]] @ weight[j]
-    if bias is not None:
-        out = out + np.asarray(bias, dt).reshape(1, -1)
-    if scale is not None:
-        out = out * np.asarray(scale, dt).reshape(1, -1)
-    if shift is not None:
-        out = out + np.asarray(shift, dt).reshape(1, -1)
-    if residual is not None:
-        out = out + np.asarray(residual, dt)
-    if relu:
-        out = np.maximum(out, 0)
-    return out.astype(dt, copy=False)
-
-
-def sparse_max_pool3d_host(feats, nbr) -> np.ndarray:
-    """numpy restatement of ``sparse_max_pool3d`` (a row without a neighbour stays -inf)."""
-    feats = np.asarray(feats)
-    nbr = np.asarray(nbr)
-    out = np.full((nbr.shape[0], feats.shape[1]), -np.inf, feats.dtype)
-    for j in range(nbr.shape[1]):
-        m = nbr[:, j] >= 0
-        out[m] = np.maximum(out[m], feats[nbr[m, j]])
-    return out
-
-
-def kernel_map_transpose_host(nbr, n_in: int) -> np.ndarray:
-    """numpy restatement of the transposed map: ``nbr_t (n_in, k^3) int32``, ``nbr_t[i, j] = o`` with ``nbr[o, j] == i``, else -1 (at most
-    one such ``o`` exists).  Entries of ``nbr`` below 0 or ``>= n_in`` are skipped."""
-    nbr = np.asarray(nbr)
-    nbr_t = np.full((int(n_in), nbr.shape[1]), -1, np.int32)
-    o, j = np.nonzero((nbr >= 0) & (nbr < int(n_in)))
-    nbr_t[nbr[o, j], j] = o
-    return nbr_t
-
-
-def sparse_conv3d_bwd_host(g, feats, nbr, weight, out=None, scale=None, relu: bool = False, has_bias: bool = False,
-                           has_residual: bool = False) -> dict:
-    """numpy restatement of the backward of ``sparse_conv3d`` in the dtype of ``g``: ``dict(dfeats, dweight, dbias, dresidual)`` (the last
-    two ``None`` unless ``has_bias`` / ``has_residual``).  The ReLU mask is taken from the ``out`` it is handed (the forward's result);
-    ``scale`` is a constant the gradient passes through multiplied by."""
-    g = np.asarray(g)
-    dt = g.dtype
-    feats, nbr, weight = np.asarray(feats, dt), np.asarray(nbr), np.asarray(weight, dt)
-    d = g
-    if relu:
-        d = np.where(np.asarray(out) > 0, g, np.zeros((), dt)).astype(dt, copy=False)
-    gz = d if scale is None else (d * np.asarray(scale, dt).reshape(1, -1)).astype(dt, copy=False)
-    dfeats = np.zeros((feats.shape[0], weight.shape[1]), dt)
-    dweight = np.zeros(weight.shape, dt)
-    for j in range(nbr.shape[1]):
-        m = nbr[:, j] >= 0
-        if m.any():
-            dweight[j] = feats[nbr[m, j]].T @ gz[m]
-            dfeats[nbr[m, j]] += gz[m] @ weight[j].T          # (the rows nbr[m, j] are distinct: no collisions)
-    return dict(dfeats=dfeats, dweight=dweight, dbias=gz.sum(0).astype(dt, copy=False) if has_bias else None,
-                dresidual=d if has_residual else None)
-
-
-def sparse_max_pool3d_bwd_host(g, feats, nbr) -> np.ndarray:
-    """numpy restatement of the backward of ``sparse_max_pool3d``: every output element's gradient goes to the input row of the offset
-    that supplied the maximum -- ties to the smallest ``j`` --, summed per input row over ascending ``j``, in the dtype of ``g``."""
-    g, feats, nbr = np.asarray(g), np.asarray(feats), np.asarray(nbr)
-    n_out, C = g.shape
-    best = np.full((n_out, C), -np.inf, feats.dtype)
-    arg = np.full((n_out, C), 255, np.int64)
-    for j in range(nbr.shape[1]):
-        m = nbr[:, j] >= 0
-        x = feats[nbr[m, j]]
-        take = (x > best[m]) | (arg[m] == 255)              # strictly larger: a tie keeps the smaller j
-        arg[m] = np.where(take, j, arg[m])
-        best[m] = np.maximum(best[m], x)
-    dfeats = np.zeros((feats.shape[0], C), g.dtype)
-    for j in range(nbr.shape[1]):
-        m = nbr[:, j] >= 0
-        dfeats[nbr[m, j]] += np.where(arg[m] == j, g[m], np.zeros((), g.dtype))
-    return dfeats
-
-
-def _segments(seg_end: Sequence[int], n: int) -> List[int]:
-    ends = [int(e) for e in seg_end]
-    if not 1 <= len(ends) <= 64:
-        raise ValueError(f"1 to 64 segments, got {len(ends)}")
-    if any(b < a for a, b in zip([0] + ends[:-1], ends)) or ends[-1] != int(n):
-        raise ValueError(f"segment ends must ascend from 0 to the {n} rows, got {ends}")
-    return ends
-
-
-def sparse_norm_host(x, seg_end: Sequence[int], eps: float, weight=None, bias=None, residual=None, relu: bool = False,
-                     return_stats: bool = False, running=None, momentum: float = 0.1):
-    """numpy restatement of the norm kernels' forward in the dtype of ``x``, two-pass: per segment ``[seg_end[s-1], seg_end[s])`` and
-    column ``mean``, biased ``var = mean((x - mean)^2)``, ``rstd = 1 / sqrt(var + eps)``;
-    ``out = relu?(((x - mean) * rstd) * weight + bias (+ residual))``.  ``return_stats``: also ``stats (S, 2, C) = (mean, rstd)``, an
-    empty segment ``(0, 0)``.  ``running = (running_mean, running_var)`` (one segment of at least 2 rows): the two arrays are updated in
-    place as the kernel updates them, ``(1 - momentum) * old + momentum * new`` with the unbiased variance (``nn.BatchNorm1d``'s rule)."""
-    x = np.asarray(x)
-    dt = x.dtype
-    ends = _segments(seg_end, x.shape[0])
-    out = np.empty_like(x)
-    stats = np.zeros((len(ends), 2, x.shape[1]), dt)
-    lo = 0
-    for s, hi in enumerate(ends):
-        if hi > lo:
-            seg = x[lo:hi]
-            mean = seg.mean(axis=0, dtype=dt)
-            var = np.square(seg - mean).mean(axis=0, dtype=dt)
-            rstd = (1 / np.sqrt(var + dt.type(eps))).astype(dt, copy=False)
-            stats[s, 0], stats[s, 1] = mean, rstd
-            out[lo:hi] = (seg - mean) * rstd
-            if running is not None:
-                if len(ends) != 1 or hi < 2:
-                    raise ValueError("running statistics need one segment of at least 2 rows")
-                m = dt.type(momentum)
-                running[0][...] = (1 - m) * running[0] + m * mean
-                running[1][...] = (1 - m) * running[1] + m * (var * dt.type(hi) / dt.type(hi - 1))
-        lo = hi
-    if weight is not None:
-        out = out * np.asarray(weight, dt).reshape(1, -1)
-    if bias is not None:
-        out = out + np.asarray(bias, dt).reshape(1, -1)
-    if residual is not None:
-        out = out + np.asarray(residual, dt)
-    if relu:
-        out = np.maximum(out, 0)
-    out = out.astype(dt, copy=False)
-    return (out, stats) if return_stats else out
-
-
-def sparse_norm_bwd_host(g, x, seg_end: Sequence[int], eps: float, weight=None, out=None, relu: bool = False, stats=None) -> dict:
-    """numpy restatement of the norm kernels' backward in the dtype of ``g``: ``dict(dx, dweight, dbias, dresidual)``.  ``gy = g * [out > 0]``
-    with the ReLU mask taken from the ``out`` it is handed (``g`` itself without ReLU); ``xhat`` from ``x`` and ``stats`` (default: the
-    two-pass statistics of ``x``); ``dresidual = gy``, ``dbias = sum gy``, ``dweight = sum gy * xhat``; per segment ``a = mean gy``,
-    ``b = mean gy * xhat``, ``dx = weight * rstd * (gy - a - xhat * b)``."""
-    g = np.asarray(g)
-    dt = g.dtype
-    x = np.asarray(x, dt)
-    ends = _segments(seg_end, x.shape[0])
-    if stats is None:
-        _, stats = sparse_norm_host(x, ends, eps, return_stats=True)
-    stats = np.asarray(stats, dt)
-    gy = np.where(np.asarray(out) > 0, g, np.zeros((), dt)).astype(dt, copy=False) if relu else g
-    w = np.ones((1, x.shape[1]), dt) if weight is None else np.asarray(weight, dt).reshape(1, -1)
-    dx = np.empty_like(x)
-    xhat = np.empty_like(x)
-    lo = 0
-    for s, hi in enumerate(ends):
-        if hi > lo:
-            xh = (x[lo:hi] - stats[s, 0]) * stats[s, 1]
-            a = gy[lo:hi].mean(axis=0, dtype=dt)
-            b = (gy[lo:hi] * xh).mean(axis=0, dtype=dt)
-            dx[lo:hi] = (w * stats[s, 1]) * (gy[lo:hi] - a - xh * b)
-            xhat[lo:hi] = xh
-        lo = hi
-    return dict(dx=dx.astype(dt, copy=False), dweight=(gy * xhat).sum(axis=0, dtype=dt), dbias=gy.sum(axis=0, dtype=dt), dresidual=gy)
 
 
 # ---------------------------------------------------------------------------------------------------------------- device
@@ -342,7 +126,7 @@ def kernel_map(coords: torch.Tensor, scene_rows: Sequence[int], tensor_stride: i
     kvol = int(kernel_size) ** 3
     nbr = torch.empty((n_in, kvol), dtype=torch.int32, device=dev)
     out_c = torch.empty((n_in, 4), dtype=torch.int32, device=dev) if int(stride) == 2 else coords
-    ends_in = (ctypes.c_int32 * B)(*[int(e) for e in scene_rows])
+    ends_in = _int32_array(scene_rows)
     sc.info_np[:] = -1
     _abi.check(lib.ptx_sparse_kernel_map(coords.data_ptr(), ends_in, B, int(tensor_stride), int(kernel_size), int(stride),
                                          out_c.data_ptr() if int(stride) == 2 else None, sc.info.data_ptr() + 8, nbr.data_ptr(),
@@ -370,24 +154,57 @@ def _f32(t: Optional[torch.Tensor], what: str, dev) -> Optional[torch.Tensor]:
     return t
 
 
+def _f32_grad(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """fp32 and contiguous WITHOUT leaving the graph: the differentiable path's twin of ``_f32``, and what a backward makes of ``g``."""
+    if t is None or (t.dtype == torch.float32 and t.is_contiguous()):
+        return t
+    return t.to(torch.float32).contiguous()
+
+
+def _channel_vectors(what: str, C: int, dev, **vecs) -> list:
+    """The per-channel operands of a layer, each ``None`` or detached fp32 of ``C`` elements, flat."""
+    out = []
+    for name, v in vecs.items():
+        v = _f32(v, what, dev)
+        if v is not None:
+            v = v.reshape(-1)
+            if v.numel() != C:
+                raise ValueError(f"{what}: {name} must have {C} elements, got {v.numel()}")
+        out.append(v)
+    return out
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _int32_array(values: Sequence[int]):
+    """Scene / segment ends as the host array the entry points take."""
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
 def _wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.is_floating_point() and t.requires_grad for t in tensors)
 
 
-def _inference_only(what: str, *tensors) -> None:
-    if _wants_grad(*tensors):
+def _train(what: str, differentiable: bool, *tensors) -> bool:
+    """The opt-in rule of every layer: record for autograd only with ``differentiable=True`` and an input that requires grad; without the
+    flag such an input is refused instead of being answered with a detached result."""
+    wanted = _wants_grad(*tensors)
+    if wanted and not differentiable:
         raise NotImplementedError(f"{what} is inference-only by default: its backward pass is not enabled, and an input requires grad. "
                                   f"Pass differentiable=True, or call it under torch.no_grad() (or detach the inputs)")
+    return wanted
 
 
-_BWD_WS: dict = {}                 # stream -> uint8 workspace of ptx_sparse_conv3d_bwd (reused across layers and steps, grown on demand)
+_WORKSPACES: dict = {}             # (tag, device, stream) -> uint8 workspace, reused across layers and steps, grown on demand
 
 
-def _bwd_workspace(nbytes: int, dev) -> torch.Tensor:
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _BWD_WS.get(key)
+def _workspace(tag: str, nbytes: int, dev) -> torch.Tensor:
+    key = (tag, str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    ws = _WORKSPACES.get(key)
     if ws is None or ws.numel() < nbytes:
-        ws = _BWD_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        ws = _WORKSPACES[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     return ws
 
 
@@ -408,9 +225,8 @@ def _conv_forward(feats, kmap, weight, vecs, residual, relu) -> torch.Tensor:
     n_out, kvol = kmap.nbr.shape
     cin, cout = int(weight.shape[1]), int(weight.shape[2])
     out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
-    ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
     _abi.check(_abi.lib().ptx_sparse_conv3d(feats.data_ptr(), feats.shape[0], kmap.nbr.data_ptr(), n_out, kvol, weight.data_ptr(), cin,
-                                            cout, ptr(vecs[0]), ptr(vecs[1]), ptr(vecs[2]), ptr(residual), int(bool(relu)),
+                                            cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(residual), int(bool(relu)),
                                             out.data_ptr(), torch.cuda.current_stream(feats.device).cuda_stream), "ptx_sparse_conv3d")
     return out
 
@@ -434,8 +250,7 @@ class _SparseConv3dFn(torch.autograd.Function):
         kmap, scale, relu = ctx.kmap, ctx.scale, ctx.relu
         need_f, need_w, need_b, need_r = ctx.needs_input_grad[:4]
         dev = feats.device
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()
+        g = _f32_grad(g)
         n_out, kvol = kmap.nbr.shape
         n_in, cin, cout = int(feats.shape[0]), int(weight.shape[1]), int(weight.shape[2])
         lib = _abi.lib()
@@ -451,13 +266,12 @@ class _SparseConv3dFn(torch.autograd.Function):
         nbytes = lib.ptx_sparse_conv3d_bwd_workspace_bytes(n_out, kvol, cin, cout)
         if nbytes == 0:
             raise ValueError(f"sparse_conv3d backward: unsupported widths Cin={cin} Cout={cout} with {kvol} offsets")
-        ws = _bwd_workspace(nbytes, dev) if (need_w or need_b) else None
+        ws = _workspace("conv_bwd", nbytes, dev) if (need_w or need_b) else None
         nbr_t = _transposed(kmap, n_in) if need_f else None
-        ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-        _abi.check(lib.ptx_sparse_conv3d_bwd(g.data_ptr(), ptr(out), ptr(scale), int(relu), feats.data_ptr(), n_in, kmap.nbr.data_ptr(),
-                                             ptr(nbr_t), n_out, kvol, weight.data_ptr(), cin, cout, ptr(gz),
-                                             ptr(dres) if (relu and scale is not None) else None, ptr(dbias), ptr(dfeats), ptr(dweight),
-                                             ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+        _abi.check(lib.ptx_sparse_conv3d_bwd(g.data_ptr(), _ptr(out), _ptr(scale), int(relu), feats.data_ptr(), n_in, kmap.nbr.data_ptr(),
+                                             _ptr(nbr_t), n_out, kvol, weight.data_ptr(), cin, cout, _ptr(gz),
+                                             _ptr(dres) if (relu and scale is not None) else None, _ptr(dbias), _ptr(dfeats), _ptr(dweight),
+                                             _ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
                    "ptx_sparse_conv3d_bwd")
         if dbias is not None:
             dbias = dbias.reshape(ctx.bias_shape)
@@ -482,8 +296,7 @@ class _SparseMaxPool3dFn(torch.autograd.Function):
     def backward(ctx, g):
         (arg,) = ctx.saved_tensors
         kmap, n_in = ctx.kmap, ctx.n_in
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()
+        g = _f32_grad(g)
         n_out, kvol = kmap.nbr.shape
         C = int(arg.shape[1])
         dfeats = torch.empty((n_in, C), dtype=torch.float32, device=g.device)
@@ -492,13 +305,6 @@ class _SparseMaxPool3dFn(torch.autograd.Function):
                                                         dfeats.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream),
                    "ptx_sparse_max_pool3d_bwd")
         return dfeats, None
-
-
-def _f32_grad(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """fp32 and contiguous WITHOUT leaving the graph (the differentiable path's twin of ``_f32``)."""
-    if t is None or (t.dtype == torch.float32 and t.is_contiguous()):
-        return t
-    return t.to(torch.float32).contiguous()
 
 
 def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -511,14 +317,10 @@ def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bi
     ``residual`` requiring grad, the same launch is recorded for autograd (``ptx_sparse_conv3d_bwd``; same output bits) -- Cin a
     multiple of 64 up to 512 or the stem's 3; ``scale`` / ``shift`` are constants (a folded frozen BatchNorm) and must not require
     grad: the gradient passes through multiplied by ``scale``."""
-    train = False
-    if differentiable:
-        if _wants_grad(scale, shift):
-            raise ValueError("sparse_conv3d(differentiable=True): scale / shift are the constants of a folded frozen BatchNorm and get no "
-                             "gradient, but one of them requires grad; detach them (a training BatchNorm is nn.BatchNorm1d on the rows)")
-        train = _wants_grad(feats, weight, bias, residual)
-    else:
-        _inference_only("sparse_conv3d", feats, weight, bias, scale, shift, residual)
+    if differentiable and _wants_grad(scale, shift):
+        raise ValueError("sparse_conv3d(differentiable=True): scale / shift are the constants of a folded frozen BatchNorm and get no "
+                         "gradient, but one of them requires grad; detach them (a training BatchNorm is nn.BatchNorm1d on the rows)")
+    train = _train("sparse_conv3d", differentiable, feats, weight, bias, scale, shift, residual)
     if not (feats.is_cuda and kmap.nbr.is_cuda):
         raise RuntimeError("sparse_conv3d (HIP) needs GPU tensors: there is no CPU path")
     dev = feats.device
@@ -530,14 +332,7 @@ def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bi
     if kmap.n_in and feats.shape[0] != kmap.n_in:
         raise ValueError(f"sparse_conv3d: the kernel map was built over {kmap.n_in} rows, feats has {feats.shape[0]}")
     n_out, cin, cout = kmap.nbr.shape[0], int(weight.shape[1]), int(weight.shape[2])
-    vecs = []
-    for name, v in (("bias", bias), ("scale", scale), ("shift", shift)):
-        v = _f32(v, "sparse_conv3d", dev)
-        if v is not None:
-            v = v.reshape(-1)
-            if v.numel() != cout:
-                raise ValueError(f"sparse_conv3d: {name} must have {cout} elements, got {v.numel()}")
-        vecs.append(v)
+    vecs = _channel_vectors("sparse_conv3d", cout, dev, bias=bias, scale=scale, shift=shift)
     residual = _f32(residual, "sparse_conv3d", dev)
     if residual is not None and tuple(residual.shape) != (n_out, cout):
         raise ValueError(f"sparse_conv3d: residual must be {(n_out, cout)}, got {tuple(residual.shape)}")
@@ -557,9 +352,7 @@ def sparse_max_pool3d(feats: torch.Tensor, kmap: KernelMap, differentiable: bool
     Inference-only unless ``differentiable=True``: then, with grad mode on and ``feats`` requiring grad, ``ptx_sparse_max_pool3d_arg``
     also records which offset supplied each maximum (same output bits) and the backward routes the gradient there.  Ties go to the
     smallest offset index ``j``."""
-    train = differentiable and _wants_grad(feats)
-    if not differentiable:
-        _inference_only("sparse_max_pool3d", feats)
+    train = _train("sparse_max_pool3d", differentiable, feats)
     if not (feats.is_cuda and kmap.nbr.is_cuda):
         raise RuntimeError("sparse_max_pool3d (HIP) needs GPU tensors: there is no CPU path")
     dev = feats.device
@@ -579,23 +372,12 @@ def sparse_max_pool3d(feats: torch.Tensor, kmap: KernelMap, differentiable: bool
 
 
 # ---------------------------------------------------------------------------------------------------------------- norms
-_NORM_WS: dict = {}                # stream -> uint8 workspace of ptx_sparse_norm_fwd / _bwd (reused across layers and steps, grown on demand)
-
-
 def _norm_workspace(n: int, S: int, C: int, dev) -> torch.Tensor:
     nbytes = _abi.lib().ptx_sparse_norm_workspace_bytes(n, S, C)
     if nbytes == 0:
         raise ValueError(f"sparse norm: unsupported size, {n} rows x {C} channels in {S} segments (channels: a multiple of 64 up to 512; "
                          f"1 to 64 segments)")
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _NORM_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _NORM_WS[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+    return _workspace("norm", nbytes, dev)
 
 
 def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, momentum=0.0):
@@ -606,7 +388,7 @@ def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, mome
     ws = _norm_workspace(n, S, C, dev)
     out = torch.empty_like(x)
     stats = torch.empty((S, 2, C), dtype=torch.float32, device=dev)
-    seg = (ctypes.c_int32 * S)(*ends)
+    seg = _int32_array(ends)
     rm, rv = running if running is not None else (None, None)
     _abi.check(_abi.lib().ptx_sparse_norm_fwd(x.data_ptr(), seg, S, n, C, float(eps), _ptr(weight), _ptr(bias), _ptr(residual), int(bool(relu)),
                                               _ptr(rm), _ptr(rv), float(momentum), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -618,7 +400,7 @@ def _norm_apply(x, ends, stats, weight, bias, residual, relu):
     n, C = int(x.shape[0]), int(x.shape[1])
     S = len(ends)
     out = torch.empty_like(x)
-    seg = (ctypes.c_int32 * S)(*ends)
+    seg = _int32_array(ends)
     _abi.check(_abi.lib().ptx_sparse_norm_apply(x.data_ptr(), seg, S, n, C, stats.data_ptr(), _ptr(weight), _ptr(bias), _ptr(residual),
                                                 int(bool(relu)), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
                "ptx_sparse_norm_apply")
@@ -644,8 +426,7 @@ class _SparseNormFn(torch.autograd.Function):
         x, stats, w, out = ctx.saved_tensors
         need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
         dev = x.device
-        if g.dtype != torch.float32 or not g.is_contiguous():
-            g = g.to(torch.float32).contiguous()
+        g = _f32_grad(g)
         n, C = int(x.shape[0]), int(x.shape[1])
         S = len(ctx.ends)
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
@@ -657,7 +438,7 @@ class _SparseNormFn(torch.autograd.Function):
             dres = new(n, C) if ctx.relu else g
         if need_x or need_w or need_b or (need_r and ctx.relu):
             ws = _norm_workspace(n, S, C, dev)
-            seg = (ctypes.c_int32 * S)(*ctx.ends)
+            seg = _int32_array(ctx.ends)
             _abi.check(_abi.lib().ptx_sparse_norm_bwd(g.data_ptr(), x.data_ptr(), _ptr(out), seg, S, n, C, stats.data_ptr(), _ptr(w), _ptr(dx),
                                                       _ptr(dw), _ptr(db), _ptr(dres) if ctx.relu else None, ws.data_ptr(), ws.numel(),
                                                       torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_bwd")
@@ -677,14 +458,7 @@ def _norm_operands(what: str, feats, weight, bias, residual):
     if x.dim() != 2 or x.shape[1] < 64 or x.shape[1] > 512 or x.shape[1] % 64:
         raise ValueError(f"{what}: feats (n,C) with C a multiple of 64 up to 512 expected, got {tuple(x.shape)}")
     C = int(x.shape[1])
-    vecs = []
-    for name, v in (("weight", weight), ("bias", bias)):
-        v = _f32(v, what, dev)
-        if v is not None:
-            v = v.reshape(-1)
-            if v.numel() != C:
-                raise ValueError(f"{what}: {name} must have {C} elements, got {v.numel()}")
-        vecs.append(v)
+    vecs = _channel_vectors(what, C, dev, weight=weight, bias=bias)
     residual = _f32(residual, what, dev)
     if residual is not None and tuple(residual.shape) != tuple(x.shape):
         raise ValueError(f"{what}: residual must be {tuple(x.shape)}, got {tuple(residual.shape)}")
@@ -701,11 +475,7 @@ def sparse_segment_norm(feats: torch.Tensor, seg_end: Sequence[int], eps: float,
     with the segments' ``(mean, rstd)``.  Inference-only unless ``differentiable=True``: then, with grad mode on and ``feats`` /
     ``weight`` / ``bias`` / ``residual`` requiring grad, the same launches are recorded for autograd (``ptx_sparse_norm_bwd``; same
     output bits)."""
-    if differentiable:
-        train = _wants_grad(feats, weight, bias, residual)
-    else:
-        _inference_only("sparse_segment_norm", feats, weight, bias, residual)
-        train = False
+    train = _train("sparse_segment_norm", differentiable, feats, weight, bias, residual)
     x, w, b, res = _norm_operands("sparse_segment_norm", feats, weight, bias, residual)
     ends = _segments(seg_end, x.shape[0])
     if not train:
@@ -782,11 +552,7 @@ def sparse_batch_norm(feats: torch.Tensor, bn: nn.Module, residual: Optional[tor
     ``differentiable=True``; then the training-mode call is recorded for autograd (gradients to ``feats``, ``bn.weight``, ``bn.bias``,
     ``residual``).  An eval-mode BatchNorm is a constant affine map: to train through it fold it into ``sparse_conv3d`` (``bn_fold``)."""
     _check_bn(bn)
-    if differentiable:
-        train = _wants_grad(feats, bn.weight, bn.bias, residual)
-    else:
-        _inference_only("sparse_batch_norm", feats, bn.weight, bn.bias, residual)
-        train = False
+    train = _train("sparse_batch_norm", differentiable, feats, bn.weight, bn.bias, residual)
     if feats.dim() == 2 and bn.num_features != feats.shape[1]:
         raise ValueError(f"sparse_batch_norm: the BatchNorm has {bn.num_features} features, feats has {feats.shape[1]} channels")
     x, w, b, res = _norm_operands("sparse_batch_norm", feats, bn.weight, bn.bias, residual)

@@ -3,10 +3,10 @@
 Eval: ``MinkResNet(34, 3)`` with seeded kaiming kernels, BatchNorm weights in U(0.5, 1.5), running means N(0, 0.1) and running variances
 in U(0.5, 1.5) on the rows of the convolution's tests (2351 rows, four scenes of which one is empty and one has a single row): every
 level's rows bit for bit against ``forward_host`` and ``pipeline.level_coordinates``, every level's features against ``forward_host``
-in float64 under the rule of the convolution's tests (``_hold``: at most 8 x the error of ``forward_host`` in float32).
+in float64 under the rule of the convolution's tests (``sparse_util.hold``: at most 8 x the error of ``forward_host`` in float32).
 
 Train: one step of ``MinkResNet(18, 3, differentiable=True)``, loss = sum_l (out_l * G_l).sum(), against the same network composed from
-torch ops over the host kernel maps in float64 on the CPU (``composition`` of tests/test_sparse_conv_grad_host.py, ``F.batch_norm``, the
+torch ops over the host kernel maps in float64 on the CPU (``composition`` of tests/sparse_util.py, ``F.batch_norm``, the
 restated instance norm, a stacked max), yardstick the same composition in float32, 8 x; the ReLU masks of both references are the
 GPU's outputs', as in the layer tests.  Both torch references run with ``CPU_THREADS`` threads, set and restored around them: torch
 splits its fp32 reductions over the rows by thread, so the yardstick's own error depends on the count -- 2e-6 of scale with 8 or 16
@@ -24,8 +24,7 @@ import torch.nn.functional as F
 
 from proxytransformation_amd import MinkResNet, sparse
 from proxytransformation_amd.pipeline import MINK_RESNET_STRIDES, level_coordinates
-from tests.test_gpu_sparse_conv import _hold, _rel, _rows
-from tests.test_sparse_conv_grad_host import composition
+from tests import sparse_util as su
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +47,7 @@ def _seeded(depth, **kw):
 
 @functools.lru_cache(maxsize=None)
 def _inputs():
-    rows, ends = _rows(1)
+    rows, ends = su.rows(1)
     feats = np.random.default_rng(11).uniform(0.0, 1.0, (rows.shape[0], 3)).astype(np.float32)      # colours
     return rows, list(ends), feats
 
@@ -74,7 +73,7 @@ def test_eval_forward_against_the_host_restatement():
         assert lv.scene_rows[2] == lv.scene_rows[1]            # the empty scene stays empty
         assert lv.feats.shape == (r64.coords.shape[0], 64 * 2 ** l) and lv.feats.dtype == torch.float32
         assert torch.equal(lv.feats, again[l].feats), "two forwards on the same inputs differ"
-        _hold(f"MinkResNet34 eval level {l} rows={lv.feats.shape[0]}", lv.feats.cpu().numpy(), r32.feats, r64.feats)
+        su.hold(f"MinkResNet34 eval level {l} rows={lv.feats.shape[0]}", lv.feats.cpu().numpy(), r32.feats, r64.feats)
 
 
 def test_golden_names_load_strictly_and_the_fold_is_cached():
@@ -121,7 +120,7 @@ def _torch_network(ref, maps, feats, masks):
             y = y + residual
         return y * masks[name].to(y.dtype) if relu else y
 
-    x = _instance_norm(composition(feats, maps["stem"][2], ref.conv1.kernel), maps["stem"][1], ref.norm1.weight, ref.norm1.bias)
+    x = _instance_norm(su.composition(feats, maps["stem"][2], ref.conv1.kernel), maps["stem"][1], ref.norm1.weight, ref.norm1.bias)
     x = x * masks["norm1"].to(x.dtype)
     idx = torch.from_numpy(maps["pool"][2]).long()
     x = x[idx.clamp(min=0)].masked_fill((idx < 0).unsqueeze(-1), -np.inf).max(dim=1).values
@@ -130,11 +129,11 @@ def _torch_network(ref, maps, feats, masks):
         n_down, n_side, n_same = maps["down", i][2], maps["side", i][2], maps["same", i][2]
         for j, blk in enumerate(getattr(ref, f"layer{i + 1}")):
             pre = f"layer{i + 1}.{j}."
-            h = bn(pre + "norm1", blk.norm1, composition(x, n_down if j == 0 else n_same, blk.conv1.kernel))
+            h = bn(pre + "norm1", blk.norm1, su.composition(x, n_down if j == 0 else n_same, blk.conv1.kernel))
             side = x
             if blk.downsample is not None:
-                side = bn(pre + "downsample.1", blk.downsample[1], composition(x, n_side, blk.downsample[0].kernel), relu=False)
-            x = bn(pre + "norm2", blk.norm2, composition(h, n_same, blk.conv2.kernel), residual=side)
+                side = bn(pre + "downsample.1", blk.downsample[1], su.composition(x, n_side, blk.downsample[0].kernel), relu=False)
+            x = bn(pre + "norm2", blk.norm2, su.composition(h, n_same, blk.conv2.kernel), residual=side)
         outs.append(x)
     return outs
 
@@ -177,18 +176,18 @@ def test_train_step_against_the_torch_composition():
     r64, r32 = done[torch.float64], done[torch.float32]
     for l, lv in enumerate(outs):
         assert lv.feats.shape == r64["outs"][l].shape
-        _hold(f"train level {l} out", lv.feats.detach().cpu().numpy(), r32["outs"][l], r64["outs"][l])
+        su.hold(f"train level {l} out", lv.feats.detach().cpu().numpy(), r32["outs"][l], r64["outs"][l])
     g_params = dict(gpu.named_parameters())
     for k in wrt:
         assert g_params[k].grad is not None and g_params[k].grad.shape == g_params[k].shape, k
-        _hold(f"train d {k}", g_params[k].grad.cpu().numpy(), r32["grads"][k], r64["grads"][k])
-    _hold("train d feats", x.grad.cpu().numpy(), r32["feats"], r64["feats"])
+        su.hold(f"train d {k}", g_params[k].grad.cpu().numpy(), r32["grads"][k], r64["grads"][k])
+    su.hold("train d feats", x.grad.cpu().numpy(), r32["feats"], r64["feats"])
     for k, v in gpu.named_buffers():                         # the running statistics after the step
         if k.endswith("num_batches_tracked"):
             assert int(v) == 1, k
         elif k in ("layer1.0.norm1.bn.running_mean", "layer1.0.norm1.bn.running_var", "layer2.0.downsample.1.bn.running_var",
                    "layer3.1.norm2.bn.running_mean", "layer4.1.norm2.bn.running_var"):
-            _hold(f"train {k}", v.cpu().numpy(), r32["buffers"][k], r64["buffers"][k])
+            su.hold(f"train {k}", v.cpu().numpy(), r32["buffers"][k], r64["buffers"][k])
 
 
 def test_train_mode_without_differentiable_raises():

@@ -4,75 +4,27 @@ the calls against the float64 restatement, with a bar measured in the test -- 8 
 CPU (``sparse_conv3d_host`` in float32, resp. torch's dense fp32 ops for the block): both are fp32 sums of the same length and
 differ only in summation order, a dropped term shows at 1e-2; the max-pool bit for bit; the rejections.
 
-Rows: a dense 6x6x6 block (all 27 neighbours present), ~2100 random rows in [-40,40)^3 * ts (most neighbours missing; the row count is
-no multiple of the 64-row tile), an empty scene, and a last scene with one row."""
-import functools
-
+Rows (``tests/sparse_util.py``): a dense 6x6x6 block (all 27 neighbours present), ~2100 random rows in [-40,40)^3 * ts (most neighbours
+missing; the row count is no multiple of the 64-row tile), an empty scene, and a last scene with one row."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from proxytransformation_amd import sparse
+from tests import sparse_util as su
+from tests.sparse_util import DEV
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-
-
-@functools.lru_cache(maxsize=None)
-def _rows(ts, only_random=0):
-    rng = np.random.default_rng(2024)
-    block = np.stack(np.meshgrid(*[np.arange(-3, 3)] * 3, indexing="ij"), -1).reshape(-1, 3)
-    block = block[rng.permutation(len(block))]
-    rnd = rng.integers(-40, 40, size=(2140, 3))
-    _, first = np.unique(rnd, axis=0, return_index=True)
-    rnd = rnd[np.sort(first)]
-    if only_random:
-        rnd = rnd[:only_random]
-        return np.concatenate([np.zeros((len(rnd), 1), np.int64), rnd * ts], 1).astype(np.int32), (len(rnd),)
-    one = np.array([[5, -7, 2]])
-    scenes = [block, rnd, rnd[:0], one]
-    rows = np.concatenate([np.concatenate([np.full((len(c), 1), b), c * ts], 1) for b, c in enumerate(scenes)]).astype(np.int32)
-    ends = tuple(np.cumsum([len(c) for c in scenes]).tolist())
-    assert rows.shape[0] % 64 != 0 and rows.shape[0] > 2200
-    return rows, ends
-
-
-@functools.lru_cache(maxsize=None)
-def _host_map(ts, k, s, only_random=0):
-    rows, ends = _rows(ts, only_random)
-    return sparse.kernel_map_host(rows, list(ends), ts, k, s)
-
-
-def _device_map(ts, k, s, only_random=0):
-    rows, ends = _rows(ts, only_random)
-    return sparse.kernel_map(torch.from_numpy(rows).to(DEV), list(ends), ts, k, s)
-
-
-def _rel(a, ref):
-    return float(np.abs(a.astype(np.float64) - ref).max() / np.abs(ref).max())
-
-
-_MEASURED = []
-
-
-def _hold(name, got, ref32, ref64):
-    """max |got - ref64| / max |ref64| against 8 x the same statistic of the fp32 CPU chain, both printed."""
-    e_gpu, e_cpu = _rel(got, ref64), _rel(ref32, ref64)
-    _MEASURED.append((name, e_gpu, e_cpu))
-    print(f"sparse_conv {name}: gpu {e_gpu:.3e}  fp32-cpu {e_cpu:.3e}  ratio {e_gpu / max(e_cpu, 1e-30):.2f}")
-    assert e_cpu < 1e-5, (name, e_cpu)                       # the yardstick itself is an fp32 rounding error, not a wrong answer
-    assert e_gpu <= 8.0 * e_cpu, (name, e_gpu, e_cpu)
 
 
 # ------------------------------------------------------------------------------------------------------------------ kernel map
 @pytest.mark.parametrize("ts", [1, 4])
 @pytest.mark.parametrize("k,s", [(3, 1), (3, 2), (1, 2), (2, 2)])
 def test_kernel_map_is_the_host_restatement(k, s, ts):
-    rows, ends = _rows(ts)
-    want_c, want_e, want_n = _host_map(ts, k, s)
-    km = _device_map(ts, k, s)
+    rows, ends = su.rows(ts)
+    want_c, want_e, want_n = su.host_map(ts, k, s)
+    km = su.device_map(ts, k, s)
     assert km.scene_rows == want_e and km.kernel_size == k and km.stride == s and km.tensor_stride == ts * s
     assert np.array_equal(km.coords.cpu().numpy(), want_c)
     assert km.nbr.dtype == torch.int32 and np.array_equal(km.nbr.cpu().numpy(), want_n)
@@ -88,14 +40,14 @@ def test_kernel_map_is_the_host_restatement(k, s, ts):
 def test_kernel_map_rejects_a_coordinate_outside_the_key_range():
     """The range is checked where the coordinates are, on the device: the call raises before it returns a map, so nothing that
     would consume one is ever enqueued; the scratch stays good for the next call."""
-    rows, ends = _rows(1)
+    rows, ends = su.rows(1)
     bad = rows.copy()
     bad[300, 2] = 1 << 18
     for k, s in ((3, 1), (3, 2)):
         with pytest.raises(RuntimeError, match="ptx_sparse_kernel_map failed"):
             sparse.kernel_map(torch.from_numpy(bad).to(DEV), list(ends), 1, k, s)
-    km = _device_map(1, 3, 2)
-    assert np.array_equal(km.nbr.cpu().numpy(), _host_map(1, 3, 2)[2])
+    km = su.device_map(1, 3, 2)
+    assert np.array_equal(km.nbr.cpu().numpy(), su.host_map(1, 3, 2)[2])
     with pytest.raises(RuntimeError, match="tensor_stride=3"):
         from proxytransformation_amd import _abi
         import ctypes
@@ -105,15 +57,6 @@ def test_kernel_map_rejects_a_coordinate_outside_the_key_range():
 
 
 # ------------------------------------------------------------------------------------------------------------------ convolution
-def _operands(n_in, n_out, cin, cout, kvol, seed):
-    rng = np.random.default_rng(seed)
-    return dict(feats=rng.standard_normal((n_in, cin)).astype(np.float32),
-                weight=(rng.standard_normal((kvol, cin, cout)) / np.sqrt(kvol * cin)).astype(np.float32),
-                bias=rng.standard_normal(cout).astype(np.float32) * 0.5,
-                scale=rng.uniform(0.5, 1.5, cout).astype(np.float32), shift=rng.standard_normal(cout).astype(np.float32) * 0.5,
-                residual=rng.standard_normal((n_out, cout)).astype(np.float32))
-
-
 def _run(km, ops, use=(), relu=False):
     t = lambda a: torch.from_numpy(a).to(DEV)                # noqa: E731
     with torch.no_grad():
@@ -132,18 +75,18 @@ def _refs(nbr, ops, use=(), relu=False):
 def test_convolution_against_the_float64_restatement(cin, cout, k, s):
     ts = 1 if cin == 3 else 4
     cut = 600 if cin == 512 else 0                           # the 512-wide case: the random scene alone, cut to 600 rows
-    _, _, nbr = _host_map(ts, k, s, cut)
-    km = _device_map(ts, k, s, cut)
+    _, _, nbr = su.host_map(ts, k, s, cut)
+    km = su.device_map(ts, k, s, cut)
     assert np.array_equal(km.nbr.cpu().numpy(), nbr)
-    n_in = _rows(ts, cut)[0].shape[0]
-    ops = _operands(n_in, nbr.shape[0], cin, cout, k ** 3, seed=cin + cout)
+    n_in = su.rows(ts, cut)[0].shape[0]
+    ops = su.operands(n_in, nbr.shape[0], cin, cout, k ** 3, seed=cin + cout)
     use = ("bias", "scale", "shift") if k == 1 else ()
     got = _run(km, ops, use)
     again = _run(km, ops, use)
     assert got.shape == (nbr.shape[0], cout) and got.dtype == torch.float32
     assert torch.equal(got, again), "two launches on the same inputs differ"
     r32, r64 = _refs(nbr, ops, use)
-    _hold(f"Cin={cin} Cout={cout} k={k} s={s} rows={n_in}->{nbr.shape[0]}", got.cpu().numpy(), r32, r64)
+    su.hold(f"Cin={cin} Cout={cout} k={k} s={s} rows={n_in}->{nbr.shape[0]}", got.cpu().numpy(), r32, r64)
     if k == 1:                                               # 1x1 stride 2: a coarse cell without a row AT its corner has no neighbour
         lone = (nbr < 0).all(axis=1)
         assert lone.sum() > 100
@@ -154,22 +97,22 @@ def test_convolution_against_the_float64_restatement(cin, cout, k, s):
 @pytest.mark.parametrize("use,relu", [(("bias",), False), (("scale", "shift"), True), (("residual",), False),
                                       (("bias", "scale", "shift", "residual"), True), ((), True)])
 def test_epilogue_parts(use, relu):
-    _, _, nbr = _host_map(4, 3, 1)
-    km = _device_map(4, 3, 1)
-    ops = _operands(nbr.shape[0], nbr.shape[0], 64, 64, 27, seed=77)
+    _, _, nbr = su.host_map(4, 3, 1)
+    km = su.device_map(4, 3, 1)
+    ops = su.operands(nbr.shape[0], nbr.shape[0], 64, 64, 27, seed=77)
     got = _run(km, ops, use, relu)
     r32, r64 = _refs(nbr, ops, use, relu)
-    _hold("epilogue " + "+".join(use) + ("+relu" if relu else ""), got.cpu().numpy(), r32, r64)
+    su.hold("epilogue " + "+".join(use) + ("+relu" if relu else ""), got.cpu().numpy(), r32, r64)
     if relu:
         assert float(got.min()) == 0.0
 
 
 def test_module_forward_and_conversions():
     """SparseConv3d.forward = sparse_conv3d on its ``kernel`` / ``bias``; fp64 / non-contiguous inputs are converted."""
-    _, _, nbr = _host_map(4, 3, 2)
-    km = _device_map(4, 3, 2)
-    n_in = _rows(4)[0].shape[0]
-    ops = _operands(n_in, nbr.shape[0], 64, 128, 27, seed=5)
+    _, _, nbr = su.host_map(4, 3, 2)
+    km = su.device_map(4, 3, 2)
+    n_in = su.rows(4)[0].shape[0]
+    ops = su.operands(n_in, nbr.shape[0], 64, 128, 27, seed=5)
     m = sparse.SparseConv3d(64, 128, kernel_size=3, stride=2, bias=True).to(DEV).eval()
     m.load_state_dict({"kernel": torch.from_numpy(ops["weight"]), "bias": torch.from_numpy(ops["bias"]).view(1, -1)})
     with torch.no_grad():
@@ -179,20 +122,20 @@ def test_module_forward_and_conversions():
         assert torch.equal(m(wide[:, :64], km), want)
     with pytest.raises(ValueError, match="kernel map"):
         with torch.no_grad():
-            m(torch.from_numpy(ops["feats"]).to(DEV), _device_map(4, 3, 1))
+            m(torch.from_numpy(ops["feats"]).to(DEV), su.device_map(4, 3, 1))
 
 
 def test_max_pool_is_the_restatement_bit_for_bit():
-    _, _, nbr = _host_map(4, 2, 2)
-    km = _device_map(4, 2, 2)
-    feats = np.random.default_rng(9).standard_normal((_rows(4)[0].shape[0], 64)).astype(np.float32)
+    _, _, nbr = su.host_map(4, 2, 2)
+    km = su.device_map(4, 2, 2)
+    feats = np.random.default_rng(9).standard_normal((su.rows(4)[0].shape[0], 64)).astype(np.float32)
     got = sparse.sparse_max_pool3d(torch.from_numpy(feats).to(DEV), km)
     assert np.array_equal(got.cpu().numpy(), sparse.sparse_max_pool3d_host(feats, nbr))
     assert np.isfinite(got.cpu().numpy()).all()
 
 
 def test_rejections():
-    km = _device_map(4, 3, 1)
+    km = su.device_map(4, 3, 1)
     n = km.nbr.shape[0]
     with torch.no_grad():
         with pytest.raises(RuntimeError, match=r"ptx_sparse_conv3d: Cin=24 Cout=64"):
@@ -274,4 +217,4 @@ def test_basic_block_against_dense_torch():
     sided = bn(F.conv3d(g, dense_w(wd, 1), stride=2), sd, bd)
     outd = F.relu(bn(F.conv3d(hd, dense_w(w2, 3), padding=1), s2, b2) + sided) * mask
     ref32 = outd[0][:, oi[:, 0], oi[:, 1], oi[:, 2]].numpy().T
-    _hold("BasicBlock 64->128 rows=2000->%d" % oc.shape[0], got, ref32, ref64)
+    su.hold("BasicBlock 64->128 rows=2000->%d" % oc.shape[0], got, ref32, ref64)

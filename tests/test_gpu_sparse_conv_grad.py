@@ -1,6 +1,6 @@
 """Backward of the sparse convolution and max-pool (``differentiable=True``; csrc/sparse_bwd.hip): the transposed kernel map bit for bit
 against ``kernel_map_transpose_host``; dfeats / dweight / dbias / dresidual against the float64 restatement ``sparse_conv3d_bwd_host``
-under the rule of tests/test_gpu_sparse_conv.py (``_hold``: 8 x the error of the SAME chain in fp32 on the CPU, the ReLU mask of both
+under the rule of tests/test_gpu_sparse_conv.py (``sparse_util.hold``: 8 x the error of the SAME chain in fp32 on the CPU, the ReLU mask of both
 references taken from the GPU's forward ``out``); bitwise repeatability; the split of dweight over row chunks at its boundaries; the
 opt-in surface; the pool's routing bit for bit; a training BasicBlock with ``nn.BatchNorm1d`` on the rows; and the link the backward
 exists for: neck (train) -> differentiable quantize -> kernel map -> stem convolution -> loss.backward().
@@ -15,12 +15,10 @@ import torch
 from torch import nn
 
 from proxytransformation_amd import sparse
-from tests.test_gpu_sparse_conv import _device_map, _hold, _host_map, _operands, _rows
-from tests.test_sparse_conv_grad_host import composition
+from tests import sparse_util as su
+from tests.sparse_util import DEV
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 def _t(a, grad=False):
@@ -33,9 +31,9 @@ def _t(a, grad=False):
 @pytest.mark.parametrize("k,s", [(3, 1), (3, 2), (1, 2), (2, 2)])
 def test_transposed_map_is_the_host_restatement(k, s, ts):
     """``KernelMap.nbr_t`` is filled by the first differentiable call on the map (here: the pool's backward) and reused afterwards."""
-    _, _, nbr = _host_map(ts, k, s)
-    km = _device_map(ts, k, s)
-    n_in = _rows(ts)[0].shape[0]
+    _, _, nbr = su.host_map(ts, k, s)
+    km = su.device_map(ts, k, s)
+    n_in = su.rows(ts)[0].shape[0]
     assert km.nbr_t is None and km.n_in == n_in
     x = torch.zeros(n_in, 4, device=DEV, requires_grad=True)
     sparse.sparse_max_pool3d(x, km, differentiable=True).sum().backward()
@@ -72,10 +70,10 @@ def test_gradients_against_the_float64_restatement(cin, cout, k, s):
     """The full set splits dweight over several row chunks with a partial last one (64 -> 64: 10 chunks of 256 rows over 2351)."""
     ts = 1 if cin == 3 else 4
     cut = 600 if cin == 512 else 0
-    _, _, nbr = _host_map(ts, k, s, cut)
-    km = _device_map(ts, k, s, cut)
-    n_in = _rows(ts, cut)[0].shape[0]
-    ops = _operands(n_in, nbr.shape[0], cin, cout, k ** 3, seed=cin + cout)
+    _, _, nbr = su.host_map(ts, k, s, cut)
+    km = su.device_map(ts, k, s, cut)
+    n_in = su.rows(ts, cut)[0].shape[0]
+    ops = su.operands(n_in, nbr.shape[0], cin, cout, k ** 3, seed=cin + cout)
     full = k == 1                                            # bias + scale + shift + residual + ReLU on the 1x1 stride-2 layer
     out, G, got = _grad_case(km, nbr, ops, full, relu=full, seed=cin)
     out2, _, again = _grad_case(km, nbr, ops, full, relu=full, seed=cin)
@@ -90,7 +88,7 @@ def test_gradients_against_the_float64_restatement(cin, cout, k, s):
         g = got[name]
         assert g is not None and g.dtype == torch.float32 and tuple(g.shape) == tuple(ops[name].shape), name
         assert torch.equal(g, again[name]), f"{name}: two backward calls on the same inputs differ"
-        _hold(f"{tag} {key}", g.cpu().numpy().reshape(r64[key].shape), r32[key], r64[key])
+        su.hold(f"{tag} {key}", g.cpu().numpy().reshape(r64[key].shape), r32[key], r64[key])
     if full:
         lone = (nbr < 0).all(axis=1)                         # rows without a neighbour feed dbias / dresidual, not dfeats / dweight
         assert lone.sum() > 100 and (out.cpu().numpy()[lone] > 0).any()
@@ -103,18 +101,18 @@ def test_one_row_scene_alone():
     km = sparse.kernel_map(_t(rows), [1], 1, 3, 1)
     nbr = sparse.kernel_map_host(rows, [1], 1, 3, 1)[2]
     assert np.array_equal(km.nbr.cpu().numpy(), nbr) and (nbr >= 0).sum() == 1
-    ops = _operands(1, 1, 64, 64, 27, seed=3)
+    ops = su.operands(1, 1, 64, 64, 27, seed=3)
     out, G, got = _grad_case(km, nbr, ops, full=True, relu=False, seed=1)
     r32, r64 = _grad_refs(nbr, ops, out.cpu().numpy(), G, True, relu=False)
     for name, key in (("feats", "dfeats"), ("weight", "dweight"), ("bias", "dbias"), ("residual", "dresidual")):
-        _hold(f"bwd one row {key}", got[name].cpu().numpy().reshape(r64[key].shape), r32[key], r64[key])
+        su.hold(f"bwd one row {key}", got[name].cpu().numpy().reshape(r64[key].shape), r32[key], r64[key])
     assert (got["weight"].cpu().numpy()[np.arange(27) != 13] == 0).all()      # only the centre offset has a pair
 
 
 def test_needs_input_grad_and_rejections():
-    _, _, nbr = _host_map(4, 3, 1)
-    km = _device_map(4, 3, 1)
-    ops = _operands(nbr.shape[0], nbr.shape[0], 64, 64, 27, seed=77)
+    _, _, nbr = su.host_map(4, 3, 1)
+    km = su.device_map(4, 3, 1)
+    ops = su.operands(nbr.shape[0], nbr.shape[0], 64, 64, 27, seed=77)
     _, _, both = _grad_case(km, nbr, ops, full=True, relu=True, seed=5)
     assert tuple(both["bias"].shape) == tuple(ops["bias"].shape)
     _, _, only_f = _grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("feats",))
@@ -154,10 +152,10 @@ def test_needs_input_grad_and_rejections():
 # ------------------------------------------------------------------------------------------------------------------ max-pool
 @pytest.mark.parametrize("k,s", [(2, 2), (3, 1)])
 def test_pool_routes_the_gradient_bit_for_bit(k, s):
-    _, _, nbr = _host_map(4, k, s)
-    km = _device_map(4, k, s)
+    _, _, nbr = su.host_map(4, k, s)
+    km = su.device_map(4, k, s)
     rng = np.random.default_rng(9)
-    feats = rng.standard_normal((_rows(4)[0].shape[0], 64)).astype(np.float32)
+    feats = rng.standard_normal((su.rows(4)[0].shape[0], 64)).astype(np.float32)
     feats[:, :8] = np.round(feats[:, :8])                    # ties: they go to the smallest j
     G = rng.standard_normal((nbr.shape[0], 64)).astype(np.float32)
     x = _t(feats, grad=True)
@@ -182,7 +180,7 @@ class _TorchConv(nn.Module):
         self.kernel, self.nbr = nn.Parameter(kernel), nbr
 
     def forward(self, x):
-        return composition(x, self.nbr, self.kernel)
+        return su.composition(x, self.nbr, self.kernel)
 
 
 def _block(conv1, bn1, conv2, bn2, x):
@@ -194,8 +192,8 @@ def test_training_basic_block_against_float64_torch():
     """SparseConv3d(64, 64, 3, differentiable=True) -> nn.BatchNorm1d(64).train() -> ReLU -> conv -> BN -> + x -> ReLU on 600 random
     rows; every parameter gradient and dx against the same block in torch float64 on the CPU, yardstick: that block in float32."""
     ts = 4
-    _, _, nbr = _host_map(ts, 3, 1, 600)
-    km = _device_map(ts, 3, 1, 600)
+    _, _, nbr = su.host_map(ts, 3, 1, 600)
+    km = su.device_map(ts, 3, 1, 600)
     rng = np.random.default_rng(17)
     x_np = rng.standard_normal((nbr.shape[0], 64)).astype(np.float32)
     G = rng.standard_normal((nbr.shape[0], 64)).astype(np.float32)
@@ -226,9 +224,9 @@ def test_training_basic_block_against_float64_torch():
     out_gpu, got, cs = run(torch.float32, DEV)
     out64, ref64, _ = run(torch.float64, "cpu")
     out32, ref32, _ = run(torch.float32, "cpu")
-    _hold("train BasicBlock out", out_gpu, out32, out64)
+    su.hold("train BasicBlock out", out_gpu, out32, out64)
     for name in got:
-        _hold(f"train BasicBlock {name}", got[name], ref32[name], ref64[name])
+        su.hold(f"train BasicBlock {name}", got[name], ref32[name], ref64[name])
     before = cs[0].kernel.detach().clone()
     torch.optim.SGD(cs[0].parameters(), lr=0.1).step()
     assert not torch.equal(cs[0].kernel.detach(), before) and bool(torch.isfinite(cs[0].kernel).all())
@@ -266,10 +264,10 @@ def test_the_neck_trains_through_the_stem_convolution():
     for dt in (torch.float64, torch.float32):
         f = feats.detach().cpu().to(dt).requires_grad_()
         w = stem.kernel.detach().cpu().to(dt).requires_grad_()
-        gf, gw = torch.autograd.grad((composition(f, nbr, w) * G.cpu().to(dt)).sum(), (f, w))
+        gf, gw = torch.autograd.grad((su.composition(f, nbr, w) * G.cpu().to(dt)).sum(), (f, w))
         scattered = np.zeros((len(kept), 3), gf.numpy().dtype)          # features = cat(outs)[rep]: row r's gradient goes to point rep[r]
         scattered[rep] = gf.numpy()
         twins[dt] = (scattered, gw.numpy())
-    _hold("link d outs", flat, twins[torch.float32][0], twins[torch.float64][0])
-    _hold("link d stem kernel", dkernel.cpu().numpy(), twins[torch.float32][1], twins[torch.float64][1])
+    su.hold("link d outs", flat, twins[torch.float32][0], twins[torch.float64][0])
+    su.hold("link d stem kernel", dkernel.cpu().numpy(), twins[torch.float32][1], twins[torch.float64][1])
     assert sum(g is not None and float(g.abs().max()) > 0 and bool(torch.isfinite(g).all()) for g in dprm) > 20      # it reaches the neck

@@ -1,6 +1,6 @@
 """The norm kernels on the voxel rows (proxytransformation_amd/sparse.py, csrc/sparse_norm.hip): instance norm and training batch norm,
 forward and backward, against the float64 restatement ``sparse_norm_host`` / ``sparse_norm_bwd_host`` under the rule of the
-convolution's tests (``_hold``: at most 8 x the error of the same fp32 chain on the CPU, which itself must be below 1e-5).
+convolution's tests (``sparse_util.hold``: at most 8 x the error of the same fp32 chain on the CPU, which itself must be below 1e-5).
 
 Segments of 256, 257, 0, 1 and 1000 rows (1514 in all): a full tile, a tile plus one row, an empty segment, a single row and a
 partial last tile; widths 64 and 512.  The conditioning case puts the columns at +-16 with unit spread: the fp32 two-pass restatement
@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from proxytransformation_amd import sparse
-from tests.test_gpu_sparse_conv import _hold
+from tests import sparse_util as su
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +52,7 @@ def test_conditioning_columns_far_from_zero(C):
     ops = _data(C, 16)
     got, stats = sparse.sparse_segment_norm(t(ops["x"]), SEGMENTS, EPS, return_stats=True)
     r32, r64 = _refs(ops, SEGMENTS, EPS)
-    _hold(f"norm conditioning C={C}", got.cpu().numpy(), r32, r64)
+    su.hold(f"norm conditioning C={C}", got.cpu().numpy(), r32, r64)
     _, s64 = sparse.sparse_norm_host(ops["x"].astype(np.float64), SEGMENTS, EPS, return_stats=True)
     stats = stats.cpu().numpy()
     for s in (0, 1, 4):                                      # the statistics themselves, to a few fp32 ulps of their size
@@ -73,18 +73,18 @@ def test_affine_residual_relu_and_the_edge_segments(C):
     assert got.dtype == torch.float32 and got.shape == (N, C)
     assert torch.equal(got, again) and torch.equal(stats, stats2), "two calls on the same inputs differ"
     r32, r64 = _refs(ops, SEGMENTS, EPS, use, True)
-    _hold(f"norm affine+residual+relu C={C}", got.cpu().numpy(), r32, r64)
+    su.hold(f"norm affine+residual+relu C={C}", got.cpu().numpy(), r32, r64)
     assert float(got.min()) == 0.0
     plain, _ = call(False)
     r32, r64 = _refs(ops, SEGMENTS, EPS, use, False)
-    _hold(f"norm affine+residual C={C}", plain.cpu().numpy(), r32, r64)
+    su.hold(f"norm affine+residual C={C}", plain.cpu().numpy(), r32, r64)
     stats = stats.cpu().numpy()
     assert stats.shape == (5, 2, C) and np.array_equal(stats[2], np.zeros((2, C), np.float32))
     assert np.array_equal(plain.cpu().numpy()[513], ops["bias"] + ops["residual"][513])
     assert np.array_equal(stats[3, 0], ops["x"][513])
     bare = sparse.sparse_instance_norm(t(ops["x"]), SEGMENTS)
     r32, r64 = _refs(ops, SEGMENTS, EPS)
-    _hold(f"instance norm C={C}", bare.cpu().numpy(), r32, r64)
+    su.hold(f"instance norm C={C}", bare.cpu().numpy(), r32, r64)
     mod = sparse.SparseInstanceNorm(C).to(DEV)
     with torch.no_grad():
         assert torch.equal(mod(t(ops["x"]), SEGMENTS), bare)  # weight 1, bias 0: x * 1 + 0
@@ -117,9 +117,9 @@ def test_training_batch_norm_two_steps_against_torch(C):
             ref64 = bn64(torch.from_numpy(x).double()).numpy()
             ref32 = bn32(torch.from_numpy(x)).numpy()
             got = sparse.sparse_batch_norm(t(x), gpu)
-        _hold(f"batch norm C={C} step {step} out", got.cpu().numpy(), ref32, ref64)
-        _hold(f"batch norm C={C} step {step} running_mean", gpu.running_mean.cpu().numpy(), bn32.running_mean.numpy(), bn64.running_mean.numpy())
-        _hold(f"batch norm C={C} step {step} running_var", gpu.running_var.cpu().numpy(), bn32.running_var.numpy(), bn64.running_var.numpy())
+        su.hold(f"batch norm C={C} step {step} out", got.cpu().numpy(), ref32, ref64)
+        su.hold(f"batch norm C={C} step {step} running_mean", gpu.running_mean.cpu().numpy(), bn32.running_mean.numpy(), bn64.running_mean.numpy())
+        su.hold(f"batch norm C={C} step {step} running_var", gpu.running_var.cpu().numpy(), bn32.running_var.numpy(), bn64.running_var.numpy())
         assert int(gpu.num_batches_tracked) == step + 1
     version = gpu.running_var._version
     with torch.no_grad():
@@ -127,7 +127,7 @@ def test_training_batch_norm_two_steps_against_torch(C):
         want = bn32.eval()(torch.from_numpy(ops["x"])).numpy()
         ref64 = bn64.eval()(torch.from_numpy(ops["x"]).double()).numpy()
         got = sparse.sparse_batch_norm(x, gpu.eval())           # eval: the affine map from the running statistics
-        _hold(f"batch norm C={C} eval", got.cpu().numpy(), want, ref64)
+        su.hold(f"batch norm C={C} eval", got.cpu().numpy(), want, ref64)
         assert gpu.running_var._version == version and int(gpu.num_batches_tracked) == 2
         scale, shift = sparse.bn_fold(gpu)
         assert sparse.bn_fold(gpu)[0] is scale                # cached
@@ -147,7 +147,7 @@ def _hold_grads(name, got, ops, ends, eps, out, relu, weight=True):
     r32 = sparse.sparse_norm_bwd_host(ops["g"], ops["x"], ends, eps, ops["weight"] if weight else None, **kw)
     for k, v in got.items():
         assert v.shape == r64[k].shape and v.dtype == np.float32, k
-        _hold(f"{name} {k}", v, r32[k], r64[k])
+        su.hold(f"{name} {k}", v, r32[k], r64[k])
 
 
 @pytest.mark.parametrize("C", [64, 512])

@@ -5,7 +5,6 @@ reference's names and shapes; ``forward_host`` on the rows of the convolution's 
 import ctypes
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from proxytransformation_amd import MODELS, REGISTRY_BACKEND, MinkResNet, _abi, backbone, sparse
-from tests.test_gpu_sparse_conv import _rows
+from tests import sparse_util as su
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NORM_ENTRY_POINTS = ("ptx_sparse_norm_workspace_bytes", "ptx_sparse_norm_fwd", "ptx_sparse_norm_apply", "ptx_sparse_norm_bwd")
@@ -142,7 +141,7 @@ def test_batchnorm_environment_switch(monkeypatch):
 
 
 def test_forward_host_levels():
-    rows, ends = _rows(1)
+    rows, ends = su.rows(1)
     torch.manual_seed(0)
     m = MinkResNet(18, 3).eval()
     feats = np.random.default_rng(4).standard_normal((rows.shape[0], 3))
@@ -168,20 +167,10 @@ def test_forward_host_levels():
 
 # ------------------------------------------------------------------------------------------------------------------ ABI surface
 def test_header_binding_and_exports_declare_the_norm_entry_points():
-    src = open(os.path.join(ROOT, "include", "proxyt.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    exports = open(os.path.join(ROOT, "proxytransformation_amd", "csrc", "exports.map")).read()
-    patterns = re.findall(r"global:\s*([^;]+);", exports)
-    assert patterns
     lib = _abi.lib()
     hooks = ctypes.CDLL(os.path.join(ROOT, "proxytransformation_amd", "libproxyt_hip_testhooks.so"))
-    for name in NORM_ENTRY_POINTS:
-        m = re.search(r"PTX_API\s+\w+\s+" + name + r"\s*\(([^;]*)\)\s*;", code)
-        assert m, name
-        assert name in _abi.SIGNATURES, name
-        assert len(m.group(1).split(",")) == len(_abi.SIGNATURES[name][1]), name
-        assert any(re.fullmatch(p.strip().replace("*", ".*"), name) for p in patterns), name
-        getattr(lib, name)
+    for name, params in su.assert_declared(NORM_ENTRY_POINTS).items():
+        assert len(params.split(",")) == len(_abi.SIGNATURES[name][1]), name
         getattr(hooks, name)
     assert _abi.ABI_VERSION == 13 and lib.ptx_abi_version() == 13 and hooks.ptx_abi_version() == 13
     assert "sparse_norm.hip" in open(os.path.join(ROOT, "proxytransformation_amd", "csrc", "Makefile")).read()

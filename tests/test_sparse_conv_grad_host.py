@@ -2,50 +2,16 @@
 ``sparse_conv3d_bwd_host`` / ``sparse_max_pool3d_bwd_host`` / ``kernel_map_transpose_host`` in float64 against torch-CPU float64 AUTOGRAD
 of the composition written out here independently (27 x ``index_select`` + ``mm``, resp. dense ``F.conv3d`` on the densified grid), the
 smallest-``j`` tie rule of the pool, and the ABI / opt-in surface of the new entry points."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from proxytransformation_amd import _abi, sparse
+from tests import sparse_util as su
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BWD_ENTRY_POINTS = ("ptx_sparse_kernel_map_transpose", "ptx_sparse_conv3d_bwd_workspace_bytes", "ptx_sparse_conv3d_bwd",
                     "ptx_sparse_max_pool3d_arg", "ptx_sparse_max_pool3d_bwd")
-
-
-def _rows(seed, ts, counts=(230, 120), lo=-4, hi=4):
-    """Distinct voxel rows of ``len(counts)`` scenes, coordinates in [lo, hi) * ts (negative and positive), in random order."""
-    rng = np.random.default_rng(seed)
-    cells = np.stack(np.meshgrid(*[np.arange(lo, hi)] * 3, indexing="ij"), -1).reshape(-1, 3)
-    rows, ends = [], []
-    for b, n in enumerate(counts):
-        pick = cells[rng.permutation(len(cells))[:n]] * ts
-        rows.append(np.concatenate([np.full((n, 1), b), pick], 1))
-        ends.append((ends[-1] if ends else 0) + n)
-    return np.concatenate(rows).astype(np.int32), ends
-
-
-def composition(feats, nbr, weight, bias=None, scale=None, shift=None, residual=None, relu=False):
-    """The layer as a user could write it from ``nbr`` in plain torch: out = sum_j index_select(feats, nbr_j) @ W_j (missing rows
-    masked), + bias, * scale + shift, + residual, ReLU.  Differentiable by autograd."""
-    nbr = torch.as_tensor(nbr).long()
-    out = feats.new_zeros((nbr.shape[0], weight.shape[2]))
-    for j in range(nbr.shape[1]):
-        present = (nbr[:, j] >= 0).to(feats.dtype).unsqueeze(1)
-        out = out + (feats.index_select(0, nbr[:, j].clamp(min=0)) * present) @ weight[j]
-    if bias is not None:
-        out = out + bias.reshape(1, -1)
-    if scale is not None:
-        out = out * scale.reshape(1, -1)
-    if shift is not None:
-        out = out + shift.reshape(1, -1)
-    if residual is not None:
-        out = out + residual
-    return torch.relu(out) if relu else out
 
 
 def _close(got, ref):
@@ -57,7 +23,7 @@ def _close(got, ref):
 @pytest.mark.parametrize("k,s", [(3, 1), (3, 2), (1, 2), (2, 2)])
 def test_conv_backward_restatement_equals_autograd_of_the_composition(k, s):
     ts, cin, cout = 4, 8, 12
-    coords, ends = _rows(21 + k + s, ts)
+    coords, ends = su.random_rows(21 + k + s, ts)
     _, _, nbr = sparse.kernel_map_host(coords, ends, ts, k, s)
     rng = np.random.default_rng(3)
     t = lambda a: torch.from_numpy(a).requires_grad_()       # noqa: E731
@@ -67,7 +33,7 @@ def test_conv_backward_restatement_equals_autograd_of_the_composition(k, s):
     G = rng.standard_normal((nbr.shape[0], cout))
     for full in (True, False):                               # the whole epilogue with ReLU, and the bare convolution
         kw = dict(bias=bias, scale=scale, shift=shift, residual=residual, relu=True) if full else {}
-        out = composition(feats, nbr, weight, **kw)
+        out = su.composition(feats, nbr, weight, **kw)
         wrt = (feats, weight, bias, residual) if full else (feats, weight)
         grads = torch.autograd.grad((out * torch.from_numpy(G)).sum(), wrt)
         got = sparse.sparse_conv3d_bwd_host(G, feats.detach().numpy(), nbr, weight.detach().numpy(), out=out.detach().numpy() if full else None,
@@ -86,7 +52,7 @@ def test_conv_backward_restatement_equals_autograd_of_the_composition(k, s):
 
 def test_conv_backward_restatement_equals_dense_conv3d_autograd():
     k, s, ts, cin, cout = 3, 1, 4, 6, 10
-    coords, ends = _rows(14, ts)
+    coords, ends = su.random_rows(14, ts)
     out_c, out_ends, nbr = sparse.kernel_map_host(coords, ends, ts, k, s)
     rng = np.random.default_rng(8)
     feats = rng.standard_normal((coords.shape[0], cin))
@@ -116,7 +82,7 @@ def test_conv_backward_restatement_equals_dense_conv3d_autograd():
 @pytest.mark.parametrize("k,s", [(2, 2), (3, 1)])
 def test_pool_backward_restatement_equals_autograd_of_the_stacked_max(k, s):
     ts = 4
-    coords, ends = _rows(5, ts)
+    coords, ends = su.random_rows(5, ts)
     _, _, nbr = sparse.kernel_map_host(coords, ends, ts, k, s)
     rng = np.random.default_rng(2)
     feats = rng.standard_normal((coords.shape[0], 8))         # continuous draws: no ties
@@ -147,7 +113,7 @@ def test_pool_backward_ties_go_to_the_smallest_offset():
 @pytest.mark.parametrize("k,s", [(3, 1), (3, 2), (1, 2), (2, 2)])
 def test_transposed_map_inverts_the_map(k, s):
     ts = 2
-    coords, ends = _rows(9, ts, counts=(200, 1, 90))
+    coords, ends = su.random_rows(9, ts, counts=(200, 1, 90))
     _, _, nbr = sparse.kernel_map_host(coords, ends, ts, k, s)
     n_in = coords.shape[0]
     nbr_t = sparse.kernel_map_transpose_host(nbr, n_in)
@@ -162,17 +128,8 @@ def test_transposed_map_inverts_the_map(k, s):
 
 
 def test_header_binding_and_exports_declare_the_backward_entry_points():
-    src = open(os.path.join(ROOT, "include", "proxyt.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    exports = open(os.path.join(ROOT, "proxytransformation_amd", "csrc", "exports.map")).read()
-    patterns = re.findall(r"global:\s*([^;]+);", exports)
-    assert patterns
+    su.assert_declared(BWD_ENTRY_POINTS)
     lib = _abi.lib()
-    for name in BWD_ENTRY_POINTS:
-        assert re.search(r"PTX_API\s+\w+\s+" + name + r"\s*\(", code), name
-        assert name in _abi.SIGNATURES, name
-        assert any(re.fullmatch(p.strip().replace("*", ".*"), name) for p in patterns), name
-        getattr(lib, name)
     assert _abi.ABI_VERSION == 13 and lib.ptx_abi_version() == 13
     assert len(_abi.SIGNATURES["ptx_sparse_conv3d_bwd"][1]) == 21 and len(_abi.SIGNATURES["ptx_sparse_kernel_map_transpose"][1]) == 6
     ws = lib.ptx_sparse_conv3d_bwd_workspace_bytes

@@ -2,7 +2,6 @@
 ``kernel_map_host`` / ``sparse_conv3d_host`` / ``sparse_max_pool3d_host`` against dense ``F.conv3d`` / ``F.max_pool3d`` on the densified
 grid in float64, the stride-2 output rows against the coarsening rule, and the ABI / nn.Module surface of the new entry points."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -10,21 +9,10 @@ import torch
 import torch.nn.functional as F
 
 from proxytransformation_amd import _abi, sparse
+from tests import sparse_util as su
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_ENTRY_POINTS = ("ptx_sparse_kernel_map_workspace_bytes", "ptx_sparse_kernel_map", "ptx_sparse_conv3d", "ptx_sparse_max_pool3d")
-
-
-def _rows(seed, ts, counts=(230, 120), lo=-4, hi=4):
-    """Distinct voxel rows of ``len(counts)`` scenes, coordinates in [lo, hi) * ts (negative and positive), in random order."""
-    rng = np.random.default_rng(seed)
-    cells = np.stack(np.meshgrid(*[np.arange(lo, hi)] * 3, indexing="ij"), -1).reshape(-1, 3)
-    rows, ends = [], []
-    for b, n in enumerate(counts):
-        pick = cells[rng.permutation(len(cells))[:n]] * ts
-        rows.append(np.concatenate([np.full((n, 1), b), pick], 1))
-        ends.append((ends[-1] if ends else 0) + n)
-    return np.concatenate(rows).astype(np.int32), ends
 
 
 def _densify(c3, feats, origin, ts, size, fill=0.0):
@@ -44,7 +32,7 @@ def _dense_weight(weight, k):
 
 @pytest.mark.parametrize("k,s,ts,cin,cout", [(3, 2, 1, 3, 64), (3, 1, 4, 64, 64), (1, 2, 4, 64, 128), (3, 2, 4, 64, 128), (3, 1, 8, 512, 512)])
 def test_restatement_equals_dense_conv3d(k, s, ts, cin, cout):
-    coords, ends = _rows(11 + k + s + ts, ts, counts=(230, 120) if cin < 512 else (150,))
+    coords, ends = su.random_rows(11 + k + s + ts, ts, counts=(230, 120) if cin < 512 else (150,))
     rng = np.random.default_rng(5)
     feats = rng.standard_normal((coords.shape[0], cin))
     weight = rng.standard_normal((k ** 3, cin, cout)) / np.sqrt(k ** 3 * cin)
@@ -67,7 +55,7 @@ def test_restatement_equals_dense_conv3d(k, s, ts, cin, cout):
 
 def test_restatement_equals_dense_max_pool():
     ts = 4
-    coords, ends = _rows(3, ts)
+    coords, ends = su.random_rows(3, ts)
     feats = np.random.default_rng(1).standard_normal((coords.shape[0], 8))
     out_c, out_ends, nbr = sparse.kernel_map_host(coords, ends, ts, 2, 2)
     got = sparse.sparse_max_pool3d_host(feats, nbr)
@@ -84,7 +72,7 @@ def test_restatement_equals_dense_max_pool():
 @pytest.mark.parametrize("ts", [1, 4])
 def test_stride2_rows_are_the_coarsening_rule(ts):
     """floor (not truncation: negative coordinates), first occurrence, row for row."""
-    coords, ends = _rows(7, ts, counts=(200, 1, 90), lo=-5, hi=3)
+    coords, ends = su.random_rows(7, ts, counts=(200, 1, 90), lo=-5, hi=3)
     out_c, out_ends, nbr = sparse.kernel_map_host(coords, ends, ts, 3, 2)
     want, want_ends, lo = [], [], 0
     for b, e in enumerate(ends):
@@ -112,19 +100,14 @@ def test_kernel_offsets_order():
 
 
 def test_header_and_binding_declare_the_entry_points():
+    su.assert_declared(NEW_ENTRY_POINTS)
     src = open(os.path.join(ROOT, "include", "proxyt.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    for name in NEW_ENTRY_POINTS:
-        assert re.search(r"PTX_API\s+\w+\s+" + name + r"\s*\(", code), name
-        assert name in _abi.SIGNATURES, name
     section = src[src.index("sparse 3D convolution on the voxel rows"):src.index("image feature -> point sampling")]
     for ref in ("DET:398", "mink_resnet.py:58-63", "mink_resnet.py:67-69", "mink_resnet.py:103-109"):
         assert ref in section, ref
     assert len(_abi.SIGNATURES["ptx_sparse_kernel_map"][1]) == 13 and len(_abi.SIGNATURES["ptx_sparse_conv3d"][1]) == 15
     assert len(_abi.SIGNATURES["ptx_sparse_max_pool3d"][1]) == 7
     lib = _abi.lib()
-    for name in NEW_ENTRY_POINTS:
-        getattr(lib, name)
     assert lib.ptx_sparse_kernel_map_workspace_bytes(4, 4096) >= 2 * lib.ptx_voxel_workspace_bytes(4, 4096)
     assert lib.ptx_sparse_kernel_map_workspace_bytes(65, 16) == 0
 

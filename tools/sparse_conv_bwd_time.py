@@ -38,10 +38,6 @@ from sparse_conv_time import B, N, PEAK_TF, VOXEL, alternate, block_us, offset_l
 
 
 # ---------------------------------------------------------------------------------------------------------------- summation model
-def _rel(a, ref):
-    return float(np.abs(a.astype(np.float64) - ref).max() / np.abs(ref).max())
-
-
 def _chain(A, Bm):
     """(p, M), (p, N): the sum over p of the outer products, one after the other in fp32, from zero."""
     acc = np.zeros((A.shape[1], Bm.shape[1]), np.float32)
@@ -85,7 +81,7 @@ def model_dbias(gz):
 
 def model_lines():
     from proxytransformation_amd import sparse
-    from tests.test_gpu_sparse_conv import _host_map, _operands, _rows
+    from tests.sparse_util import host_map as _host_map, operands as _operands, rel as _rel, rows as _rows
     lines = ["fp32 numpy model of the kernels' summation order at the shapes of tests/test_gpu_sparse_conv_grad.py (CPU): error against the "
              "float64 restatement as a ratio to the BLAS-fp32 restatement's (the test's yardstick; the bar is 8)"]
     for cin, cout, k, s in [(64, 64, 3, 1), (64, 128, 3, 2), (128, 256, 1, 2)]:

@@ -20,37 +20,9 @@
 
 #include "common.h"
 #include "split3.h"
+#include "train_rules.h"
 
 namespace ptx {
-
-// ------------------------------------------------------------------------------ dropout sites
-// keep(seed, i) is train_ops.hip's k_dropout: the masks of a (seed, element) pair are the same in both files
-__device__ __forceinline__ uint32_t tf_mix32(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return (uint32_t)((x ^ (x >> 31)) >> 32);
-}
-struct Drop1 { uint64_t seed; uint32_t thresh; float ks; int on; };
-static Drop1 make_drop(float p, uint64_t seed)
-{
-    Drop1 d;
-    d.on = p > 0.0f ? 1 : 0; d.seed = seed * 0x100000001B3ull;
-    d.thresh = (uint32_t)((double)p * 4294967296.0); d.ks = 1.0f / (1.0f - p);
-    return d;
-}
-__device__ __forceinline__ float drop_apply(const Drop1 &d, float v, uint64_t i)
-{
-    if (!d.on) return v;
-    return tf_mix32(d.seed + i) >= d.thresh ? v * d.ks : 0.0f;
-}
-__device__ __forceinline__ float tf_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float tf_gelu_g(float x)
-{
-    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-    return cdf + x * 0.3989422804014327f * expf(-0.5f * x * x);
-}
 
 constexpr int kRowsPerChunk = 8;       // rows of one work-group in the backward row kernels (4 waves x 2 rows: ~R / 8 work-groups
                                        // fill the chip; 16 rows left these passes latency-bound at 260 work-groups, r04)
@@ -109,8 +81,8 @@ __global__ __launch_bounds__(256) void k_t_gelu_drop(const float *__restrict__ x
     for (long i = blockIdx.x * 256l + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 v = reinterpret_cast<const float4 *>(x)[i];
         float4 o;
-        o.x = drop_apply(d, tf_gelu(v.x), 4 * i); o.y = drop_apply(d, tf_gelu(v.y), 4 * i + 1);
-        o.z = drop_apply(d, tf_gelu(v.z), 4 * i + 2); o.w = drop_apply(d, tf_gelu(v.w), 4 * i + 3);
+        o.x = drop_apply(d, gelu_exact(v.x), 4 * i); o.y = drop_apply(d, gelu_exact(v.y), 4 * i + 1);
+        o.z = drop_apply(d, gelu_exact(v.z), 4 * i + 2); o.w = drop_apply(d, gelu_exact(v.w), 4 * i + 3);
         reinterpret_cast<float4 *>(y)[i] = o;
     }
 }
@@ -427,10 +399,10 @@ __global__ __launch_bounds__(256) void k_t_gelu_bwd(const float *__restrict__ hp
                 if (g < ng) {
                     const size_t i = base + 256 * g + 4 * lane;
                     float4 o;
-                    o.x = drop_apply(d, dv[g].x, i) * tf_gelu_g(hv[g].x);
-                    o.y = drop_apply(d, dv[g].y, i + 1) * tf_gelu_g(hv[g].y);
-                    o.z = drop_apply(d, dv[g].z, i + 2) * tf_gelu_g(hv[g].z);
-                    o.w = drop_apply(d, dv[g].w, i + 3) * tf_gelu_g(hv[g].w);
+                    o.x = drop_apply(d, dv[g].x, i) * gelu_exact_g(hv[g].x);
+                    o.y = drop_apply(d, dv[g].y, i + 1) * gelu_exact_g(hv[g].y);
+                    o.z = drop_apply(d, dv[g].z, i + 2) * gelu_exact_g(hv[g].z);
+                    o.w = drop_apply(d, dv[g].w, i + 3) * gelu_exact_g(hv[g].w);
                     *reinterpret_cast<float4 *>(dhpre + i) = o;
                     acc[g][0] += o.x; acc[g][1] += o.y; acc[g][2] += o.z; acc[g][3] += o.w;
                 }
@@ -455,7 +427,7 @@ __global__ __launch_bounds__(256) void k_t_gelu_bwd(const float *__restrict__ hp
         for (int q = 0; q < kMaxQH; ++q) {
             if (q < nq) {
                 const size_t i = base + lane + 64 * q;
-                const float v = drop_apply(d, dhact[i], i) * tf_gelu_g(hpre[i]);
+                const float v = drop_apply(d, dhact[i], i) * gelu_exact_g(hpre[i]);
                 dhpre[i] = v; acc[0][q] += v;
             }
         }

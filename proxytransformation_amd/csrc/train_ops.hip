@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "imgstore.h"
+#include "train_rules.h"
 
 namespace ptx {
 
@@ -325,14 +326,8 @@ __global__ __launch_bounds__(256) void k_colsum_fin(const double *__restrict__ p
 }
 
 // ------------------------------------------------------------------------------ element-wise family
-// op 0: y = a + b              1: y = a * s          2: y = gelu_erf(a)         3: y = b * gelu'(a)  (a = pre-activation, b = dy)
+// op 0: y = a + b              1: y = a * s          2: y = gelu_exact(a)       3: y = b * gelu'(a)  (a = pre-activation, b = dy)
 //    4: y = relu(a)            5: y = b * (a > 0)    6: y = a + bias[col]       7: y = a + s * b       8: y = a * b
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float gelu_g(float x)
-{
-    const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
-    return cdf + x * 0.3989422804014327f * expf(-0.5f * x * x);
-}
 __global__ void k_eltwise(int op, const float *__restrict__ a, const float *__restrict__ b, float s, long n, int ncol,
                           float *__restrict__ y)
 {
@@ -342,8 +337,8 @@ __global__ void k_eltwise(int op, const float *__restrict__ a, const float *__re
         switch (op) {
             case 0: v = av + b[i]; break;
             case 1: v = av * s; break;
-            case 2: v = gelu_f(av); break;
-            case 3: v = b[i] * gelu_g(av); break;
+            case 2: v = gelu_exact(av); break;
+            case 3: v = b[i] * gelu_exact_g(av); break;
             case 4: v = fmaxf(av, 0.0f); break;
             case 5: v = av > 0.0f ? b[i] : 0.0f; break;
             case 6: v = av + b[i % ncol]; break;
@@ -354,23 +349,14 @@ __global__ void k_eltwise(int op, const float *__restrict__ a, const float *__re
     }
 }
 
-// Dropout / DropPath with a counter-based generator: element i of stream `seed` is kept iff hash(seed, i >> shift) maps
-// above p; kept values are scaled by 1 / (1 - p).  The mask is a pure function of (seed, index): the backward pass
-// recomputes it (same kernel, dy in place of x).  shift groups elements that share one decision (DropPath: one per
-// sample, PRE:268 -> group = elements per sample; a non-power-of-two group is passed as `group`).
-__device__ __forceinline__ uint32_t mix32(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return (uint32_t)((x ^ (x >> 31)) >> 32);
-}
+// Dropout / DropPath by the rule of train_rules.h: element i of stream `seed` shares the decision of index i / group (DropPath: one
+// per sample, PRE:268 -> group = elements per sample).  The backward pass is the same kernel with dy in place of x.
 __global__ void k_dropout(const float *__restrict__ x, long n, long group, float p, uint64_t seed, float *__restrict__ y)
 {
-    const float keep_scale = 1.0f / (1.0f - p);
-    const uint32_t thresh = (uint32_t)((double)p * 4294967296.0);
+    const float keep_scale = drop_keep_scale(p);
+    const uint32_t thresh = drop_thresh(p);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const uint32_t r = mix32(seed * 0x100000001B3ull + (uint64_t)(i / group));
+        const uint32_t r = drop_mix32(drop_stream(seed) + (uint64_t)(i / group));
         y[i] = r >= thresh ? x[i] * keep_scale : 0.0f;
     }
 }

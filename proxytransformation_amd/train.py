@@ -20,6 +20,12 @@ How this file is built:
 * gradients of ``pt_replace`` follow ``index_put_``'s backward (PRE:495): every valid slot whose target point survives
   the drop receives that point's output gradient, duplicates included.
 
+The step exists in three forms, held to the same fixtures by tests/test_gpu_train.py: ``_TrainStepC`` (the default: one autograd
+node, one library call per direction), ``_TrainStep`` (the same node with its two bodies in Python) and the per-operator graph of
+``forward_train`` (the fallback for shapes outside the fused kernels' range).  What the two Python forms have in common -- the index
+half, the side-stream prologue of the image branch, the ``aux`` dict -- is written once (``_index_*``, ``_on_side``, ``_aux``);
+``_aux_shapes`` and ``_fill_block`` serve the C step as well.
+
 Dropout masks come from a counter-based hash of (seed, call, site, element); torch's Philox stream is not reproduced
 (not reproducible across devices anyway).  With all three rates at 0 the pass is deterministic and is
 checked against gradients captured from the reference itself (tests/golden/g4_train.npz).
@@ -28,6 +34,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
@@ -35,8 +42,8 @@ import torch
 from . import _abi
 
 _F32 = torch.float32
-# test switches: the generic one-launch-per-operator composition stays available (shapes outside the fused kernels' range use it)
-# Which form of the step runs (module constants, not environment switches: tests/test_gpu_train.py patches them to drive the fallbacks).
+# Which form of the step runs (module constants, not environment switches: tests/test_gpu_train.py and tests/test_gpu_ddp.py patch them
+# to drive the fallbacks; the one-launch-per-operator composition is also what shapes outside the fused kernels' range use).
 _FUSED_ATTN = True       # the fused attention core of a block (ptx_train_attn_fwd / _bwd) instead of one launch per operator
 _FUSED_BLOCK = True      # one ProxyBlock + trailing LayerNorm + head + BatchNorm1d as two C calls (ptx_train_block_fwd / _bwd)
 _FUSED_IMG = True        # AttentionPool2d on its folded form (ptx_train_imgpool_fwd / _bwd)
@@ -44,18 +51,8 @@ _SIDE_STREAM = True      # the image branch on a side stream beside the index ha
 _BLOCKS_APART = True     # one-node step: the image block on the side stream too, beside the text block (forward and backward)
 _ONE_NODE = True         # the float half as ONE autograd node (_TrainStep)
 _C_STEP = True           # r06: the one node's two bodies behind ONE library call each (ptx_train_step_fwd / _bwd, csrc/train_step.hip)
-_IMG_FIRST = True        # one-node step: the image branch enqueued in front of the clustering half (profiles/r04_train_ab.txt)
-_IMG_POS = 1             # per-operator graph: where the image branch is enqueued -- 0 first, 1 after the selection, 2 before the
-                         # text block, 3 after it
-
-
-_TICKS = None          # scratch/train_hostprof3.py: list of (label, perf_counter) of the last forward
-
-
-def _tick(label):
-    if _TICKS is not None:
-        import time
-        _TICKS.append((label, time.perf_counter()))
+# Where the image branch is enqueued is fixed (profiles/r04_train_ab.txt measured the alternatives): the one-node step enqueues it first,
+# the per-operator graph right after the cluster selection.
 
 
 def _side_stream(mod, dev):
@@ -832,16 +829,9 @@ class _BlockFused(torch.autograd.Function):
         lib = _abi.lib()
         x, proxy = _c(x), _c(proxy)
         a = _abi.PtxTrainBlock()
-        (a.B, a.n, a.L, a.C, a.H, a.heads, a.s, a.nout, a.eps1, a.eps2, a.eps3, a.bn_eps, a.bn_momentum, a.p_attn, a.p_drop,
-         a.p_path, seeds) = cfg[:17]
-        a.compute_dtype = cfg[17] if len(cfg) > 17 else 0
-        for i, sd in enumerate(seeds):
-            a.seed[i] = sd & 0xFFFFFFFFFFFFFFFF
         a.x, a.proxy, a.mask = _p(x), _p(proxy), _p(mask)
         params = tuple(None if t is None else _c(t) for t in params)
-        for i, t in enumerate(params):
-            a.param[i] = _p(t)
-        a.bn_run_mean, a.bn_run_var = _p(run_mean), _p(run_var)
+        _fill_block(a, cfg, params, run_mean, run_var)
         s0, s1, s2 = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
         _ck(lib.ptx_train_block_sizes(ctypes.byref(a), ctypes.byref(s0), ctypes.byref(s1), ctypes.byref(s2)), "ptx_train_block_sizes")
         sz = (s0.value, s1.value, s2.value)
@@ -894,16 +884,36 @@ def _block_params(blk, out_norm, head, head_bn):
             head_bn.bias)
 
 
+# The scalar fields of PtxTrainBlock that _block_cfg decides, by their names in the struct; with "seeds" they are the keys of a block's cfg.
+_BLOCK_SCALARS = ("B", "n", "L", "C", "H", "heads", "s", "nout", "eps1", "eps2", "eps3", "bn_eps", "bn_momentum", "p_attn", "p_drop",
+                  "p_path", "compute_dtype")
+if not set(_BLOCK_SCALARS) < {f[0] for f in _abi.PtxTrainBlock._fields_}:          # setattr would quietly take a misspelt name
+    raise ImportError("train._BLOCK_SCALARS names a field that PtxTrainBlock does not have")
+
+
 def _block_cfg(mod, blk, out_norm, head, head_bn, B, n, L, seeds, mods=None, params=None):
-    """(cfg tuple, parameters in PTX_TB_* order) of one fused block call.  ``mods`` = (norm1, norm2) and ``params`` come from the
+    """(cfg dict, parameters in PTX_TB_* order) of one fused block call.  ``mods`` = (norm1, norm2) and ``params`` come from the
     module's per-weights cache in the one-node step (_static); the scalars are read from their owners on every call."""
     if params is None:
         params = _block_params(blk, out_norm, head, head_bn)
     n1, n2 = mods if mods is not None else (blk.norm1, blk.norm2)
-    cfg = (B, n, L, mod.embed_dim, params[13].shape[0], mod.num_heads, params[3].shape[2], params[19].shape[0],
-           n1.eps, n2.eps, out_norm.eps, head_bn.eps, head_bn.momentum, float(mod.attn_drop_rate),
-           float(mod.drop_rate), float(mod._dpr_last(blk)), tuple(seeds), 1 if getattr(mod, "compute_dtype", "fp32") == "bf16" else 0)
+    cfg = dict(B=B, n=n, L=L, C=mod.embed_dim, H=params[13].shape[0], heads=mod.num_heads, s=params[3].shape[2], nout=params[19].shape[0],
+               eps1=n1.eps, eps2=n2.eps, eps3=out_norm.eps, bn_eps=head_bn.eps, bn_momentum=head_bn.momentum,
+               p_attn=float(mod.attn_drop_rate), p_drop=float(mod.drop_rate), p_path=float(mod._dpr_last(blk)),
+               compute_dtype=1 if getattr(mod, "compute_dtype", "fp32") == "bf16" else 0, seeds=tuple(seeds))
     return cfg, params
+
+
+def _fill_block(a, cfg, params, run_mean, run_var):
+    """The step-independent half of a PtxTrainBlock: the scalars and seeds of ``cfg`` (_block_cfg), the parameter pointers (PTX_TB_*
+    order, contiguous tensors or None) and the running statistics of the head's BatchNorm."""
+    for k in _BLOCK_SCALARS:
+        setattr(a, k, cfg[k])
+    for i, sd in enumerate(cfg["seeds"]):
+        a.seed[i] = sd & 0xFFFFFFFFFFFFFFFF
+    for i, t in enumerate(params):
+        a.param[i] = _p(t)
+    a.bn_run_mean, a.bn_run_var = _p(run_mean), _p(run_var)
 
 
 def _static(mod):
@@ -966,17 +976,135 @@ def _block(mod, blk, out_norm, head, head_bn, xa, xb, proxy2d, mask_u8, B, n, L,
     return t
 
 
+# --------------------------------------------------------------------------- what the Python forms of the step share
+def _stack_points(points):
+    """The scenes as one (B,N,3) fp32 tensor (PRE:426-427; _check_inputs has already looked at the dtypes)."""
+    return torch.stack(points) if all([p.dtype == _F32 for p in points]) else torch.stack([p.to(_F32) for p in points])
+
+
+def _on_side(mod, dev, body):
+    """``body()`` -- the image branch -- on the module's side stream, behind what the caller's stream holds so far (on the caller's
+    stream itself with _SIDE_STREAM off); the result is made known to the caller's stream.  Returns (result, side, main)."""
+    main = torch.cuda.current_stream(dev)
+    side = _side_stream(mod, dev) if _SIDE_STREAM else None
+    if side is not None:
+        side.wait_stream(main)
+    with torch.cuda.stream(side if side is not None else main):
+        out = body()
+    if side is not None:
+        out.record_stream(main)
+    return out, side, main
+
+
+def _index_centres(mod, pts, st):
+    """Index half, part 1: grid centres + ball query #1 (PRE:55-56) of the scenes ``pts`` (B,N,3).  Returns minmax, c0, cl1."""
+    lib = _abi.lib()
+    dev = pts.device
+    B, N = pts.shape[0], pts.shape[1]
+    M, K = mod.num_cluster, mod.num_sub
+    i32 = dict(dtype=torch.int32, device=dev)
+    minmax = torch.empty((B, 2, 3), dtype=_F32, device=dev)
+    c0 = torch.empty((B, M, 3), dtype=_F32, device=dev)
+    lin = mod._train_lin(dev)
+    enc_scratch = torch.empty((max(B * 6, 64),), **i32)        # NOT the lane workspace: its encoded boxes must stay zero
+    _ck(lib.ptx_grid_centers(_p(pts), B, N, _p(lin), mod.grid_size, 4.0, _p(minmax), _p(c0), _p(enc_scratch),
+                             enc_scratch.numel() * 4, st), "ptx_grid_centers")
+    idx1 = torch.empty((B, M, K), **i32)
+    cl1 = torch.empty((B, M, K, 3), dtype=_F32, device=dev)
+    _ck(lib.ptx_ball_query(_p(c0), _p(pts), B, M, N, K, 3.0, _p(idx1), _p(cl1), None, st), "ptx_ball_query")
+    return minmax, c0, cl1
+
+
+def _index_select(mod, shape, pts, centers, order_override, st):
+    """Index half, part 2: ball query #2 around ``centers`` (detached, (B*M,3); the module's _centers_override replaces them) and the
+    cluster selection with its ownership tags (PRE:65, 352-420, 478-523).  Returns the record of index tensors."""
+    lib = _abi.lib()
+    dev = pts.device
+    B, N = pts.shape[0], pts.shape[1]
+    M, K, Mt, Mk = mod.num_cluster, mod.num_sub, shape.Mt, shape.Mk
+    Kd = Mt - Mk
+    i32 = dict(dtype=torch.int32, device=dev)
+    if mod._centers_override is not None:
+        centers = mod._centers_override.to(device=dev, dtype=_F32).reshape(B * M, 3).contiguous()
+    r = SimpleNamespace()
+    r.idx2 = torch.empty((B, M, K), **i32)
+    cl2 = torch.empty((B, M, K, 3), dtype=_F32, device=dev)
+    pad = torch.empty((B, M), **i32)
+    _ck(lib.ptx_ball_query(_p(centers), _p(pts), B, M, N, K, 3.0, _p(r.idx2), _p(cl2), _p(pad), st), "ptx_ball_query")
+    r.order = torch.empty((B, Mt), **i32)
+    picks = torch.empty((B, max(Kd, 1)), **i32)
+    r.keep = torch.empty((B, Mk), **i32)
+    kcenter_i = torch.empty((B, Mk, 3), dtype=_F32, device=dev)
+    r.kcluster = torch.empty((B, Mk, K, 3), dtype=_F32, device=dev)
+    r.kidx = torch.empty((B, Mk, K), **i32)
+    drop_idx = torch.empty((B, max(Kd, 1) * K), **i32)
+    r.tag = torch.empty((B, N), **i32)                      # every word is written by ptx_select_clusters
+    oo = None if order_override is None else order_override.to(device=dev, dtype=torch.int32).contiguous()
+    _ck(lib.ptx_select_clusters(ctypes.byref(shape), _p(r.idx2), _p(centers), _p(cl2), _p(pad), _p(oo), _p(r.order), _p(picks),
+                                _p(r.keep), _p(kcenter_i), _p(r.kcluster), _p(r.kidx), _p(drop_idx), _p(r.tag), st),
+        "ptx_select_clusters")
+    r.picks, r.drop_idx = picks[:, :Kd], drop_idx[:, : Kd * K]            # the Kd dropped clusters
+    return r
+
+
+def _pinned_counts(mod, B, st):
+    """The pinned words that receive the per-scene output counts, with the event behind their copy: one pair per (B, caller's stream)."""
+    if getattr(mod, "_train_pin", None) is None:
+        mod._train_pin = {}
+    pin = mod._train_pin.get((B, st))
+    if pin is None:
+        pin = mod._train_pin[(B, st)] = (torch.empty((B,), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+    return pin
+
+
+def _index_positions(mod, shape, r, st):
+    """Index half, part 3: output positions and the rows of the kept centres; adds ``opos``, ``src`` and ``pin`` to the record."""
+    lib = _abi.lib()
+    B, N = r.tag.shape
+    M, Mt, Mk = mod.num_cluster, shape.Mt, shape.Mk
+    i32 = dict(dtype=torch.int32, device=r.tag.device)
+    ntiles = (N + 2047) // 2048
+    tile_counts = torch.empty((B * ntiles,), **i32)
+    r.opos = torch.empty((B, N), **i32)
+    counts = torch.empty((B,), **i32)
+    _ck(lib.ptx_op_out_positions(_p(r.tag), B, N, _p(tile_counts), _p(r.opos), _p(counts), st), "ptx_op_out_positions")
+    # the list lengths of PRE:467 are known here: copy them out now and wait at the very end (_kept_counts), so that the host keeps
+    # enqueueing the float half while the index half runs (r04: a blocking read at the end idled the GPU across the forward / backward seam)
+    pin = r.pin = _pinned_counts(mod, B, st)
+    pin[1].synchronize()                                         # an earlier call's copy into the same pinned words
+    pin[0].copy_(counts, non_blocking=True)
+    pin[1].record()
+    r.src = torch.empty((B * Mk,), **i32)
+    _ck(lib.ptx_op_keep_rows(_p(r.order), _p(r.keep), B, M, Mt, Mk, _p(r.src), st), "ptx_op_keep_rows")
+
+
+def _kept_counts(r):
+    """The list lengths of PRE:467, awaited."""
+    r.pin[1].synchronize()
+    return r.pin[0].tolist()
+
+
+def _aux_shapes(B, N, M, K, Mt, Mk, C, V):
+    """The step's intermediates that forward_debug, return_transforms and the tests read: name -> (shape, dtype).  The ONE list of
+    their names: the Python forms fill it from their tensors (_aux), the C step from its arena (_Aux)."""
+    Kd, i32 = Mt - Mk, torch.int32
+    return dict(idx2=((B, M, K), i32), order=((B, Mt), i32), picks=((B, Kd), i32), keep=((B, Mk), i32), kidx=((B, Mk, K), i32),
+                drop_idx=((B, Kd * K), i32), centers=((B * M, 3), _F32), translate=((B * Mk, 3), _F32), transform=((B * Mk, 9), _F32),
+                point_proxy=((B * Mk, C), _F32), img_proxy=((B * V, C), _F32), kcenter=((B * Mk, 3), _F32), opos=((B, N), i32))
+
+
+def _aux(r, shapes, **floats):
+    """The aux dict of a Python form: the index tensors of the record ``r`` and the float tensors given by name."""
+    return {k: floats[k] if k in floats else getattr(r, k) for k in shapes}
+
+
 def forward_train(mod, points: List[torch.Tensor], text_feats, text_mask, img_feat, shape, ws, order_override=None):
     """Train-mode forward of ``mod`` (a ProxyTransformationNormReverse).  Returns (list of (N_i',3) tensors with
     grad_fn, dict of index tensors for tests)."""
-    lib = _abi.lib()
     dev = points[0].device
     st = _st()
-    _tick("enter")
     B, N = len(points), points[0].shape[0]
     M, K, Mt, Mk, C = mod.num_cluster, mod.num_sub, shape.Mt, shape.Mk, mod.embed_dim
-    Kd = Mt - Mk
-    i32 = dict(dtype=torch.int32, device=dev)
     mod._train_calls += 1
     seeds = site_seeds(torch.initial_seed(), mod._train_calls, mod._instance_salt)
     if _one_node_ok(mod, (B * img_feat.shape[1], mod.input_dim, mod.img_spacial_dim ** 2), Mk, text_feats.shape[1], img_feat.shape[1]):
@@ -990,106 +1118,44 @@ def forward_train(mod, points: List[torch.Tensor], text_feats, text_mask, img_fe
         n = len(res) - 3
         aux["kcenter"], aux["translate"], aux["transform"] = res[n:]
         return list(res[:n]), aux
-    pts = torch.stack([p.detach().to(_F32) for p in points]).contiguous()          # PRE:426-427
-
+    pts = _stack_points([p.detach() for p in points])
     V = img_feat.shape[1]
 
-    def _image_branch():
+    def image_branch():
         # ---- image branch (PRE:449-455), on a side stream: it depends on nothing before it, and the host is ahead of the GPU here
-        # (farthest point sampling keeps one work-group per scene busy for ~0.2 ms), so it overlaps the index half and the text
-        # block.  Autograd runs a node's backward on the stream of its forward and picks the most recently created ready node
-        # first: created HERE -- after the text block -- this chain's backward is enqueued right after the image block's and
-        # overlaps the text block's backward (created at the top of the forward it ran last, alone, for 0.5 ms)
-        V = img_feat.shape[1]
-        hw = mod.img_spacial_dim ** 2
+        # (farthest point sampling keeps one work-group per scene busy for ~0.2 ms), so it overlaps the rest of the index half and
+        # the text block.  Autograd runs a node's backward on the stream of its forward, so this chain's backward overlaps the
+        # text block's backward too
         ap = mod.attn_pool2d
-        img3 = _c(img_feat).view(B * V, mod.input_dim, hw)
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(mod, dev) if _SIDE_STREAM else None
-        if side is not None:
-            side.wait_stream(main)
-        with torch.cuda.stream(side if side is not None else main):
-            if _imgpool_ok(img3, C, mod.num_heads):
-                o = _ImgPool.apply(img3, mod.channel_mapper.weight, mod.channel_mapper.bias, ap.positional_embedding, ap.q_proj.weight,
-                                   ap.q_proj.bias, ap.k_proj.weight, ap.k_proj.bias, ap.v_proj.weight, ap.v_proj.bias, mod.num_heads)
-            else:
-                tok = _ImgTokens.apply(img3, mod.channel_mapper.weight, mod.channel_mapper.bias, ap.positional_embedding)
-                o = _AttnPoolCore.apply(tok, ap.q_proj.weight, ap.q_proj.bias, ap.k_proj.weight, ap.k_proj.bias, ap.v_proj.weight,
-                                        ap.v_proj.bias, mod.num_heads)
-            y = _Linear.apply(o, ap.c_proj.weight, ap.c_proj.bias)
-            img_proxy = _LayerNorm.apply(y, mod.norm_img.weight, mod.norm_img.bias, mod.norm_img.eps)       # (B*V, C)
-        if side is not None:
-            img_proxy.record_stream(main)
-        return img_proxy, side, main
+        if _imgpool_ok(img3, C, mod.num_heads):
+            o = _ImgPool.apply(img3, mod.channel_mapper.weight, mod.channel_mapper.bias, ap.positional_embedding, ap.q_proj.weight,
+                               ap.q_proj.bias, ap.k_proj.weight, ap.k_proj.bias, ap.v_proj.weight, ap.v_proj.bias, mod.num_heads)
+        else:
+            tok = _ImgTokens.apply(img3, mod.channel_mapper.weight, mod.channel_mapper.bias, ap.positional_embedding)
+            o = _AttnPoolCore.apply(tok, ap.q_proj.weight, ap.q_proj.bias, ap.k_proj.weight, ap.k_proj.bias, ap.v_proj.weight,
+                                    ap.v_proj.bias, mod.num_heads)
+        y = _Linear.apply(o, ap.c_proj.weight, ap.c_proj.bias)
+        return _LayerNorm.apply(y, mod.norm_img.weight, mod.norm_img.bias, mod.norm_img.eps)       # (B*V, C)
 
-    if _IMG_POS == 0:
-        img_proxy, side, main = _image_branch()
-    # ---- index half, part 1: grid centres + ball query #1 (PRE:55-56)
-    minmax = torch.empty((B, 2, 3), dtype=_F32, device=dev)
-    c0 = torch.empty((B, M, 3), dtype=_F32, device=dev)
-    lin = mod._train_lin(dev)
-    enc_scratch = torch.empty((max(B * 6, 64),), **i32)        # NOT the lane workspace: its encoded boxes must stay zero
-    _ck(lib.ptx_grid_centers(_p(pts), B, N, _p(lin), mod.grid_size, 4.0, _p(minmax), _p(c0), _p(enc_scratch),
-                             enc_scratch.numel() * 4, st), "ptx_grid_centers")
-    idx1 = torch.empty((B, M, K), **i32)
-    cl1 = torch.empty((B, M, K, 3), dtype=_F32, device=dev)
-    _ck(lib.ptx_ball_query(_p(c0), _p(pts), B, M, N, K, 3.0, _p(idx1), _p(cl1), None, st), "ptx_ball_query")
-
-    _tick("index1")
-    # ---- offset network (PRE:58-62)
+    # ---- index half, part 1 + offset network (PRE:55-62)
+    minmax, c0, cl1 = _index_centres(mod, pts, st)
     off = mod.get_deformable_cluster.get_offsets
     bn = off.mlp[1]
     pooled = _SlotNet.apply(c0.view(B * M, 3), cl1, off.mlp[0].weight, off.mlp[0].bias, bn.weight, bn.bias,
                             bn.running_mean, bn.running_var, bn.eps, bn.momentum, False)
     centers = _OffsetHead.apply(pooled, off.channel_mapper.weight, c0, minmax, M, 4.0)       # (B*M,3)
+    # ---- index half, parts 2 and 3, the image branch enqueued between them
+    r = _index_select(mod, shape, pts, centers.detach(), order_override, st)
+    img3 = _c(img_feat).view(B * V, mod.input_dim, mod.img_spacial_dim ** 2)
+    img_proxy, side, main = _on_side(mod, dev, image_branch)
+    _index_positions(mod, shape, r, st)
 
-    _tick("offset_net")
-    # ---- index half, part 2: ball query #2, selection, tags, output positions (PRE:65, 352-420, 478-523)
-    cdet = centers.detach()
-    if mod._centers_override is not None:
-        cdet = mod._centers_override.to(device=dev, dtype=_F32).reshape(B * M, 3).contiguous()
-    idx2 = torch.empty((B, M, K), **i32)
-    cl2 = torch.empty((B, M, K, 3), dtype=_F32, device=dev)
-    pad = torch.empty((B, M), **i32)
-    _ck(lib.ptx_ball_query(_p(cdet), _p(pts), B, M, N, K, 3.0, _p(idx2), _p(cl2), _p(pad), st), "ptx_ball_query")
-    order = torch.empty((B, Mt), **i32)
-    picks = torch.empty((B, max(Kd, 1)), **i32)
-    keep = torch.empty((B, Mk), **i32)
-    kcenter_i = torch.empty((B, Mk, 3), dtype=_F32, device=dev)
-    kcluster = torch.empty((B, Mk, K, 3), dtype=_F32, device=dev)
-    kidx = torch.empty((B, Mk, K), **i32)
-    drop_idx = torch.empty((B, max(Kd, 1) * K), **i32)
-    tag = torch.empty((B, N), **i32)                      # every word is written by ptx_select_clusters
-    oo = None if order_override is None else order_override.to(device=dev, dtype=torch.int32).contiguous()
-    _ck(lib.ptx_select_clusters(ctypes.byref(shape), _p(idx2), _p(cdet), _p(cl2), _p(pad), _p(oo), _p(order), _p(picks),
-                                _p(keep), _p(kcenter_i), _p(kcluster), _p(kidx), _p(drop_idx), _p(tag), st), "ptx_select_clusters")
-    if _IMG_POS == 1:
-        img_proxy, side, main = _image_branch()
-    ntiles = (N + 2047) // 2048
-    tile_counts = torch.empty((B * ntiles,), **i32)
-    opos = torch.empty((B, N), **i32)
-    counts = torch.empty((B,), **i32)
-    _ck(lib.ptx_op_out_positions(_p(tag), B, N, _p(tile_counts), _p(opos), _p(counts), st), "ptx_op_out_positions")
-    # the list lengths of PRE:467 are known here: copy them out now and wait at the very end, so that the host keeps enqueueing
-    # the float half while the index half runs (r04: a blocking read at the end idled the GPU across the forward / backward seam)
-    if getattr(mod, "_train_pin", None) is None:
-        mod._train_pin = {}
-    pin = mod._train_pin.get((B, st))
-    if pin is None:
-        pin = mod._train_pin[(B, st)] = (torch.empty((B,), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-    pin[1].synchronize()                                         # an earlier call's copy into the same pinned words
-    pin[0].copy_(counts, non_blocking=True)
-    pin[1].record()
-    src = torch.empty((B * Mk,), **i32)
-    _ck(lib.ptx_op_keep_rows(_p(order), _p(keep), B, M, Mt, Mk, _p(src), st), "ptx_op_keep_rows")
-
-    _tick("index2")
     # ---- float half: kept centres, point proxies (PRE:437)
-    kcenter = _GatherRows.apply(centers, src)                                    # (B*Mk,3), differentiable
+    kcenter = _GatherRows.apply(centers, r.src)                                  # (B*Mk,3), differentiable
     kc_enc, kc_aff = fork(kcenter, 2)
     enc = mod.simple_encoder
     ebn = enc.mlp[1]
-    pp = _SlotNet.apply(kc_enc, kcluster, enc.mlp[0].weight, enc.mlp[0].bias, ebn.weight, ebn.bias, ebn.running_mean,
+    pp = _SlotNet.apply(kc_enc, r.kcluster, enc.mlp[0].weight, enc.mlp[0].bias, ebn.weight, ebn.bias, ebn.running_mean,
                         ebn.running_var, ebn.eps, ebn.momentum, True)            # (B*Mk, C)
     if _FUSED_BLOCK:                      # the fused block node sums its two uses of the point proxies itself
         pp_t1, pp_i1 = fork(pp, 2)
@@ -1097,34 +1163,23 @@ def forward_train(mod, points: List[torch.Tensor], text_feats, text_mask, img_fe
     else:
         pp_t1, pp_t2, pp_i1, pp_i2 = fork(pp, 4)
 
-    _tick("encoder")
-    if _IMG_POS == 2:
-        img_proxy, side, main = _image_branch()
     # ---- text branch (PRE:440-446)
     L = text_feats.shape[1]
     tf2 = _c(text_feats.to(_F32)).view(B * L, C)
     translate = _block(mod, mod.textformer[-1], mod.text_norm[-1], mod.text_trans, mod.text_trans_norm, pp_t1, pp_t2,
                        tf2, text_mask, B, Mk, L, seeds[0])
 
-    _tick("text_block")
-    if _IMG_POS == 3:
-        img_proxy, side, main = _image_branch()
-    _tick("img_branch")
     if side is not None:
         main.wait_stream(side)
         img_proxy = _StreamHop.apply(img_proxy, side)
     transform = _block(mod, mod.imgformer[-1], mod.img_norm[-1], mod.img_trans, mod.img_trans_norm, pp_i1, pp_i2,
                        img_proxy, None, B, Mk, V, seeds[1])
 
-    _tick("img_block")
     # ---- submanifold reshape + scatter + drop (PRE:459-467)
-    pin[1].synchronize()
-    n_keep = pin[0].tolist()                                                    # the list lengths of PRE:467
-    outs = list(_AffineApply.apply(kc_aff, translate, transform, pts, tag, opos, kidx, kcluster, shape, ws, n_keep))
-    _tick("affine")
-    aux = dict(idx2=idx2, order=order, picks=picks[:, :Kd], keep=keep, kidx=kidx, drop_idx=drop_idx[:, : Kd * K],
-               centers=centers, translate=translate, transform=transform, point_proxy=pp, img_proxy=img_proxy,
-               kcenter=kcenter, opos=opos)
+    n_keep = _kept_counts(r)
+    outs = list(_AffineApply.apply(kc_aff, translate, transform, pts, r.tag, r.opos, r.kidx, r.kcluster, shape, ws, n_keep))
+    aux = _aux(r, _aux_shapes(B, N, M, K, Mt, Mk, C, V), centers=centers, translate=translate, transform=transform, point_proxy=pp,
+               img_proxy=img_proxy, kcenter=kcenter)
     return outs, aux
 
 
@@ -1155,92 +1210,40 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, st8, text_feats, img_feat, *params):
         mod, points, text_mask, shape, ws, order_override = st8["args"]
-        lib = _abi.lib()
         dev = points[0].device
         st = _st()
         B, N = len(points), points[0].shape[0]
         M, K, Mt, Mk, C = mod.num_cluster, mod.num_sub, shape.Mt, shape.Mk, mod.embed_dim
-        Kd = Mt - Mk
-        i32 = dict(dtype=torch.int32, device=dev)
-        # PRE:426-427 (no graph is recorded inside a Function's forward: no detach; _check_inputs has already looked at the dtypes)
-        pts = torch.stack(points) if all([p.dtype == _F32 for p in points]) else torch.stack([p.to(_F32) for p in points])
+        pts = _stack_points(points)                      # no graph is recorded inside a Function's forward: no detach
         seeds = st8["seeds"]
         T = {}                                                        # the tape: one context per node body
         # ---- image branch on the side stream (PRE:449-450): it needs nothing from the clustering half, so it is enqueued FIRST and runs
         # beside the ball queries and the farthest point sampling (one work-group per scene for 0.2 ms: the chip is idle next to it)
         V = img_feat.shape[1]
-        hw = mod.img_spacial_dim ** 2
         S = _static(mod)
         ip_par = S["ip_par"]
-        img3 = _c(img_feat).view(B * V, mod.input_dim, hw)
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(mod, dev) if _SIDE_STREAM else None
+        img3 = _c(img_feat).view(B * V, mod.input_dim, mod.img_spacial_dim ** 2)
 
         def run_img():
-            if side is not None:
-                side.wait_stream(main)
-            with torch.cuda.stream(side if side is not None else main):
-                T["ip"] = _Ctx((ctx.needs_input_grad[2],))
-                return _ImgPool.forward(T["ip"], img3, *ip_par[:9], mod.num_heads, *ip_par[9:], S["norm_img"].eps)
-        img_proxy = run_img() if _IMG_FIRST else None
+            T["ip"] = _Ctx((ctx.needs_input_grad[2],))
+            return _ImgPool.forward(T["ip"], img3, *ip_par[:9], mod.num_heads, *ip_par[9:], S["norm_img"].eps)
+        img_proxy, side, main = _on_side(mod, dev, run_img)
         # ---- index half, part 1 + offset network (PRE:55-62)
-        minmax = torch.empty((B, 2, 3), dtype=_F32, device=dev)
-        c0 = torch.empty((B, M, 3), dtype=_F32, device=dev)
-        lin = mod._train_lin(dev)
-        enc_scratch = torch.empty((max(B * 6, 64),), **i32)
-        _ck(lib.ptx_grid_centers(_p(pts), B, N, _p(lin), mod.grid_size, 4.0, _p(minmax), _p(c0), _p(enc_scratch),
-                                 enc_scratch.numel() * 4, st), "ptx_grid_centers")
-        idx1 = torch.empty((B, M, K), **i32)
-        cl1 = torch.empty((B, M, K, 3), dtype=_F32, device=dev)
-        _ck(lib.ptx_ball_query(_p(c0), _p(pts), B, M, N, K, 3.0, _p(idx1), _p(cl1), None, st), "ptx_ball_query")
+        minmax, c0, cl1 = _index_centres(mod, pts, st)
         bn = S["bn"]
         T["off"] = _Ctx((False,) * 11)
         pooled = _SlotNet.forward(T["off"], c0.view(B * M, 3), cl1, *S["off_par"], *S["off_run"], bn.eps, bn.momentum, False)
         T["oh"] = _Ctx()
         centers = _OffsetHead.forward(T["oh"], pooled, S["oh"], c0, minmax, M, 4.0)
-        # ---- index half, part 2 (PRE:65, 352-420, 478-523)
-        cdet = centers
-        if mod._centers_override is not None:
-            cdet = mod._centers_override.to(device=dev, dtype=_F32).reshape(B * M, 3).contiguous()
-        idx2 = torch.empty((B, M, K), **i32)
-        cl2 = torch.empty((B, M, K, 3), dtype=_F32, device=dev)
-        pad = torch.empty((B, M), **i32)
-        _ck(lib.ptx_ball_query(_p(cdet), _p(pts), B, M, N, K, 3.0, _p(idx2), _p(cl2), _p(pad), st), "ptx_ball_query")
-        order = torch.empty((B, Mt), **i32)
-        picks = torch.empty((B, max(Kd, 1)), **i32)
-        keep = torch.empty((B, Mk), **i32)
-        kcenter_i = torch.empty((B, Mk, 3), dtype=_F32, device=dev)
-        kcluster = torch.empty((B, Mk, K, 3), dtype=_F32, device=dev)
-        kidx = torch.empty((B, Mk, K), **i32)
-        drop_idx = torch.empty((B, max(Kd, 1) * K), **i32)
-        tag = torch.empty((B, N), **i32)                      # every word is written by ptx_select_clusters
-        oo = None if order_override is None else order_override.to(device=dev, dtype=torch.int32).contiguous()
-        _ck(lib.ptx_select_clusters(ctypes.byref(shape), _p(idx2), _p(cdet), _p(cl2), _p(pad), _p(oo), _p(order), _p(picks),
-                                    _p(keep), _p(kcenter_i), _p(kcluster), _p(kidx), _p(drop_idx), _p(tag), st), "ptx_select_clusters")
-        if img_proxy is None:
-            img_proxy = run_img()
-        # ---- output positions; the list lengths of PRE:467 are copied out now and awaited at the very end
-        ntiles = (N + 2047) // 2048
-        tile_counts = torch.empty((B * ntiles,), **i32)
-        opos = torch.empty((B, N), **i32)
-        counts = torch.empty((B,), **i32)
-        _ck(lib.ptx_op_out_positions(_p(tag), B, N, _p(tile_counts), _p(opos), _p(counts), st), "ptx_op_out_positions")
-        if getattr(mod, "_train_pin", None) is None:
-            mod._train_pin = {}
-        pin = mod._train_pin.get((B, st))
-        if pin is None:
-            pin = mod._train_pin[(B, st)] = (torch.empty((B,), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-        pin[1].synchronize()
-        pin[0].copy_(counts, non_blocking=True)
-        pin[1].record()
-        src = torch.empty((B * Mk,), **i32)
-        _ck(lib.ptx_op_keep_rows(_p(order), _p(keep), B, M, Mt, Mk, _p(src), st), "ptx_op_keep_rows")
+        # ---- index half, parts 2 and 3 (PRE:65, 352-420, 478-523)
+        r = _index_select(mod, shape, pts, centers, order_override, st)
+        _index_positions(mod, shape, r, st)
         # ---- float half (PRE:437-455)
         T["g"] = _Ctx()
-        kcenter = _GatherRows.forward(T["g"], centers, src)
+        kcenter = _GatherRows.forward(T["g"], centers, r.src)
         ebn = S["ebn"]
         T["enc"] = _Ctx((True,) + (False,) * 10)
-        pp = _SlotNet.forward(T["enc"], kcenter, kcluster, *S["enc_par"], *S["enc_run"], ebn.eps, ebn.momentum, True)
+        pp = _SlotNet.forward(T["enc"], kcenter, r.kcluster, *S["enc_par"], *S["enc_run"], ebn.eps, ebn.momentum, True)
         L = text_feats.shape[1]
         tf2 = _c(text_feats.to(_F32)).view(B * L, C)
         tbm, ibm = S["tb"], S["ib"]
@@ -1258,18 +1261,15 @@ class _TrainStep(torch.autograd.Function):
             transform.record_stream(main)
         translate = _BlockFused.forward(T["tb"], pp, tf2, text_mask, cfg_t, *tbm[6], *par_t)
         if side is not None:
-            img_proxy.record_stream(main)
             main.wait_stream(side)
         if not apart:
             transform = _BlockFused.forward(T["ib"], pp, img_proxy, None, cfg_i, *ibm[6], *par_i)
         # ---- submanifold reshape + scatter + drop (PRE:459-467)
-        pin[1].synchronize()
-        n_keep = pin[0].tolist()
+        n_keep = _kept_counts(r)
         T["aff"] = _Ctx()
-        outs = _AffineApply.forward(T["aff"], kcenter, translate, transform, pts, tag, opos, kidx, kcluster, shape, ws, n_keep)
-        st8["aux"] = dict(idx2=idx2, order=order, picks=picks[:, :Kd], keep=keep, kidx=kidx, drop_idx=drop_idx[:, : Kd * K],
-                          centers=centers, translate=translate, transform=transform, point_proxy=pp, img_proxy=img_proxy,
-                          kcenter=kcenter, opos=opos)
+        outs = _AffineApply.forward(T["aff"], kcenter, translate, transform, pts, r.tag, r.opos, r.kidx, r.kcluster, shape, ws, n_keep)
+        st8["aux"] = _aux(r, _aux_shapes(B, N, M, K, Mt, Mk, C, V), centers=centers, translate=translate, transform=transform,
+                          point_proxy=pp, img_proxy=img_proxy, kcenter=kcenter)
         ctx.tape = T
         ctx.set_materialize_grads(False)                # unused outputs (normally the three transforms) arrive as None, not as zero fills
         ctx.out_like = [(o.shape, o.dtype) for o in outs]
@@ -1296,16 +1296,14 @@ class _TrainStep(torch.autograd.Function):
                     G[id(p_)] = g_
 
         n = len(ctx.out_like)
-        g_kc, g_tr, g_tf = douts[n:n + 3]               # gradients that arrive through return_transforms' tensors (None: unused)
+        extra = douts[n:n + 3]                          # gradients that arrive through return_transforms' tensors (None: unused)
         dev = T["aff"].saved_tensors[3].device
         douts = [g if g is not None else torch.zeros(shp, dtype=dt_, device=dev) for g, (shp, dt_) in zip(douts[:n], ctx.out_like)]
-        dkc_aff, dtranslate, dtransform = _AffineApply.backward(T["aff"], *douts)[:3]
-        if g_kc is not None:
-            dkc_aff = add_(_c(dkc_aff), _c(g_kc.to(_F32)).view(dkc_aff.shape))
-        if g_tr is not None:
-            dtranslate = add_(_c(dtranslate), _c(g_tr.to(_F32)).view(dtranslate.shape))
-        if g_tf is not None:
-            dtransform = add_(_c(dtransform), _c(g_tf.to(_F32)).view(dtransform.shape))
+        d3 = list(_AffineApply.backward(T["aff"], *douts)[:3])
+        for i, g in enumerate(extra):
+            if g is not None:
+                d3[i] = add_(_c(d3[i]), _c(g.to(_F32)).view(d3[i].shape))
+        dkc_aff, dtranslate, dtransform = d3
         apart = side is not None and _BLOCKS_APART
         side_grads = []
         if apart:
@@ -1439,16 +1437,9 @@ def _cstep_fill(mod, S, cs, shape, pts, text2, text_mask, img3, seeds, ws, order
     (ip.wc, ip.bc, ip.pos, ip.wq, ip.bq, ip.wk, ip.bk, ip.wv, ip.bv, ip.cw, ip.cb, ip.lnw, ip.lnb) = (_p(t) for t in ipp)
     ip.ln_eps = S["norm_img"].eps
     B, Mk = shape.B, shape.Mk
-    for blk, bm, L_, sd, mask in ((st.tb, S["tb"], shape.L, seeds[0], text_mask), (st.ib, S["ib"], shape.V, seeds[1], None)):
+    for blk, bm, L_, sd in ((st.tb, S["tb"], shape.L, seeds[0]), (st.ib, S["ib"], shape.V, seeds[1])):
         cfg, par = _block_cfg(mod, *bm[:4], B, Mk, L_, sd, bm[4], bm[5])
-        (blk.B, blk.n, blk.L, blk.C, blk.H, blk.heads, blk.s, blk.nout, blk.eps1, blk.eps2, blk.eps3, blk.bn_eps, blk.bn_momentum,
-         blk.p_attn, blk.p_drop, blk.p_path, sds) = cfg[:17]
-        blk.compute_dtype = cfg[17]
-        for i, v in enumerate(sds):
-            blk.seed[i] = v & 0xFFFFFFFFFFFFFFFF
-        for i, t in enumerate(par):
-            blk.param[i] = _p(t)
-        blk.bn_run_mean, blk.bn_run_var = _p(bm[6][0]), _p(bm[6][1])
+        _fill_block(blk, cfg, par, *bm[6])
     st.ws, st.ws_bytes = _p(ws), ws.numel()
     st.side_stream = None if side is None else side.cuda_stream
     st.blocks_apart = 1 if (side is not None and _BLOCKS_APART) else 0
@@ -1463,7 +1454,7 @@ class _TrainStepC(torch.autograd.Function):
         dev = points[0].device
         B, N = len(points), points[0].shape[0]
         C, Mk = mod.embed_dim, shape.Mk
-        pts = torch.stack(points) if all([p.dtype == _F32 for p in points]) else torch.stack([p.to(_F32) for p in points])
+        pts = _stack_points(points)
         S = _static(mod)
         cs = _cstep_static(mod, S, dev)
         V, L = img_feat.shape[1], text_feats.shape[1]
@@ -1492,13 +1483,7 @@ class _TrainStepC(torch.autograd.Function):
         _ck(lib.ptx_train_step_fwd(ctypes.byref(st), main.cuda_stream), "ptx_train_step_fwd")
         ev_counts.synchronize()                                  # the list lengths of PRE:467
         n_keep = pin.tolist()
-        Kd, M, K = shape.Mt - Mk, mod.num_cluster, shape.K
-        i32 = torch.int32
-        spec = dict(idx2=(lay.idx2, (B, M, K), i32), order=(lay.order, (B, shape.Mt), i32), picks=(lay.picks, (B, Kd), i32),
-                    keep=(lay.keep, (B, Mk), i32), kidx=(lay.kidx, (B, Mk, K), i32), drop_idx=(lay.drop_idx, (B, Kd * K), i32),
-                    centers=(lay.centers, (B * M, 3), _F32), translate=(lay.translate, (B * Mk, 3), _F32),
-                    transform=(lay.transform, (B * Mk, 9), _F32), point_proxy=(lay.point_proxy, (B * Mk, C), _F32),
-                    img_proxy=(lay.img_proxy, (B * V, C), _F32), kcenter=(lay.kcenter, (B * Mk, 3), _F32), opos=(lay.opos, (B, N), i32))
+        spec = {k: (getattr(lay, k), *v) for k, v in _aux_shapes(B, N, mod.num_cluster, shape.K, shape.Mt, Mk, C, V).items()}
         aux = st8["aux"] = _Aux(arena, spec)
         ctx.set_materialize_grads(False)
         ctx.keep = (arena, pts, tf2, img3, text_mask, ws, keep, params)      # everything the backward's raw pointers refer to

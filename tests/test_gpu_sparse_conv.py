@@ -57,35 +57,20 @@ def test_kernel_map_rejects_a_coordinate_outside_the_key_range():
 
 
 # ------------------------------------------------------------------------------------------------------------------ convolution
-def _run(km, ops, use=(), relu=False):
-    t = lambda a: torch.from_numpy(a).to(DEV)                # noqa: E731
-    with torch.no_grad():
-        return sparse.sparse_conv3d(t(ops["feats"]), km, t(ops["weight"]), relu=relu, **{u: t(ops[u]) for u in use})
-
-
-def _refs(nbr, ops, use=(), relu=False):
-    r64 = sparse.sparse_conv3d_host(ops["feats"].astype(np.float64), nbr, ops["weight"].astype(np.float64), relu=relu,
-                                    **{u: ops[u].astype(np.float64) for u in use})
-    r32 = sparse.sparse_conv3d_host(ops["feats"], nbr, ops["weight"], relu=relu, **{u: ops[u] for u in use})
-    assert r32.dtype == np.float32
-    return r32, r64
-
-
-@pytest.mark.parametrize("cin,cout,k,s", [(3, 64, 3, 2), (64, 64, 3, 1), (64, 128, 3, 2), (128, 256, 1, 2), (512, 512, 3, 1)])
+@pytest.mark.parametrize("cin,cout,k,s", su.LAYER_SHAPES)
 def test_convolution_against_the_float64_restatement(cin, cout, k, s):
-    ts = 1 if cin == 3 else 4
-    cut = 600 if cin == 512 else 0                           # the 512-wide case: the random scene alone, cut to 600 rows
+    ts, cut = su.layer_rows(cin)                             # the 512-wide case: the random scene alone, cut to 600 rows
     _, _, nbr = su.host_map(ts, k, s, cut)
     km = su.device_map(ts, k, s, cut)
     assert np.array_equal(km.nbr.cpu().numpy(), nbr)
     n_in = su.rows(ts, cut)[0].shape[0]
     ops = su.operands(n_in, nbr.shape[0], cin, cout, k ** 3, seed=cin + cout)
     use = ("bias", "scale", "shift") if k == 1 else ()
-    got = _run(km, ops, use)
-    again = _run(km, ops, use)
+    got = su.conv_run(km, ops, use)
+    again = su.conv_run(km, ops, use)
     assert got.shape == (nbr.shape[0], cout) and got.dtype == torch.float32
     assert torch.equal(got, again), "two launches on the same inputs differ"
-    r32, r64 = _refs(nbr, ops, use)
+    r32, r64 = su.conv_refs(nbr, ops, use)
     su.hold(f"Cin={cin} Cout={cout} k={k} s={s} rows={n_in}->{nbr.shape[0]}", got.cpu().numpy(), r32, r64)
     if k == 1:                                               # 1x1 stride 2: a coarse cell without a row AT its corner has no neighbour
         lone = (nbr < 0).all(axis=1)
@@ -100,8 +85,8 @@ def test_epilogue_parts(use, relu):
     _, _, nbr = su.host_map(4, 3, 1)
     km = su.device_map(4, 3, 1)
     ops = su.operands(nbr.shape[0], nbr.shape[0], 64, 64, 27, seed=77)
-    got = _run(km, ops, use, relu)
-    r32, r64 = _refs(nbr, ops, use, relu)
+    got = su.conv_run(km, ops, use, relu)
+    r32, r64 = su.conv_refs(nbr, ops, use, relu)
     su.hold("epilogue " + "+".join(use) + ("+relu" if relu else ""), got.cpu().numpy(), r32, r64)
     if relu:
         assert float(got.min()) == 0.0
@@ -116,7 +101,7 @@ def test_module_forward_and_conversions():
     m = sparse.SparseConv3d(64, 128, kernel_size=3, stride=2, bias=True).to(DEV).eval()
     m.load_state_dict({"kernel": torch.from_numpy(ops["weight"]), "bias": torch.from_numpy(ops["bias"]).view(1, -1)})
     with torch.no_grad():
-        want = _run(km, ops, ("bias",))
+        want = su.conv_run(km, ops, ("bias",))
         assert torch.equal(m(torch.from_numpy(ops["feats"]).to(DEV), km), want)
         wide = torch.from_numpy(np.concatenate([ops["feats"], ops["feats"]], 1)).to(DEV).double()
         assert torch.equal(m(wide[:, :64], km), want)

@@ -21,9 +21,7 @@ from tests.sparse_util import DEV
 pytestmark = pytest.mark.gpu
 
 
-def _t(a, grad=False):
-    x = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    return x.requires_grad_() if grad else x
+_t = su.dev
 
 
 # ------------------------------------------------------------------------------------------------------------------ transposed map
@@ -45,44 +43,23 @@ def test_transposed_map_is_the_host_restatement(k, s, ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------ convolution
-def _grad_case(km, nbr, ops, full, relu, seed, wrt=("feats", "weight", "bias", "residual")):
-    """One differentiable call + backward of loss = (out * G).sum(); returns (out, G, {name: grad})."""
-    names = ("feats", "weight") + (("bias", "residual") if full else ())
-    leaves = {n: _t(ops[n], grad=n in wrt) for n in names}
-    kw = dict(bias=leaves["bias"], scale=_t(ops["scale"]), shift=_t(ops["shift"]), residual=leaves["residual"]) if full else {}
-    out = sparse.sparse_conv3d(leaves["feats"], km, leaves["weight"], relu=relu, differentiable=True, **kw)
-    G = np.random.default_rng(seed).standard_normal(tuple(out.shape)).astype(np.float32)
-    (out * _t(G)).sum().backward()
-    return out.detach(), G, {n: v.grad for n, v in leaves.items()}
-
-
-def _grad_refs(nbr, ops, out, G, full, relu):
-    kw32 = dict(out=out, scale=ops["scale"] if full else None, relu=relu, has_bias=full, has_residual=full)
-    r32 = sparse.sparse_conv3d_bwd_host(G, ops["feats"], nbr, ops["weight"], **kw32)
-    kw64 = dict(kw32, scale=ops["scale"].astype(np.float64) if full else None)
-    r64 = sparse.sparse_conv3d_bwd_host(G.astype(np.float64), ops["feats"].astype(np.float64), nbr, ops["weight"].astype(np.float64), **kw64)
-    assert r32["dfeats"].dtype == np.float32 and r64["dweight"].dtype == np.float64
-    return r32, r64
-
-
-@pytest.mark.parametrize("cin,cout,k,s", [(3, 64, 3, 2), (64, 64, 3, 1), (64, 128, 3, 2), (128, 256, 1, 2), (512, 512, 3, 1)])
+@pytest.mark.parametrize("cin,cout,k,s", su.LAYER_SHAPES)
 def test_gradients_against_the_float64_restatement(cin, cout, k, s):
     """The full set splits dweight over several row chunks with a partial last one (64 -> 64: 10 chunks of 256 rows over 2351)."""
-    ts = 1 if cin == 3 else 4
-    cut = 600 if cin == 512 else 0
+    ts, cut = su.layer_rows(cin)
     _, _, nbr = su.host_map(ts, k, s, cut)
     km = su.device_map(ts, k, s, cut)
     n_in = su.rows(ts, cut)[0].shape[0]
     ops = su.operands(n_in, nbr.shape[0], cin, cout, k ** 3, seed=cin + cout)
     full = k == 1                                            # bias + scale + shift + residual + ReLU on the 1x1 stride-2 layer
-    out, G, got = _grad_case(km, nbr, ops, full, relu=full, seed=cin)
-    out2, _, again = _grad_case(km, nbr, ops, full, relu=full, seed=cin)
+    out, G, got = su.grad_case(km, nbr, ops, full, relu=full, seed=cin)
+    out2, _, again = su.grad_case(km, nbr, ops, full, relu=full, seed=cin)
     with torch.no_grad():                                    # forward identity: the plain call, and differentiable under no_grad
         kw = {u: _t(ops[u]) for u in ("bias", "scale", "shift", "residual")} if full else {}
         plain = sparse.sparse_conv3d(_t(ops["feats"]), km, _t(ops["weight"]), relu=full, **kw)
         quiet = sparse.sparse_conv3d(_t(ops["feats"]), km, _t(ops["weight"]), relu=full, differentiable=True, **kw)
     assert torch.equal(out, plain) and torch.equal(quiet, plain) and torch.equal(out2, plain) and quiet.grad_fn is None
-    r32, r64 = _grad_refs(nbr, ops, out.cpu().numpy(), G, full, relu=full)
+    r32, r64 = su.grad_refs(nbr, ops, out.cpu().numpy(), G, full, relu=full)
     tag = f"bwd Cin={cin} Cout={cout} k={k} s={s} rows={n_in}->{nbr.shape[0]}"
     for name, key in (("feats", "dfeats"), ("weight", "dweight")) + ((("bias", "dbias"), ("residual", "dresidual")) if full else ()):
         g = got[name]
@@ -102,8 +79,8 @@ def test_one_row_scene_alone():
     nbr = sparse.kernel_map_host(rows, [1], 1, 3, 1)[2]
     assert np.array_equal(km.nbr.cpu().numpy(), nbr) and (nbr >= 0).sum() == 1
     ops = su.operands(1, 1, 64, 64, 27, seed=3)
-    out, G, got = _grad_case(km, nbr, ops, full=True, relu=False, seed=1)
-    r32, r64 = _grad_refs(nbr, ops, out.cpu().numpy(), G, True, relu=False)
+    out, G, got = su.grad_case(km, nbr, ops, full=True, relu=False, seed=1)
+    r32, r64 = su.grad_refs(nbr, ops, out.cpu().numpy(), G, True, relu=False)
     for name, key in (("feats", "dfeats"), ("weight", "dweight"), ("bias", "dbias"), ("residual", "dresidual")):
         su.hold(f"bwd one row {key}", got[name].cpu().numpy().reshape(r64[key].shape), r32[key], r64[key])
     assert (got["weight"].cpu().numpy()[np.arange(27) != 13] == 0).all()      # only the centre offset has a pair
@@ -113,14 +90,14 @@ def test_needs_input_grad_and_rejections():
     _, _, nbr = su.host_map(4, 3, 1)
     km = su.device_map(4, 3, 1)
     ops = su.operands(nbr.shape[0], nbr.shape[0], 64, 64, 27, seed=77)
-    _, _, both = _grad_case(km, nbr, ops, full=True, relu=True, seed=5)
+    _, _, both = su.grad_case(km, nbr, ops, full=True, relu=True, seed=5)
     assert tuple(both["bias"].shape) == tuple(ops["bias"].shape)
-    _, _, only_f = _grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("feats",))
+    _, _, only_f = su.grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("feats",))
     assert only_f["weight"] is None and only_f["bias"] is None and only_f["residual"] is None
     assert torch.equal(only_f["feats"], both["feats"])
-    _, _, only_w = _grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("weight",))
+    _, _, only_w = su.grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("weight",))
     assert only_w["feats"] is None and only_w["bias"] is None and torch.equal(only_w["weight"], both["weight"])
-    _, _, only_b = _grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("bias", "residual"))
+    _, _, only_b = su.grad_case(km, nbr, ops, full=True, relu=True, seed=5, wrt=("bias", "residual"))
     assert only_b["feats"] is None and only_b["weight"] is None
     assert torch.equal(only_b["bias"], both["bias"]) and torch.equal(only_b["residual"], both["residual"])
     # ReLU without scale: dresidual is gz itself

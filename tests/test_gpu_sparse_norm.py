@@ -29,20 +29,7 @@ def t(a):
 
 @functools.lru_cache(maxsize=None)
 def _data(C, offset):
-    rng = np.random.default_rng(100 + C + offset)
-    x = rng.standard_normal((N, C)).astype(np.float32)
-    if offset:
-        x += (offset * np.where(rng.random(C) < 0.5, -1.0, 1.0)).astype(np.float32)
-    ops = dict(x=x, weight=rng.uniform(0.5, 1.5, C).astype(np.float32), bias=(rng.standard_normal(C) * 0.5).astype(np.float32),
-               residual=rng.standard_normal((N, C)).astype(np.float32), g=rng.standard_normal((N, C)).astype(np.float32))
-    return ops
-
-
-def _refs(ops, ends, eps, use=(), relu=False):
-    r64 = sparse.sparse_norm_host(ops["x"].astype(np.float64), ends, eps, relu=relu, **{u: ops[u].astype(np.float64) for u in use})
-    r32 = sparse.sparse_norm_host(ops["x"], ends, eps, relu=relu, **{u: ops[u] for u in use})
-    assert r32.dtype == np.float32
-    return r32, r64
+    return su.norm_operands(N, C, offset, 100 + C + offset)
 
 
 # ------------------------------------------------------------------------------------------------------------------ forward
@@ -51,13 +38,9 @@ def test_conditioning_columns_far_from_zero(C):
     """(a) x = N(0,1) + 16 * (+-1 per column): what E[x^2] - E[x]^2 cannot do in fp32."""
     ops = _data(C, 16)
     got, stats = sparse.sparse_segment_norm(t(ops["x"]), SEGMENTS, EPS, return_stats=True)
-    r32, r64 = _refs(ops, SEGMENTS, EPS)
+    r32, r64 = su.norm_refs(ops, SEGMENTS, EPS)
     su.hold(f"norm conditioning C={C}", got.cpu().numpy(), r32, r64)
-    _, s64 = sparse.sparse_norm_host(ops["x"].astype(np.float64), SEGMENTS, EPS, return_stats=True)
-    stats = stats.cpu().numpy()
-    for s in (0, 1, 4):                                      # the statistics themselves, to a few fp32 ulps of their size
-        assert float(np.abs(stats[s, 0] - s64[s, 0]).max()) <= 4e-6 * 16
-        assert float(np.abs(stats[s, 1] / s64[s, 1] - 1).max()) <= 4e-6
+    su.hold_norm_stats(stats.cpu().numpy(), ops, SEGMENTS, EPS, (0, 1, 4), 16)
 
 
 @pytest.mark.parametrize("C", [64, 512])
@@ -72,37 +55,22 @@ def test_affine_residual_relu_and_the_edge_segments(C):
     again, stats2 = call(True)
     assert got.dtype == torch.float32 and got.shape == (N, C)
     assert torch.equal(got, again) and torch.equal(stats, stats2), "two calls on the same inputs differ"
-    r32, r64 = _refs(ops, SEGMENTS, EPS, use, True)
+    r32, r64 = su.norm_refs(ops, SEGMENTS, EPS, use, True)
     su.hold(f"norm affine+residual+relu C={C}", got.cpu().numpy(), r32, r64)
     assert float(got.min()) == 0.0
     plain, _ = call(False)
-    r32, r64 = _refs(ops, SEGMENTS, EPS, use, False)
+    r32, r64 = su.norm_refs(ops, SEGMENTS, EPS, use, False)
     su.hold(f"norm affine+residual C={C}", plain.cpu().numpy(), r32, r64)
     stats = stats.cpu().numpy()
     assert stats.shape == (5, 2, C) and np.array_equal(stats[2], np.zeros((2, C), np.float32))
     assert np.array_equal(plain.cpu().numpy()[513], ops["bias"] + ops["residual"][513])
     assert np.array_equal(stats[3, 0], ops["x"][513])
     bare = sparse.sparse_instance_norm(t(ops["x"]), SEGMENTS)
-    r32, r64 = _refs(ops, SEGMENTS, EPS)
+    r32, r64 = su.norm_refs(ops, SEGMENTS, EPS)
     su.hold(f"instance norm C={C}", bare.cpu().numpy(), r32, r64)
     mod = sparse.SparseInstanceNorm(C).to(DEV)
     with torch.no_grad():
         assert torch.equal(mod(t(ops["x"]), SEGMENTS), bare)  # weight 1, bias 0: x * 1 + 0
-
-
-def _bn_pair(C, seed):
-    rng = np.random.default_rng(seed)
-    bn64 = torch.nn.BatchNorm1d(C, eps=1e-5, momentum=0.1).double()
-    with torch.no_grad():
-        bn64.weight.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, C).astype(np.float32)))
-        bn64.bias.copy_(torch.from_numpy((rng.standard_normal(C) * 0.5).astype(np.float32)))
-        bn64.running_mean.copy_(torch.from_numpy((rng.standard_normal(C) * 0.1).astype(np.float32)))
-        bn64.running_var.copy_(torch.from_numpy(rng.uniform(0.5, 1.5, C).astype(np.float32)))
-    bn32 = torch.nn.BatchNorm1d(C, eps=1e-5, momentum=0.1)
-    bn32.load_state_dict({k: v.float() if v.is_floating_point() else v for k, v in bn64.state_dict().items()})
-    gpu = torch.nn.BatchNorm1d(C, eps=1e-5, momentum=0.1)
-    gpu.load_state_dict(bn32.state_dict())
-    return bn64.train(), bn32.train(), gpu.to(DEV).train()
 
 
 @pytest.mark.parametrize("C", [64, 512])
@@ -110,7 +78,7 @@ def test_training_batch_norm_two_steps_against_torch(C):
     """(c) one segment with the running statistics, two consecutive steps, against nn.BatchNorm1d in float64 on the CPU (yardstick: the
     same module in float32 on the CPU)."""
     ops = _data(C, 0)
-    bn64, bn32, gpu = _bn_pair(C, 7)
+    bn64, bn32, gpu = su.bn_pair(C, 7)
     for step, rows in enumerate((slice(0, N), slice(200, 1101))):
         x = np.ascontiguousarray(ops["x"][rows]) * np.float32(1.5) + np.float32(0.25)
         with torch.no_grad():
@@ -139,17 +107,6 @@ def test_training_batch_norm_two_steps_against_torch(C):
 
 
 # ------------------------------------------------------------------------------------------------------------------ backward
-def _hold_grads(name, got, ops, ends, eps, out, relu, weight=True):
-    """``got``: dict of numpy gradients; the ReLU mask of both references is the GPU's ``out``."""
-    kw = dict(out=out, relu=relu)
-    r64 = sparse.sparse_norm_bwd_host(ops["g"].astype(np.float64), ops["x"].astype(np.float64), ends, eps,
-                                      ops["weight"].astype(np.float64) if weight else None, **kw)
-    r32 = sparse.sparse_norm_bwd_host(ops["g"], ops["x"], ends, eps, ops["weight"] if weight else None, **kw)
-    for k, v in got.items():
-        assert v.shape == r64[k].shape and v.dtype == np.float32, k
-        su.hold(f"{name} {k}", v, r32[k], r64[k])
-
-
 @pytest.mark.parametrize("C", [64, 512])
 def test_backward_of_the_segment_norm(C):
     """(d), (e) for (b): dx, dweight, dbias, dresidual; dresidual is bit-equal to where(out > 0, g, 0); two backwards give equal bits."""
@@ -174,7 +131,7 @@ def test_backward_of_the_segment_norm(C):
     assert grads["weight"].shape == (C,) and grads["x"].shape == (N, C)
     got = dict(dx=grads["x"].cpu().numpy(), dweight=grads["weight"].cpu().numpy(), dbias=grads["bias"].cpu().numpy(),
                dresidual=grads["residual"].cpu().numpy())
-    _hold_grads(f"norm bwd relu C={C}", got, ops, SEGMENTS, EPS, out_np, True)
+    su.hold_norm_grads(f"norm bwd relu C={C}", got, ops, SEGMENTS, EPS, out_np, True)
     # needs_input_grad is honoured: only what was asked for comes back, with the same bits
     _, only_x = step(True, ("x",))
     assert torch.equal(only_x["x"], grads["x"]) and only_x["weight"] is None and only_x["residual"] is None
@@ -184,14 +141,14 @@ def test_backward_of_the_segment_norm(C):
     out, grads = step(False, every)
     assert torch.equal(grads["residual"], t(ops["g"]))
     got = dict(dx=grads["x"].cpu().numpy(), dweight=grads["weight"].cpu().numpy(), dbias=grads["bias"].cpu().numpy())
-    _hold_grads(f"norm bwd C={C}", got, ops, SEGMENTS, EPS, None, False)
+    su.hold_norm_grads(f"norm bwd C={C}", got, ops, SEGMENTS, EPS, None, False)
 
 
 @pytest.mark.parametrize("C", [64, 512])
 def test_backward_of_the_training_batch_norm(C):
     """(d) for (c): one segment, through ``sparse_batch_norm`` and the module's own parameters, with residual and ReLU."""
     ops = _data(C, 0)
-    _, _, gpu = _bn_pair(C, 9)
+    _, _, gpu = su.bn_pair(C, 9)
     with torch.no_grad():
         gpu.weight.copy_(t(ops["weight"]))
     x, res = t(ops["x"]).requires_grad_(), t(ops["residual"]).requires_grad_()
@@ -200,7 +157,7 @@ def test_backward_of_the_training_batch_norm(C):
     out_np = out.detach().cpu().numpy()
     assert np.array_equal(res.grad.cpu().numpy(), np.where(out_np > 0, ops["g"], np.float32(0)))
     got = dict(dx=x.grad.cpu().numpy(), dweight=gpu.weight.grad.cpu().numpy(), dbias=gpu.bias.grad.cpu().numpy(), dresidual=res.grad.cpu().numpy())
-    _hold_grads(f"batch norm bwd C={C}", got, ops, [N], gpu.eps, out_np, True)
+    su.hold_norm_grads(f"batch norm bwd C={C}", got, ops, [N], gpu.eps, out_np, True)
     assert int(gpu.num_batches_tracked) == 1
 
 

@@ -181,6 +181,23 @@ def test_header_binding_and_exports_declare_the_norm_entry_points():
     assert ws(400000, 6, 64) <= 2 * 4 * 64 * (400000 // 256 + 6) + 2 * (2 * 4 * 64 * 6) + 1024      # two floats per tile and column; a segment's means, its sums
 
 
+def test_norm_workspace_is_the_restated_tile_bound():
+    """``sparse_util.norm_plan`` restates the norms' private workspace plan (at most n // 256 + S tiles); the library's total is its at
+    the segment layouts of tests/test_gpu_sparse_regimes.py, whose tile counts -- 17 and 34 per segment, 96 -- are what that module is
+    about and stay inside the bound."""
+    ws = _abi.lib().ptx_sparse_norm_workspace_bytes
+    tiles = {name: su.seg_tiles(sizes) for name, sizes in su.NORM_REGIMES.items()}
+    assert tiles["four"] == [17, 0, 34, 1] and tiles["sixty-four"][:4] == tiles["four"] and tiles["one"] == [96]
+    assert [sum(s) for s in su.NORM_REGIMES.values()] == [12598, 27645, 24548] and len(su.NORM_REGIMES["sixty-four"]) == 64
+    assert [-(-t // 16) for t in (17, 34, 96)] == [2, 3, 6]    # tiles per slot run
+    for name, sizes in su.NORM_REGIMES.items():
+        n, S = sum(sizes), len(sizes)
+        for C in (64, 128):
+            bound, total = su.norm_plan(n, S, C)
+            assert sum(tiles[name]) <= bound == n // 256 + S and ws(n, S, C) == total, (name, C)
+    assert ws(400000, 6, 64) == su.norm_plan(400000, 6, 64)[1] and ws(0, 1, 512) == su.norm_plan(0, 1, 512)[1]
+
+
 def test_norm_argument_checks_answer_einval_before_touching_a_device():
     lib = _abi.lib()
     EINVAL = -1

@@ -139,6 +139,29 @@ def test_header_binding_and_exports_declare_the_backward_entry_points():
     assert ws(2_000_000, 27, 512, 512) <= (256 << 20) + 28 * (1 << 20) + 8 * (1 << 20)     # bounded: 256 MiB of slabs + one + the tiles
 
 
+def test_dweight_plan_restatement_is_the_library_s():
+    """``sparse_util.dw_plan`` restates the library's private split of dweight over the rows; its workspace total is the library's at the
+    shapes of the layer tests and of ``DW_REGIMES``, and at the latter it gives the chunk sizes tests/test_gpu_sparse_regimes.py is
+    about: more than the 1024 rows of one compaction round, in 1, 2 and 5 chunks.  A changed plan fails here, not silently there."""
+    ws = _abi.lib().ptx_sparse_conv3d_bwd_workspace_bytes
+    shapes = []
+    for cin, cout, k, s in su.LAYER_SHAPES:
+        ts, cut = su.layer_rows(cin)
+        n_out = su.host_map(ts, k, s, cut)[2].shape[0]
+        shapes.append((n_out, k ** 3, cin, cout))
+    assert [su.dw_plan(*sh)[:2] for sh in shapes] == [(1024, 3), (256, 10), (256, 9), (256, 9), (640, 1)]
+    for name, c in su.DW_REGIMES.items():
+        n = sum(c["counts"])
+        R, S, _ = su.dw_plan(n, 27, c["cin"], c["cout"])
+        assert (R, S) == (c["R"], c["S"]) and R > 1024 and (S - 1) * R < n <= S * R, name
+        assert su.dense_map(name)[0].shape[0] == n
+        shapes.append((n, 27, c["cin"], c["cout"]))
+    assert [su.DW_REGIMES[k]["S"] for k in ("512->512", "256->512", "stem")] == [1, 2, 5]
+    assert su.DW_REGIMES["stem"]["R"] // 4 == 272 and 272 % 64 != 0       # the stem's wave quarter, off the 64-row grid
+    for sh in shapes + [(0, 1, 64, 64), (400000, 27, 64, 64), (2_000_000, 27, 512, 512), (100000, 8, 64, 128)]:
+        assert ws(*sh) == su.dw_plan(*sh)[2] > 0, sh
+
+
 def test_default_stays_inference_only_and_there_is_no_cpu_path():
     km = sparse.KernelMap(coords=torch.zeros(2, 4, dtype=torch.int32), scene_rows=[2], nbr=torch.zeros(2, 1, dtype=torch.int32),
                           kernel_size=1, stride=1, tensor_stride=1)

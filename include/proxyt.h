@@ -441,7 +441,7 @@ PTX_API int ptx_voxel_coarsen(const int32_t *coords_in, const int32_t *in_scene_
  * stride=2), mink_resnet.py:67-69 MinkowskiMaxPooling(kernel_size=2, stride=2), mink_resnet.py:103-109 the 1x1 stride-2 downsample,
  * mink_resnet.py:111-119 the BasicBlocks' 3x3x3 convolutions): kernel maps over the rows the calls above produce, and a fused gather-GEMM convolution and max-pool that consume
  * them, and their backward passes.  MinkowskiInstanceNorm (mink_resnet.py:64) and a training MinkowskiBatchNorm: the norm section below; the backbone is
- * assembled in Python (proxytransformation_amd/backbone.py); neck_3d is not here.
+ * assembled in Python (proxytransformation_amd/backbone.py); neck_3d: the sparse-neck section below.
  *
  * Kernel map.  coords_in (n_in,4) int32 rows (scene, x, y, z) of a level of tensor stride `tensor_stride` (a power of two; every
  * coordinate a multiple of it), scene b's rows [in_scene_end[b-1], in_scene_end[b]) with in_scene_end a [host] array of B ints (read
@@ -535,6 +535,61 @@ PTX_API int ptx_sparse_norm_apply(const float *x, const int32_t *seg_end, int S,
 PTX_API int ptx_sparse_norm_bwd(const float *g, const float *x, const float *out, const int32_t *seg_end, int S, int n, int C,
                         const float *stats, const float *weight, float *dx, float *dweight, float *dbias, float *dresidual,
                         void *workspace, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------ the sparse neck: MinkNeck, eval forward (ABI 13, by addition)
+ * `feats, scores, coords = self.neck_3d(x, batch_size)` (necks/mink_neck.py:142-161): the generative transposed convolution, the sum
+ * over the union of two row sets, the trilinear score lookup, the per-scene top-k prune and the classification head, plus the
+ * convolution with an activation selector and wide inputs.  The neck is assembled in Python (proxytransformation_amd/neck.py) and
+ * restated in numpy (neck_host.py).  fp32; no float atomics and fixed summation orders: two calls on the same inputs give the same bits;
+ * everything is ordered on `stream`; the host waits only for the union's row counts (pinned words, ptx_wait_counts) and never
+ * synchronises the device; host checks (PTX_EINVAL / PTX_ENOSPACE with the numbers in the message) come before anything is enqueued.
+ * Rows, scene ends ([host] arrays of B ints, B <= 64) and tensor strides are ptx_sparse_kernel_map's.  Forward only: no backward, no
+ * training BatchNorm, no bf16.
+ *
+ * ptx_sparse_conv3d with `act` a selector -- 0 none, 1 ReLU (ptx_sparse_conv3d's bits), 2 ELU alpha = 1: v > 0 ? v : expm1f(v) -- and
+ * Cin a multiple of 16 up to 1024 (or the stem's 3).  The same kernel. */
+PTX_API int ptx_sparse_conv3d_act(const float *feats, int n_in, const int32_t *nbr, int n_out, int kvol, const float *weight, int Cin, int Cout,
+                          const float *bias, const float *scale, const float *shift, const float *residual, int act, float *out,
+                          void *stream);
+/* MinkowskiGenerativeConvolutionTranspose(kernel_size=2, stride=2) (mink_neck.py:90-94): coords (n,4) of tensor stride
+ * `tensor_stride` >= 2, feats (n,Cin), weight (8,Cin,Cout).  Row 8 i + j of coords_out (8 n,4) is coords[i] + offset j of a kernel of 2 at
+ * tensor_stride / 2 (j counts x fastest, then y, then z: our reading of MinkowskiEngine, parity unpinned against ME itself), row 8 i + j of
+ * out (8 n,Cout) is act(feats[i] @ weight[j] (* scale + shift)): the dense product (n,Cin) @ (Cin, 8 Cout) on the exact-fp32 matrix
+ * instruction in ptx_sparse_conv3d's blocked order.  Children of distinct parents are distinct: no table.  Scene ends: 8 x the input's.
+ * Cin: a multiple of 64 up to 1024; Cout: a multiple of 64 up to 512; act as above.  Two launches. */
+PTX_API int ptx_sparse_conv_transpose_gen(const int32_t *coords, int n, int tensor_stride, const float *feats, const float *weight, int Cin,
+                                  int Cout, const float *scale, const float *shift, int act, int32_t *coords_out, float *out, void *stream);
+/* Workspace of the three calls below: B scenes, ncap >= the largest scene's rows of the set that is indexed (A's, the score rows'),
+ * rows >= the rows of either operand of the union (0 for the score lookup).  0: unsupported size. */
+PTX_API size_t ptx_neck_workspace_bytes(int B, int ncap, int rows);
+/* `inputs[i] + x` (mink_neck.py:149): A and B, rows of the same tensor stride and width C (a multiple of 4), both grouped by scene.  The
+ * result's rows of scene b are A's rows of b in A's order, then the rows of B in b that are absent from A, in B's order; features
+ * A[a] + B[k] where both exist (one fp32 add), the single operand's row elsewhere.  B's rows must be distinct.  out_coords / out_feats:
+ * capacity rows(A) + rows(B).  count_words: 2 int32 = {rows, rows of A whose coordinate >> log2(tensor_stride) left +-2^18};
+ * out_scene_end: B int32; published like ptx_sparse_kernel_map's (preset to -1, poll with ptx_wait_counts).  The lookup of B's
+ * coordinates in A is the kernel maps' hash table.  One memset pair + four launches. */
+PTX_API int ptx_neck_union_add(const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
+                       const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords,
+                       float *out_feats, int32_t *out_scene_end, int32_t *count_words, void *workspace, size_t ws_bytes, void *stream);
+/* `scores.features_at_coordinates(x.C.float())` (mink_neck.py:175): scores (m,1) on the rows s_coords of tensor stride ts =
+ * `tensor_stride`, q_coords (n_q,4) any integer coordinates (the neck's are multiples of ts / 2).  Per axis l = floor(q / ts) * ts; the
+ * eight corners c = l + {0, ts}^3, indexed x fastest; w_c = prod_axis (1 - |q - c| / ts); out[i] = sum over the corners present in the
+ * same scene of w_c * scores[c], in ascending corner index from 0.0f (absent corners contribute nothing, nothing is renormalised, a
+ * query without a present corner gets 0.0).  Bit-identical to the fp32 numpy restatement. */
+PTX_API int ptx_neck_prune_scores(const int32_t *q_coords, int n_q, const int32_t *s_coords, const int32_t *s_scene_end, int B,
+                          int tensor_stride, const float *scores, float *out, void *workspace, size_t ws_bytes, void *stream);
+/* The per-scene top-k of mink_neck.py:178-185 with MinkowskiPruning: scene b keeps its min(rows_b, k) rows with the largest scores (n);
+ * among equal scores the lower row index wins (torch.topk leaves ties unspecified); -0.0 and +0.0 are equal; a NaN orders by its bits
+ * (above +inf with the sign bit clear, below -inf with it set).  dest (n) int32: the place of each row among the kept rows, or -1; the
+ * kept rows keep their relative order; coords (n,4) / feats (n,C) are copied to out_coords / out_feats at dest.  The new scene ends are
+ * the accumulated min(rows_b, k): the host knows them without a wait.  A radix select per scene, integer counts only.  Two launches. */
+PTX_API int ptx_neck_topk_prune(const float *scores, const int32_t *scene_end, int B, int k, const int32_t *coords, const float *feats, int C,
+                        int32_t *dest, int32_t *out_coords, float *out_feats, void *stream);
+/* conv_cls (kernel 1, with bias; mink_neck.py:122-126) and the prune score of mink_neck.py:200-201 in one kernel: cls (n,num_classes) =
+ * feats (n,C) @ weight (C,num_classes) + bias (num_classes, optional), score (n) = max over the classes of cls.  C: a multiple of 64 up
+ * to 512; 1 <= num_classes <= 16.  Fixed order: 16 lanes per row, each its channels 4 l + 64 m ascending, then the lanes by halving. */
+PTX_API int ptx_neck_head(const float *feats, int n, int C, const float *weight, const float *bias, int num_classes, float *cls, float *score,
+                  void *stream);
 
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/

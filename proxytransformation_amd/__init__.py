@@ -7,6 +7,7 @@ Only what the path needs lives here:
 * ``csrc/`` + ``libproxyt_hip.so``           -- hand-written HIP kernels for gfx950 behind
   the C ABI of ``include/proxyt.h`` (bound with ctypes in ``_abi``);
 * ``backbone.MinkResNet``                    -- the sparse 3D backbone (backbones/mink_resnet.py) on the layers of ``sparse``;
+* ``neck.MinkNeck``                          -- the sparse neck and head (necks/mink_neck.py), eval forward, on ``neck`` / ``sparse``;
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -17,6 +18,7 @@ Importing the package does not need a GPU and does not load the shared library;
 from .registry import MODELS, REGISTRY_BACKEND
 from .module import ProxyTransformationNormReverse
 from .backbone import MinkResNet
+from .neck import MinkNeck
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "MinkResNet", "ProxyTransformationNormReverse"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse"]
 __version__ = "0.1.0"

@@ -190,6 +190,13 @@ SIGNATURES.update({
     "ptx_sparse_norm_fwd": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _Z, _P]),
     "ptx_sparse_norm_apply": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "ptx_sparse_norm_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_sparse_conv3d_act": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "ptx_sparse_conv_transpose_gen": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "ptx_neck_workspace_bytes": (_Z, [_I, _I, _I]),
+    "ptx_neck_union_add": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_neck_prune_scores": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _Z, _P]),
+    "ptx_neck_topk_prune": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "ptx_neck_head": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),

@@ -1,0 +1,446 @@
+// The row operations of `feats, scores, coords = self.neck_3d(x, batch_size)` (necks/mink_neck.py:142-161) that are not convolutions -- the
+// convolutions themselves (ELU epilogue, Cin up to 1024, the generative transposed one) are instantiations of k_sparse_conv in sparse.hip:
+//
+//   ptx_neck_union_add      `inputs[i] + x` (mink_neck.py:149): the sum of two sparse tensors over the UNION of their rows.  A's rows are
+//       hashed by k_vox_insert (voxel.h: the table of the kernel maps, the value is the row's index); k_union_match, one thread per row of
+//       B, probes it (vox_find) and records both directions (match[k] = a, partner[a] = k); k_union_rank, one work-group per scene, ranks
+//       the unmatched rows of B in B's order (ballot prefix over runs of 256 rows); k_union_write, one thread per (row, 4 channels),
+//       writes A's rows of a scene in A's order (A[a] + B[k] where both exist: one fp32 add), then B's unmatched rows, and publishes the
+//       row count and the scene ends through pinned words like k_sparse_query.
+//   ptx_neck_prune_scores   `scores.features_at_coordinates(x.C.float())` (mink_neck.py:175): trilinear lookup of the coarser level's
+//       (m,1) score at the finer level's coordinates: the same table over the score rows, one thread per query, eight probes, the
+//       present corners added in ascending corner index.
+//   ptx_neck_topk_prune     the per-scene top-k of mink_neck.py:178-185 and MinkowskiPruning: one work-group per scene runs a radix
+//       select (4 passes of 8 bits over an order-preserving integer key, LDS histograms of integer counts) for the k-th largest score,
+//       then ranks the kept rows in their order: everything above the threshold, and of the rows AT the threshold the first few by row
+//       index.  k_prune_copy moves coordinates and features to their ranks.  The new scene ends are min(rows, k) accumulated: host knowledge.
+//   ptx_neck_head           conv_cls (kernel 1, with bias) and the prune score max over the classes in one kernel: 16 lanes per row, each
+//       with a fixed share of the channels, combined by a fixed shuffle tree.
+//
+// fp32, no float atomics, fixed summation orders (bitwise reproducible), everything ordered on the caller's stream; the host waits only
+// for the union's row counts.  Held to the numpy restatements of proxytransformation_amd/neck_host.py.
+#include "voxel.h"
+#include "sparse.h"
+
+namespace ptx {
+
+constexpr int kNeckMaxClasses = 16;
+
+struct NeckLayout { size_t table, match, partner, rank, extra, total; };
+static NeckLayout neck_layout(int B, int ncap, int rows)
+{
+    NeckLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes, 256); return r; };
+    L.table = take(vox_layout(B, ncap).total);
+    L.match = take((size_t)rows * 4);
+    L.partner = take((size_t)rows * 4);
+    L.rank = take((size_t)rows * 4);
+    L.extra = take(64 * 4);
+    L.total = o;
+    return L;
+}
+
+// exclusive rank of `flag` among the 256 threads of the work-group in thread order, and the work-group's total; s_w: 4 ints of LDS
+__device__ __forceinline__ int block_rank(bool flag, int *s_w, int &total)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int within = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                        // (the previous call's reads of s_w are done)
+    if (lane == 0) s_w[wid] = __popcll(m);
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wid; ++w) before += s_w[w];
+    total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return before + within;
+}
+
+// ---- union add ------------------------------------------------------------------------------------------------------------
+struct UnionArgs {
+    const int32_t *a_coords, *b_coords; const float *a_feats, *b_feats;
+    const unsigned long long *keys; const int32_t *first; unsigned int mask;      // the index table of A's rows
+    const int32_t *index_overflow;
+    int B, ncap, shift, C, nA, nB;
+    int32_t *match, *partner, *rank, *extra;               // extra[b]: unmatched rows of B in scene b
+    int32_t *out_coords; float *out_feats; int32_t *count_words, *out_scene_end;
+    int32_t a_end[64], b_end[64];
+};
+
+__global__ __launch_bounds__(256) void k_union_match(UnionArgs a)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= a.nB) return;
+    const int4 c = *reinterpret_cast<const int4 *>(a.b_coords + (size_t)k * 4);
+    const int b = c.x;
+    int found = -1;
+    if (b >= 0 && b < a.B) {
+        const int v[3] = {c.y >> a.shift, c.z >> a.shift, c.w >> a.shift};
+        const int gi = vox_find(a.keys, a.first, a.mask, b, v);
+        if (gi >= 0) found = (b > 0 ? a.a_end[b - 1] : 0) + (gi - b * a.ncap);
+    }
+    if (found >= a.nA) found = -1;                          // (never from a table over A's rows)
+    a.match[k] = found;
+    if (found >= 0) a.partner[found] = k;                   // B's rows are distinct: one writer per row of A
+}
+
+__global__ __launch_bounds__(256) void k_union_rank(UnionArgs a)
+{
+    __shared__ int s_w[4];
+    const int b = blockIdx.x;
+    const int lo = b > 0 ? a.b_end[b - 1] : 0, hi = a.b_end[b];
+    int run = 0;
+    for (int base = lo; base < hi; base += 256) {
+        const int k = base + threadIdx.x;
+        const bool alone = k < hi && a.match[k] < 0;
+        int total;
+        const int r = block_rank(alone, s_w, total);
+        if (alone) a.rank[k] = run + r;
+        run += total;
+    }
+    if (threadIdx.x == 0) a.extra[b] = run;
+}
+
+__global__ __launch_bounds__(256) void k_union_write(UnionArgs a)
+{
+    __shared__ int s_before[65];                            // unmatched rows of B in the scenes before b; [B]: all of them
+    if (threadIdx.x <= a.B) {
+        int s = 0;
+        for (int b = 0; b < (int)threadIdx.x; ++b) s += a.extra[b];
+        s_before[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // sizes for the host (system scope: the words may be device-mapped pinned host memory it polls); the count last
+        for (int b = 0; b < a.B; ++b)
+            __hip_atomic_store(a.out_scene_end + b, a.a_end[b] + s_before[b + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(a.count_words + 1, a.index_overflow[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(a.count_words, a.nA + s_before[a.B], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    const int c4n = a.C >> 2;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int r = (int)(t / c4n), c4 = (int)(t - (long)r * c4n);
+    if (r >= a.nA + a.nB) return;
+    int4 c;
+    float4 v;
+    int pos;
+    if (r < a.nA) {
+        c = *reinterpret_cast<const int4 *>(a.a_coords + (size_t)r * 4);
+        if (c.x < 0 || c.x >= a.B) return;                  // (a row outside every scene: the caller's ends do not cover it)
+        pos = r + s_before[c.x];
+        v = ld4(a.a_feats + (size_t)r * a.C + c4 * 4);
+        const int p = a.partner[r];
+        if (p >= 0 && p < a.nB) v = add4(v, ld4(a.b_feats + (size_t)p * a.C + c4 * 4));
+    } else {
+        const int k = r - a.nA;
+        if (a.match[k] >= 0) return;
+        c = *reinterpret_cast<const int4 *>(a.b_coords + (size_t)k * 4);
+        if (c.x < 0 || c.x >= a.B) return;
+        pos = a.a_end[c.x] + s_before[c.x] + a.rank[k];
+        v = ld4(a.b_feats + (size_t)k * a.C + c4 * 4);
+    }
+    if (pos < 0 || pos >= a.nA + a.nB) return;
+    st4(a.out_feats + (size_t)pos * a.C + c4 * 4, v);
+    if (c4 == 0) *reinterpret_cast<int4 *>(a.out_coords + (size_t)pos * 4) = c;
+}
+
+// ---- prune scores -----------------------------------------------------------------------------------------------------------
+struct ScoreArgs {
+    const int32_t *q_coords; const float *scores; float *out;
+    const unsigned long long *keys; const int32_t *first; unsigned int mask;      // the index table of the score rows
+    int B, ncap, shift, n_q, m;
+    int32_t s_end[64];
+};
+
+__global__ __launch_bounds__(256) void k_prune_scores(ScoreArgs a)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_q) return;
+    const int4 c = *reinterpret_cast<const int4 *>(a.q_coords + (size_t)i * 4);
+    const int b = c.x;
+    float acc = 0.0f;
+    if (b >= 0 && b < a.B) {
+        const int q[3] = {c.y, c.z, c.w};
+        const int l[3] = {c.y >> a.shift, c.z >> a.shift, c.w >> a.shift};        // floor(q / ts)
+        const float inv = 1.0f / (float)(1 << a.shift);
+        const int start = b > 0 ? a.s_end[b - 1] : 0;
+        for (int corner = 0; corner < 8; ++corner) {        // x fastest; ascending: the order of the sum
+            const int v[3] = {l[0] + (corner & 1), l[1] + ((corner >> 1) & 1), l[2] + (corner >> 2)};
+            const int gi = vox_find(a.keys, a.first, a.mask, b, v);
+            if (gi < 0) continue;
+            const int row = start + (gi - b * a.ncap);
+            if (row >= a.m) continue;
+            float w = 1.0f;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) w = w * (1.0f - fabsf((float)(q[d] - v[d] * (1 << a.shift))) * inv);
+            acc = acc + w * a.scores[row];
+        }
+    }
+    a.out[i] = acc;
+}
+
+// ---- top-k prune --------------------------------------------------------------------------------------------------------------
+// the order of the scores as unsigned integers: larger score, larger key; -0.0 and +0.0 share one.  A NaN orders by its bits: above +inf
+// with the sign bit clear, below -inf with it set (neck_host.topk_key restates it)
+__device__ __forceinline__ uint32_t topk_key(float s)
+{
+    uint32_t u = __float_as_uint(s);
+    if ((u << 1) == 0u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+struct TopkArgs {
+    const float *scores; int B, k;
+    int32_t *dest;                                          // (n): the row's place among the kept rows, or -1
+    int32_t in_end[64];
+};
+
+__global__ __launch_bounds__(256) void k_topk_select(TopkArgs a)
+{
+    __shared__ int s_hist[256];
+    __shared__ int s_w[4];
+    __shared__ uint32_t s_prefix;
+    __shared__ int s_need;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int lo = b > 0 ? a.in_end[b - 1] : 0, hi = a.in_end[b];
+    int out0 = 0;                                           // kept rows of the scenes before
+    for (int s = 0, prev = 0; s < b; ++s) {
+        out0 += min(a.in_end[s] - prev, a.k);
+        prev = a.in_end[s];
+    }
+    if (hi - lo <= a.k) {                                   // nothing to prune
+        for (int i = lo + tid; i < hi; i += 256) a.dest[i] = out0 + (i - lo);
+        return;
+    }
+    uint32_t prefix = 0u, known = 0u;                       // the threshold key's bits found so far
+    int need = a.k;                                         // rows still to take among those that match `prefix`
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        s_hist[tid] = 0;
+        __syncthreads();
+        for (int i = lo + tid; i < hi; i += 256) {
+            const uint32_t key = topk_key(a.scores[i]);
+            if ((key & known) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int d = 255, left = need;
+            while (d > 0 && s_hist[d] < left) { left -= s_hist[d]; --d; }
+            s_prefix = prefix | ((uint32_t)d << shift);
+            s_need = left;
+        }
+        __syncthreads();
+        prefix = s_prefix; need = s_need; known |= 255u << shift;
+        __syncthreads();
+    }
+    // prefix: the k-th largest key; need >= 1 of the rows that carry it are kept, the lowest row indices first
+    int run_eq = 0, run_keep = 0;
+    for (int base = lo; base < hi; base += 256) {
+        const int i = base + tid;
+        const uint32_t key = i < hi ? topk_key(a.scores[i]) : 0u;
+        const bool eq = i < hi && key == prefix;
+        int total;
+        const int r_eq = block_rank(eq, s_w, total);
+        const bool keep = i < hi && (key > prefix || (eq && run_eq + r_eq < need));
+        run_eq += total;
+        const int r_keep = block_rank(keep, s_w, total);
+        if (i < hi) a.dest[i] = keep ? out0 + run_keep + r_keep : -1;
+        run_keep += total;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_prune_copy(const int32_t *__restrict__ dest, const int32_t *__restrict__ coords,
+                                                    const float *__restrict__ feats, int n, int C, int n_keep,
+                                                    int32_t *__restrict__ out_coords, float *__restrict__ out_feats)
+{
+    const int c4n = C >> 2;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int r = (int)(t / c4n), c4 = (int)(t - (long)r * c4n);
+    if (r >= n) return;
+    const int d = dest[r];
+    if (d < 0 || d >= n_keep) return;
+    st4(out_feats + (size_t)d * C + c4 * 4, ld4(feats + (size_t)r * C + c4 * 4));
+    if (c4 == 0) *reinterpret_cast<int4 *>(out_coords + (size_t)d * 4) = *reinterpret_cast<const int4 *>(coords + (size_t)r * 4);
+}
+
+// ---- head ---------------------------------------------------------------------------------------------------------------------
+// work-group = 16 rows x 16 lanes; lane l of a row holds channels 4 l + 64 m .. + 3 (m ascending: one 256-B piece of the row per 16
+// lanes and m).  Per class: the lane's products added in ascending channel order, the 16 lanes by xor 8, 4, 2, 1; + bias.
+__global__ __launch_bounds__(256) void k_neck_head(const float *__restrict__ feats, int n, int C, const float *__restrict__ weight,
+                                                   const float *__restrict__ bias, int K, float *__restrict__ cls, float *__restrict__ score)
+{
+    __shared__ __attribute__((aligned(16))) float s_w[kNeckMaxClasses * 512];     // [class][channel]
+    for (int e = threadIdx.x; e < C * K; e += 256) s_w[(e % K) * C + e / K] = weight[e];      // weight (C, K)
+    __syncthreads();
+    const int l = threadIdx.x & 15, row = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int nm = C >> 6;
+    float4 x[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) x[m] = (m < nm && row < n) ? ld4(feats + (size_t)row * C + 64 * m + 4 * l) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float best = -INFINITY;
+    for (int k = 0; k < K; ++k) {
+        float s = 0.0f;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            if (m < nm) {
+                const float4 w = ld4(&s_w[k * C + 64 * m + 4 * l]);
+                s = s + x[m].x * w.x; s = s + x[m].y * w.y; s = s + x[m].z * w.z; s = s + x[m].w * w.w;
+            }
+        }
+        s = s + __shfl_xor(s, 8, 16); s = s + __shfl_xor(s, 4, 16); s = s + __shfl_xor(s, 2, 16); s = s + __shfl_xor(s, 1, 16);
+        if (bias) s = s + bias[k];
+        best = fmaxf(best, s);
+        if (l == 0 && row < n) cls[(size_t)row * K + k] = s;
+    }
+    if (l == 0 && row < n) score[row] = best;
+}
+
+// scene ends: B ascending ints from 0; the last one is returned in n
+static int neck_ends(const char *who, const char *what, const int32_t *ends, int B, int &n, int &ncap)
+{
+    PTX_REQUIRE(ends != nullptr, "%s: %s is null", who, what);
+    int prev = 0;
+    ncap = 1;
+    for (int b = 0; b < B; ++b) {
+        PTX_REQUIRE(ends[b] >= prev, "%s: %s must not decrease", who, what);
+        ncap = ends[b] - prev > ncap ? ends[b] - prev : ncap;
+        prev = ends[b];
+    }
+    n = prev;
+    return PTX_OK;
+}
+
+static int neck_stride_shift(const char *who, int B, int tensor_stride, int &shift)
+{
+    PTX_REQUIRE(B >= 1 && B <= 64 && tensor_stride >= 1 && (tensor_stride & (tensor_stride - 1)) == 0 && tensor_stride <= (1 << 15),
+                "%s: B=%d tensor_stride=%d (B: 1 to 64; tensor_stride: a power of two up to 2^15)", who, B, tensor_stride);
+    shift = 0;
+    while ((1 << shift) < tensor_stride) ++shift;
+    return PTX_OK;
+}
+
+}  // namespace ptx
+
+using namespace ptx;
+
+extern "C" {
+
+size_t ptx_neck_workspace_bytes(int B, int ncap, int rows)
+{
+    if (B < 1 || ncap < 1 || rows < 0 || B > 64 || (long)B * ncap > (1l << 30) || rows > (1 << 30)) return 0;
+    return neck_layout(B, ncap, rows).total;
+}
+
+int ptx_neck_union_add(const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
+                       const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords, float *out_feats,
+                       int32_t *out_scene_end, int32_t *count_words, void *workspace, size_t ws_bytes, void *stream)
+{
+    const char *who = "ptx_neck_union_add";
+    int shift, nA, nB, capA, capB;
+    PTX_TRY(neck_stride_shift(who, B, tensor_stride, shift));
+    PTX_REQUIRE(C >= 4 && C <= 4096 && C % 4 == 0, "%s: C=%d (a multiple of 4 up to 4096)", who, C);
+    PTX_TRY(neck_ends(who, "a_scene_end", a_scene_end, B, nA, capA));
+    PTX_TRY(neck_ends(who, "b_scene_end", b_scene_end, B, nB, capB));
+    PTX_REQUIRE((long)nA + nB < (1l << 30) && (long)B * capA <= (1l << 30), "%s: %d + %d rows is out of range", who, nA, nB);
+    PTX_REQUIRE(out_scene_end && count_words && workspace && (nA + nB == 0 || (out_coords && out_feats)) && (nA == 0 || (a_coords && a_feats)) &&
+                    (nB == 0 || (b_coords && b_feats)), "%s: null argument", who);
+    PTX_REQUIRE(sp_aligned16({a_coords, a_feats, b_coords, b_feats, out_coords, out_feats}) && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+                "%s: coordinates and features must be 16-byte aligned, the workspace 256-byte aligned", who);
+    const int rows = nA > nB ? nA : nB;
+    const NeckLayout L = neck_layout(B, capA, rows);
+    PTX_TRY(sp_workspace_fits(who, ws_bytes, L.total));
+    PTX_TRY(sp_rows_fit(who, nA + nB, C));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    const VoxLayout V = vox_layout(B, capA);
+    PTX_TRY(vox_index_rows(a_coords, a_scene_end, B, capA, shift, ws + L.table, st));
+    if (nA > 0) PTX_HIP(hipMemsetAsync(ws + L.partner, 0xff, (size_t)nA * 4, st));
+    UnionArgs a{a_coords, b_coords, a_feats, b_feats,
+                reinterpret_cast<const unsigned long long *>(ws + L.table + V.keys), reinterpret_cast<const int32_t *>(ws + L.table + V.first),
+                V.slots - 1, reinterpret_cast<const int32_t *>(ws + L.table + V.overflow), B, capA, shift, C, nA, nB,
+                reinterpret_cast<int32_t *>(ws + L.match), reinterpret_cast<int32_t *>(ws + L.partner), reinterpret_cast<int32_t *>(ws + L.rank),
+                reinterpret_cast<int32_t *>(ws + L.extra), out_coords, out_feats, count_words, out_scene_end, {}, {}};
+    for (int b = 0; b < B; ++b) { a.a_end[b] = a_scene_end[b]; a.b_end[b] = b_scene_end[b]; }
+    if (nB > 0) {
+        hipLaunchKernelGGL(k_union_match, dim3(cdiv(nB, 256)), dim3(256), 0, st, a);
+        PTX_LAUNCHED("k_union_match");
+    }
+    hipLaunchKernelGGL(k_union_rank, dim3(B), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_union_rank");
+    const long threads = (long)(nA + nB) * (C / 4);
+    hipLaunchKernelGGL(k_union_write, dim3((unsigned)(threads > 0 ? (threads + 255) / 256 : 1)), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_union_write");
+    return PTX_OK;
+}
+
+int ptx_neck_prune_scores(const int32_t *q_coords, int n_q, const int32_t *s_coords, const int32_t *s_scene_end, int B, int tensor_stride,
+                          const float *scores, float *out, void *workspace, size_t ws_bytes, void *stream)
+{
+    const char *who = "ptx_neck_prune_scores";
+    int shift, m, cap;
+    PTX_TRY(neck_stride_shift(who, B, tensor_stride, shift));
+    PTX_REQUIRE(n_q >= 0 && n_q <= (1 << 30), "%s: n_q=%d", who, n_q);
+    PTX_TRY(neck_ends(who, "s_scene_end", s_scene_end, B, m, cap));
+    PTX_REQUIRE((long)B * cap <= (1l << 30), "%s: %d score rows is out of range", who, m);
+    if (n_q == 0) return PTX_OK;
+    PTX_REQUIRE(q_coords && out && workspace && (m == 0 || (s_coords && scores)), "%s: null argument", who);
+    PTX_REQUIRE(sp_aligned16({q_coords, s_coords}) && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+                "%s: coordinates must be 16-byte aligned, the workspace 256-byte aligned", who);
+    const NeckLayout L = neck_layout(B, cap, 0);
+    PTX_TRY(sp_workspace_fits(who, ws_bytes, L.total));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char *ws = static_cast<char *>(workspace);
+    const VoxLayout V = vox_layout(B, cap);
+    PTX_TRY(vox_index_rows(s_coords, s_scene_end, B, cap, shift, ws + L.table, st));
+    ScoreArgs a{q_coords, scores, out, reinterpret_cast<const unsigned long long *>(ws + L.table + V.keys),
+                reinterpret_cast<const int32_t *>(ws + L.table + V.first), V.slots - 1, B, cap, shift, n_q, m, {}};
+    for (int b = 0; b < B; ++b) a.s_end[b] = s_scene_end[b];
+    hipLaunchKernelGGL(k_prune_scores, dim3(cdiv(n_q, 256)), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_prune_scores");
+    return PTX_OK;
+}
+
+int ptx_neck_topk_prune(const float *scores, const int32_t *scene_end, int B, int k, const int32_t *coords, const float *feats, int C,
+                        int32_t *dest, int32_t *out_coords, float *out_feats, void *stream)
+{
+    const char *who = "ptx_neck_topk_prune";
+    int n, cap;
+    PTX_REQUIRE(B >= 1 && B <= 64 && k >= 1 && C >= 4 && C <= 4096 && C % 4 == 0, "%s: B=%d k=%d C=%d (B: 1 to 64; k >= 1; C: a multiple of 4 up "
+                "to 4096)", who, B, k, C);
+    PTX_TRY(neck_ends(who, "scene_end", scene_end, B, n, cap));
+    if (n == 0) return PTX_OK;
+    PTX_REQUIRE(scores && coords && feats && dest && out_coords && out_feats, "%s: null argument", who);
+    PTX_REQUIRE(sp_aligned16({coords, feats, out_coords, out_feats}), "%s: coordinates and features must be 16-byte aligned", who);
+    PTX_TRY(sp_rows_fit(who, n, C));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    TopkArgs a{scores, B, k, dest, {}};
+    int n_keep = 0;
+    for (int b = 0, prev = 0; b < B; ++b) {
+        a.in_end[b] = scene_end[b];
+        n_keep += scene_end[b] - prev < k ? scene_end[b] - prev : k;
+        prev = scene_end[b];
+    }
+    hipLaunchKernelGGL(k_topk_select, dim3(B), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_topk_select");
+    const long threads = (long)n * (C / 4);
+    hipLaunchKernelGGL(k_prune_copy, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, dest, coords, feats, n, C, n_keep, out_coords,
+                       out_feats);
+    PTX_LAUNCHED("k_prune_copy");
+    return PTX_OK;
+}
+
+int ptx_neck_head(const float *feats, int n, int C, const float *weight, const float *bias, int num_classes, float *cls, float *score,
+                  void *stream)
+{
+    const char *who = "ptx_neck_head";
+    PTX_REQUIRE(n >= 0 && n <= (1 << 30) && sp_width_ok(C) && num_classes >= 1 && num_classes <= kNeckMaxClasses,
+                "%s: n=%d C=%d num_classes=%d (C: a multiple of 64 up to 512; num_classes: 1 to %d)", who, n, C, num_classes, kNeckMaxClasses);
+    if (n == 0) return PTX_OK;
+    PTX_REQUIRE(feats && weight && cls && score, "%s: null argument", who);
+    PTX_REQUIRE(sp_aligned16({feats}), "%s: feats must be 16-byte aligned", who);
+    hipLaunchKernelGGL(k_neck_head, dim3(cdiv(n, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), feats, n, C, weight, bias, num_classes,
+                       cls, score);
+    PTX_LAUNCHED("k_neck_head");
+    return PTX_OK;
+}
+
+}  // extern "C"

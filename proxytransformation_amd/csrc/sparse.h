@@ -9,6 +9,7 @@
 namespace ptx {
 
 constexpr int kSpMaxVol = 27;              // kernel_size <= 3
+constexpr int kSpMaxCin = 1024;            // input channels of the neck's layers (ptx_sparse_conv3d_act, ptx_sparse_conv_transpose_gen)
 // The streaming idiom of the row kernels: a 256-thread work-group owns a tile of kSpTile rows x 64 columns, thread = (row slot =
 // tid >> 4, 4 channels = tid & 15), 16-byte accesses; column sums go through LDS as [16 slots][64 columns], slots added in ascending order.
 constexpr int kSpTile = 256;

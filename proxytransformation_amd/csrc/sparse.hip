@@ -20,6 +20,9 @@
 //       reproducible.
 //       Epilogue in registers: + bias, * scale + shift (a folded eval BatchNorm), + residual, ReLU.
 //   ptx_sparse_max_pool3d   out[o] = max_j feats[nbr[o,j]] over the present neighbours.
+//   ptx_sparse_conv3d_act, ptx_sparse_conv_transpose_gen   the sparse neck's convolutions (neck.py; the rest of the neck is neck.hip):
+//       the same kernel with an activation selector (ELU) and Cin up to 1024, and as a generative transposed convolution (kernel 2,
+//       stride 2: 8 children per row, no table) -- the NECK template parameter of k_sparse_conv.
 //
 // The offset index j (row of `weight`) counts x fastest, then y, then z -- our reading of MinkowskiEngine's region iterator,
 // "parity unpinned" against ME itself, bit-exact against the host restatement (proxytransformation_amd/sparse.py).
@@ -63,28 +66,10 @@ __global__ __launch_bounds__(256) void k_sparse_query(KmapArgs a)
     const int p[3] = {c.y + d[0] * a.ts, c.z + d[1] * a.ts, c.w + d[2] * a.ts};
     const int b = c.x;
     int found = -1;
-    bool ok = b >= 0 && b < a.B;
-    int v[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        v[i] = p[i] >> a.shift;                             // exact: every coordinate is a multiple of ts = 1 << shift
-        ok = ok && v[i] >= -kVoxBias && v[i] < kVoxBias;    // (a neighbour outside the key range cannot be a row)
-    }
-    if (ok) {
-        const unsigned long long key = ((unsigned long long)b << 57) | ((unsigned long long)(v[0] + kVoxBias) << 38) |
-                                       ((unsigned long long)(v[1] + kVoxBias) << 19) | (unsigned long long)(v[2] + kVoxBias);
-        const unsigned long long k1 = key + 1ull;
-        unsigned int slot = vox_hash(key) & a.mask;
-        for (unsigned int probes = 0; probes <= a.mask; ++probes) {     // (the table is at most half full: an empty slot ends it)
-            const unsigned long long cur = a.keys[slot];
-            if (cur == 0ull) break;
-            if (cur == k1) {
-                const int gi = a.first[slot];               // b * ncap + i of the row that claimed the slot
-                found = (b > 0 ? a.in_end[b - 1] : 0) + (gi - b * a.ncap);
-                break;
-            }
-            slot = (slot + 1) & a.mask;
-        }
+    if (b >= 0 && b < a.B) {
+        const int v[3] = {p[0] >> a.shift, p[1] >> a.shift, p[2] >> a.shift};      // exact: every coordinate is a multiple of ts = 1 << shift
+        const int gi = vox_find(a.keys, a.first, a.mask, b, v);                    // b * ncap + i of the row that claimed the slot
+        if (gi >= 0) found = (b > 0 ? a.in_end[b - 1] : 0) + (gi - b * a.ncap);
     }
     a.nbr[t] = found;
 }
@@ -105,14 +90,18 @@ static KmapLayout kmap_layout(int B, int ncap)
 struct SpConvArgs {
     const float *feats; const int32_t *nbr; const float *weight;
     const float *bias, *scale, *shift, *residual; float *out;
-    int n_in, n_out, kvol, Cin, Cout, relu;
+    int n_in, n_out, kvol, Cin, Cout, relu;                 // relu: NECK instantiations read it as the activation selector (0, 1 ReLU, 2 ELU)
 };
 
 // STEM: Cin = 3 (ME.MinkowskiConvolution(3, 64, kernel_size=3, stride=2), mink_resnet.py:57-60): the 27 offsets x 3 channels are one
 // K = 81 panel (weight (27,3,Cout) IS the (81,Cout) matrix), padded with zeros to the two 64-wide steps of the loop below.
 // WT (the backward's dfeats = sum_j gz[nbr_t[:, j]] @ weight[j]^T, sparse_bwd.hip): the slab is read as (kvol, Cout, Cin) of this launch,
 // i.e. k is contiguous in memory already and goes into LDS as 16-byte pieces like the gathered rows; same arithmetic, same order.
-template <bool STEM, bool WT>
+// NECK (the layers of neck.py; the backbone's instantiations are untouched by it): 1 -- the activation behind the epilogue is a selector
+// (0 none, 1 ReLU, 2 ELU alpha = 1: v > 0 ? v : expm1f(v)); 2 -- also GENERATIVE (MinkowskiGenerativeConvolutionTranspose, kernel 2,
+// stride 2): no neighbour table, blockIdx.z = j is the one offset, tile row r reads input row r and writes output row 8 r + j, so the
+// launch is the dense product (n, Cin) @ (Cin, 8 Cout) in the same steps.
+template <bool STEM, bool WT, int NECK = 0>
 __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
 {
     __shared__ __attribute__((aligned(16))) float As[2][64][LDT];       // [k / 32][row][k % 32]: a 64-channel piece of 64 gathered rows
@@ -123,13 +112,15 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
     const int wr = wid >> 1, wc = wid & 1, li = lane & 31, hh = lane >> 5;
     const int row0 = blockIdx.x * 64, col0 = blockIdx.y * 64;
     const int kvol = a.kvol;
-    for (int e = tid; e < 64 * kvol; e += 256) {
+    for (int e = tid; NECK != 2 && e < 64 * kvol; e += 256) {
         int v = row0 + e / kvol < a.n_out ? a.nbr[(size_t)row0 * kvol + e] : -1;
         if (v >= a.n_in) v = -1;                            // (never from ptx_sparse_kernel_map)
         s_nbr[e] = v;
     }
     __syncthreads();
-    if (wid == 0) {                                         // the vote: one ballot over the tile's 64 rows per offset
+    if (NECK == 2) {
+        if (tid == 0) { s_list[0] = blockIdx.z; s_list[kSpMaxVol] = 1; }
+    } else if (wid == 0) {                                         // the vote: one ballot over the tile's 64 rows per offset
         int cnt = 0;
         for (int j = 0; j < kvol; ++j) {
             if (__ballot(s_nbr[lane * kvol + j] >= 0) != 0ull) {
@@ -177,7 +168,7 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
                 }
                 av[i] = make_float4(e[0], e[1], e[2], e[3]);
             } else {
-                const int idx = s_nbr[row * kvol + j];
+                const int idx = NECK == 2 ? (row0 + row < a.n_out ? row0 + row : -1) : s_nbr[row * kvol + j];
                 av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (idx >= 0 && c0 + kq < a.Cin) av[i] = ld4(a.feats + (size_t)idx * a.Cin + c0 + kq);
             }
@@ -218,8 +209,14 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
         if (a.scale) v = v * scale;                         // (-ffp-contract=off: two roundings, like the restatement)
         if (a.shift) v = v + shift;
         if (a.residual) v = v + resv[r];
-        if (a.relu) v = fmaxf(v, 0.0f);
-        if (row < a.n_out) a.out[(size_t)row * a.Cout + n] = v;
+        if (NECK == 0) {
+            if (a.relu) v = fmaxf(v, 0.0f);
+        } else if (a.relu == 1) {
+            v = fmaxf(v, 0.0f);
+        } else if (a.relu == 2) {
+            v = v > 0.0f ? v : expm1f(v);
+        }
+        if (row < a.n_out) a.out[((size_t)row * (NECK == 2 ? 8 : 1) + (NECK == 2 ? blockIdx.z : 0)) * a.Cout + n] = v;
     }
 }
 
@@ -282,6 +279,41 @@ int sparse_conv_transposed(const float *gz, int n_out, const int32_t *nbr_t, int
     return PTX_OK;
 }
 
+// the children of row i: rows 8 i + j at coords[i] + offset j of kernel_offsets(2) at the finer stride `half` (x fastest, then y, then z)
+__global__ __launch_bounds__(256) void k_gen_coords(const int32_t *__restrict__ coords, int n, int half, int32_t *__restrict__ out)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 8 * n) return;
+    int4 c = *reinterpret_cast<const int4 *>(coords + (size_t)(t >> 3) * 4);
+    c.y += (t & 1) * half; c.z += ((t >> 1) & 1) * half; c.w += ((t >> 2) & 1) * half;
+    *reinterpret_cast<int4 *>(out + (size_t)t * 4) = c;
+}
+
+// ptx_sparse_conv3d (NECK 0: Cin up to 512, `act` a flag) and ptx_sparse_conv3d_act (NECK 1: Cin up to kSpMaxCin, `act` the selector):
+// `who` names the one that was called in its messages
+template <int NECK>
+static int sparse_conv(const char *who, int cin_max, const float *feats, int n_in, const int32_t *nbr, int n_out, int kvol, const float *weight,
+                       int Cin, int Cout, const float *bias, const float *scale, const float *shift, const float *residual, int act, float *out,
+                       void *stream)
+{
+    PTX_REQUIRE(n_in >= 0 && n_out >= 0 && (kvol == 1 || kvol == 8 || kvol == 27), "%s: n_in=%d n_out=%d kvol=%d (kvol: 1, 8 or 27)", who, n_in,
+                n_out, kvol);
+    const bool stem = Cin == 3;
+    PTX_REQUIRE(sp_width_ok(Cout) && ((stem && kvol == 27) || (Cin >= 16 && Cin <= cin_max && Cin % 16 == 0)),
+                "%s: Cin=%d Cout=%d kvol=%d (Cin: 3 with 27 offsets, or a multiple of 16 up to %d; Cout: a multiple of 64 up to 512)", who, Cin,
+                Cout, kvol, cin_max);
+    if (n_out == 0) return PTX_OK;
+    PTX_REQUIRE((feats || n_in == 0) && nbr && weight && out, "%s: null argument", who);
+    PTX_REQUIRE(sp_aligned16({feats, weight}), "%s: feats and weight must be 16-byte aligned", who);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const SpConvArgs a{feats, nbr, weight, bias, scale, shift, residual, out, n_in, n_out, kvol, Cin, Cout, act};
+    const dim3 grid(cdiv(n_out, 64), Cout / 64);
+    if (stem) hipLaunchKernelGGL((k_sparse_conv<true, false, NECK>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_sparse_conv<false, false, NECK>), grid, dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_sparse_conv");
+    return PTX_OK;
+}
+
 }  // namespace ptx
 
 using namespace ptx;
@@ -341,21 +373,38 @@ int ptx_sparse_conv3d(const float *feats, int n_in, const int32_t *nbr, int n_ou
                       const float *bias, const float *scale, const float *shift, const float *residual, int relu, float *out,
                       void *stream)
 {
-    PTX_REQUIRE(n_in >= 0 && n_out >= 0 && (kvol == 1 || kvol == 8 || kvol == 27), "ptx_sparse_conv3d: n_in=%d n_out=%d kvol=%d (kvol: 1, 8 or 27)",
-                n_in, n_out, kvol);
-    const bool stem = Cin == 3;
-    PTX_REQUIRE(sp_width_ok(Cout) && ((stem && kvol == 27) || (Cin >= 16 && Cin <= 512 && Cin % 16 == 0)),
-                "ptx_sparse_conv3d: Cin=%d Cout=%d kvol=%d (Cin: 3 with 27 offsets, or a multiple of 16 up to 512; Cout: a multiple of 64 up "
-                "to 512)", Cin, Cout, kvol);
-    if (n_out == 0) return PTX_OK;
-    PTX_REQUIRE((feats || n_in == 0) && nbr && weight && out, "ptx_sparse_conv3d: null argument");
-    PTX_REQUIRE(sp_aligned16({feats, weight}), "ptx_sparse_conv3d: feats and weight must be 16-byte aligned");
+    return sparse_conv<0>("ptx_sparse_conv3d", 512, feats, n_in, nbr, n_out, kvol, weight, Cin, Cout, bias, scale, shift, residual, relu, out,
+                          stream);
+}
+
+int ptx_sparse_conv3d_act(const float *feats, int n_in, const int32_t *nbr, int n_out, int kvol, const float *weight, int Cin, int Cout,
+                          const float *bias, const float *scale, const float *shift, const float *residual, int act, float *out,
+                          void *stream)
+{
+    PTX_REQUIRE(act >= 0 && act <= 2, "ptx_sparse_conv3d_act: act=%d (0 none, 1 ReLU, 2 ELU)", act);
+    return sparse_conv<1>("ptx_sparse_conv3d_act", kSpMaxCin, feats, n_in, nbr, n_out, kvol, weight, Cin, Cout, bias, scale, shift, residual,
+                          act, out, stream);
+}
+
+int ptx_sparse_conv_transpose_gen(const int32_t *coords, int n, int tensor_stride, const float *feats, const float *weight, int Cin, int Cout,
+                                  const float *scale, const float *shift, int act, int32_t *coords_out, float *out, void *stream)
+{
+    PTX_REQUIRE(n >= 0 && n <= (1 << 27) && tensor_stride >= 2 && (tensor_stride & (tensor_stride - 1)) == 0 && tensor_stride <= (1 << 15),
+                "ptx_sparse_conv_transpose_gen: n=%d tensor_stride=%d (at most 2^27 rows; tensor_stride: a power of two from 2 to 2^15)", n,
+                tensor_stride);
+    PTX_REQUIRE(sp_width_ok(Cout) && Cin >= 64 && Cin <= kSpMaxCin && Cin % 64 == 0 && act >= 0 && act <= 2,
+                "ptx_sparse_conv_transpose_gen: Cin=%d Cout=%d act=%d (Cin: a multiple of 64 up to %d; Cout: a multiple of 64 up to 512; act: 0 "
+                "none, 1 ReLU, 2 ELU)", Cin, Cout, act, kSpMaxCin);
+    if (n == 0) return PTX_OK;
+    PTX_REQUIRE(coords && feats && weight && coords_out && out, "ptx_sparse_conv_transpose_gen: null argument");
+    PTX_REQUIRE(sp_aligned16({feats, weight, coords, coords_out}),
+                "ptx_sparse_conv_transpose_gen: coords, feats, weight and coords_out must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const SpConvArgs a{feats, nbr, weight, bias, scale, shift, residual, out, n_in, n_out, kvol, Cin, Cout, relu};
-    const dim3 grid(cdiv(n_out, 64), Cout / 64);
-    if (stem) hipLaunchKernelGGL((k_sparse_conv<true, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_sparse_conv<false, false>), grid, dim3(256), 0, st, a);
-    PTX_LAUNCHED("k_sparse_conv");
+    hipLaunchKernelGGL(k_gen_coords, dim3(cdiv(8 * n, 256)), dim3(256), 0, st, coords, n, tensor_stride / 2, coords_out);
+    PTX_LAUNCHED("k_gen_coords");
+    const SpConvArgs a{feats, nullptr, weight, nullptr, scale, shift, nullptr, out, n, n, 8, Cin, Cout, act};
+    hipLaunchKernelGGL((k_sparse_conv<false, false, 2>), dim3(cdiv(n, 64), Cout / 64, 8), dim3(256), 0, st, a);
+    PTX_LAUNCHED("k_sparse_conv (generative)");
     return PTX_OK;
 }
 

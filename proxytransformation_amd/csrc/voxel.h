@@ -54,6 +54,26 @@ __device__ __forceinline__ unsigned int vox_hash(unsigned long long k)
     return (unsigned int)k;
 }
 
+// The lookup of an index table (vox_index_rows below): first[slot] = b * ncap + i of the row of scene b at voxel v, or -1 when there is
+// none.  Plain loads; a voxel outside the key range cannot be a row.  (The table is at most half full: an empty slot ends the probe.)
+__device__ __forceinline__ int vox_find(const unsigned long long *keys, const int32_t *first, unsigned int mask, int b, const int (&v)[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if (v[i] < -kVoxBias || v[i] >= kVoxBias) return -1;
+    const unsigned long long key = ((unsigned long long)b << 57) | ((unsigned long long)(v[0] + kVoxBias) << 38) |
+                                   ((unsigned long long)(v[1] + kVoxBias) << 19) | (unsigned long long)(v[2] + kVoxBias);
+    const unsigned long long k1 = key + 1ull;
+    unsigned int slot = vox_hash(key) & mask;
+    for (unsigned int probes = 0; probes <= mask; ++probes) {
+        const unsigned long long cur = keys[slot];
+        if (cur == 0ull) break;
+        if (cur == k1) return first[slot];
+        slot = (slot + 1) & mask;
+    }
+    return -1;
+}
+
 struct VoxLayout { size_t zero_begin, keys, owner, tile_word, overflow, zero_bytes, first, slot_of, row_of_slot, total; unsigned int slots; };
 inline VoxLayout vox_layout(int B, int Ncap)
 {

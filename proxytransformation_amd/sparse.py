@@ -38,7 +38,7 @@ eval mode the affine map from the running statistics) are one family of streamin
 normalise -> affine (+ residual)(+ ReLU)", forward and backward, restated in numpy by ``sparse_norm_host`` / ``sparse_norm_bwd_host``.
 The same opt-in rule: inference-only unless ``differentiable=True``.  ``backbone.MinkResNet`` assembles all of this.
 
-Not here (out of scope): ``neck_3d``, double backward, bf16, gradients to ``scale`` / ``shift``, SyncBatchNorm across ranks.  There is no
+``neck_3d`` is ``neck.MinkNeck`` (``neck.py``; eval forward only).  Not here (out of scope): double backward, bf16, gradients to ``scale`` / ``shift``, SyncBatchNorm across ranks.  There is no
 CPU path for the layers themselves: tensors must be on the GPU and the library must be built.
 """
 from __future__ import annotations
@@ -221,10 +221,16 @@ def _transposed(kmap: KernelMap, n_in: int) -> torch.Tensor:
     return kmap.nbr_t
 
 
-def _conv_forward(feats, kmap, weight, vecs, residual, relu) -> torch.Tensor:
+def _conv_forward(feats, kmap, weight, vecs, residual, relu, elu=False) -> torch.Tensor:
     n_out, kvol = kmap.nbr.shape
     cin, cout = int(weight.shape[1]), int(weight.shape[2])
     out = torch.empty((n_out, cout), dtype=torch.float32, device=feats.device)
+    if elu or cin > 512:                                     # the neck's entry point: activation selector, Cin up to 1024
+        _abi.check(_abi.lib().ptx_sparse_conv3d_act(feats.data_ptr(), feats.shape[0], kmap.nbr.data_ptr(), n_out, kvol, weight.data_ptr(), cin,
+                                                    cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(residual),
+                                                    2 if elu else int(bool(relu)), out.data_ptr(),
+                                                    torch.cuda.current_stream(feats.device).cuda_stream), "ptx_sparse_conv3d_act")
+        return out
     _abi.check(_abi.lib().ptx_sparse_conv3d(feats.data_ptr(), feats.shape[0], kmap.nbr.data_ptr(), n_out, kvol, weight.data_ptr(), cin,
                                             cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(residual), int(bool(relu)),
                                             out.data_ptr(), torch.cuda.current_stream(feats.device).cuda_stream), "ptx_sparse_conv3d")
@@ -309,14 +315,20 @@ class _SparseMaxPool3dFn(torch.autograd.Function):
 
 def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
                   scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
-                  residual: Optional[torch.Tensor] = None, relu: bool = False, differentiable: bool = False) -> torch.Tensor:
+                  residual: Optional[torch.Tensor] = None, relu: bool = False, differentiable: bool = False,
+                  elu: bool = False) -> torch.Tensor:
     """``out (n_out, Cout) fp32 = epilogue(sum_j feats[nbr[:, j]] @ weight[j])`` -- one launch of ``ptx_sparse_conv3d`` on the current
     stream.  ``weight (k^3, Cin, Cout)``; epilogue, each part optional: ``+ bias``, ``* scale + shift`` (an eval BatchNorm folded by the
     caller), ``+ residual (n_out, Cout)``, ReLU.  Cout a multiple of 64 up to 512; Cin a multiple of 16 up to 512, or 3 with a 3x3x3
     kernel (the stem).  Inference-only unless ``differentiable=True``: then, with grad mode on and ``feats`` / ``weight`` / ``bias`` /
     ``residual`` requiring grad, the same launch is recorded for autograd (``ptx_sparse_conv3d_bwd``; same output bits) -- Cin a
     multiple of 64 up to 512 or the stem's 3; ``scale`` / ``shift`` are constants (a folded frozen BatchNorm) and must not require
-    grad: the gradient passes through multiplied by ``scale``."""
+    grad: the gradient passes through multiplied by ``scale``.  ``elu=True`` (the neck's layers: ELU with alpha = 1 instead of the ReLU;
+    not both) or ``Cin > 512`` (up to 1024) goes through ``ptx_sparse_conv3d_act``, the same kernel; ``elu`` is inference-only."""
+    if elu and relu:
+        raise ValueError("sparse_conv3d: elu and relu are one activation slot; pass one of them")
+    if elu and differentiable and _wants_grad(feats, weight, bias, residual):
+        raise NotImplementedError("sparse_conv3d(elu=True) is inference-only: the backward pass through the ELU epilogue is not implemented")
     if differentiable and _wants_grad(scale, shift):
         raise ValueError("sparse_conv3d(differentiable=True): scale / shift are the constants of a folded frozen BatchNorm and get no "
                          "gradient, but one of them requires grad; detach them (a training BatchNorm is nn.BatchNorm1d on the rows)")
@@ -337,7 +349,7 @@ def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bi
     if residual is not None and tuple(residual.shape) != (n_out, cout):
         raise ValueError(f"sparse_conv3d: residual must be {(n_out, cout)}, got {tuple(residual.shape)}")
     if not train:
-        return _conv_forward(feats, kmap, weight, vecs, residual, relu)
+        return _conv_forward(feats, kmap, weight, vecs, residual, relu, elu)
     if not ((cin == 3 and kvol == 27) or (64 <= cin <= 512 and cin % 64 == 0)) or not (64 <= cout <= 512 and cout % 64 == 0):
         raise ValueError(f"sparse_conv3d(differentiable=True): Cin={cin} Cout={cout} with {kvol} offsets -- the backward takes Cin a multiple "
                          f"of 64 up to 512 (or 3 with 27 offsets) and Cout a multiple of 64 up to 512")
@@ -602,11 +614,12 @@ class SparseConv3d(nn.Module):
         with torch.no_grad():                                    # mink_resnet.py:79-81: kaiming normal, fan_out, relu
             self.kernel.normal_(0.0, (2.0 / (kvol * self.out_channels)) ** 0.5)
 
-    def forward(self, feats: torch.Tensor, kmap: KernelMap, scale=None, shift=None, residual=None, relu: bool = False) -> torch.Tensor:
+    def forward(self, feats: torch.Tensor, kmap: KernelMap, scale=None, shift=None, residual=None, relu: bool = False,
+                elu: bool = False) -> torch.Tensor:
         if (kmap.kernel_size, kmap.stride) != (self.kernel_size, self.stride):
             raise ValueError(f"SparseConv3d(kernel_size={self.kernel_size}, stride={self.stride}) got a kernel map of "
                              f"kernel_size={kmap.kernel_size}, stride={kmap.stride}")
-        return sparse_conv3d(feats, kmap, self.kernel, self.bias, scale, shift, residual, relu, differentiable=self.differentiable)
+        return sparse_conv3d(feats, kmap, self.kernel, self.bias, scale, shift, residual, relu, differentiable=self.differentiable, elu=elu)
 
     def extra_repr(self) -> str:
         return f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, bias={self.bias is not None}"

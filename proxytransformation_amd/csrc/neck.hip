@@ -265,6 +265,9 @@ __global__ __launch_bounds__(256) void k_prune_copy(const int32_t *__restrict__ 
 // ---- head ---------------------------------------------------------------------------------------------------------------------
 // work-group = 16 rows x 16 lanes; lane l of a row holds channels 4 l + 64 m .. + 3 (m ascending: one 256-B piece of the row per 16
 // lanes and m).  Per class: the lane's products added in ascending channel order, the 16 lanes by xor 8, 4, 2, 1; + bias.
+// score = max over the classes as neck_host.head_host's cls.max(axis=1) has it: a NaN class score, in whichever class, makes the score
+// NaN (fmaxf alone would drop it and hand the prune a finite score, or -inf, for a row whose features went NaN); the maximum of
+// NaN-free class scores is fmaxf's, bit for bit.
 __global__ __launch_bounds__(256) void k_neck_head(const float *__restrict__ feats, int n, int C, const float *__restrict__ weight,
                                                    const float *__restrict__ bias, int K, float *__restrict__ cls, float *__restrict__ score)
 {
@@ -277,6 +280,7 @@ __global__ __launch_bounds__(256) void k_neck_head(const float *__restrict__ fea
 #pragma unroll
     for (int m = 0; m < 8; ++m) x[m] = (m < nm && row < n) ? ld4(feats + (size_t)row * C + 64 * m + 4 * l) : make_float4(0.f, 0.f, 0.f, 0.f);
     float best = -INFINITY;
+    bool any_nan = false;
     for (int k = 0; k < K; ++k) {
         float s = 0.0f;
 #pragma unroll
@@ -289,9 +293,10 @@ __global__ __launch_bounds__(256) void k_neck_head(const float *__restrict__ fea
         s = s + __shfl_xor(s, 8, 16); s = s + __shfl_xor(s, 4, 16); s = s + __shfl_xor(s, 2, 16); s = s + __shfl_xor(s, 1, 16);
         if (bias) s = s + bias[k];
         best = fmaxf(best, s);
+        any_nan = any_nan || s != s;
         if (l == 0 && row < n) cls[(size_t)row * K + k] = s;
     }
-    if (l == 0 && row < n) score[row] = best;
+    if (l == 0 && row < n) score[row] = any_nan ? __builtin_nanf("") : best;
 }
 
 // scene ends: B ascending ints from 0; the last one is returned in n

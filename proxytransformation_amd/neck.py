@@ -177,7 +177,8 @@ def topk_prune(scores: torch.Tensor, coords: torch.Tensor, scene_rows: Sequence[
 
 def neck_head(feats: torch.Tensor, kernel: torch.Tensor, bias: Optional[torch.Tensor] = None):
     """``(cls (n,K) fp32, score (n,) fp32)``: ``feats (n,C) @ kernel (1,C,K) + bias`` and its maximum over the classes in one kernel
-    (``neck_host.head_host``; ``ptx_neck_head``).  C a multiple of 64 up to 512, 1 <= K <= 16."""
+    (``neck_host.head_host``; ``ptx_neck_head``).  C a multiple of 64 up to 512, 1 <= K <= 16.  A NaN class score makes the row's
+    score NaN, as numpy's ``max`` does."""
     _train("neck_head", False, feats, kernel, bias)
     if not feats.is_cuda:
         raise RuntimeError("neck_head (HIP) needs GPU tensors: there is no CPU path")

@@ -181,7 +181,8 @@ def prune_host(keep, coords, scene_rows: Sequence[int], feats):
 
 def head_host(feats, weight, bias=None):
     """``conv_cls`` (kernel 1) and the prune score: ``(cls (n,K), score (n,))`` with ``cls = feats @ weight (C,K) + bias`` and
-    ``score = max_k cls`` in the dtype of ``feats``."""
+    ``score = max_k cls`` in the dtype of ``feats``.  The maximum is numpy's: a NaN class score, in whichever class, makes the score
+    NaN (the kernel complies: a row whose features went NaN must not reach the prune with a finite score)."""
     feats = np.asarray(feats)
     dt = feats.dtype
     cls = feats @ np.asarray(weight, dt).reshape(feats.shape[1], -1)

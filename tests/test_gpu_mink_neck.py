@@ -1,14 +1,11 @@
 """The sparse neck on the device (proxytransformation_amd/neck.py; csrc/neck.hip and the neck instantiations of csrc/sparse.hip) held to
 the numpy restatements of neck_host.py: bit for bit where the operation is exact (coordinates, ends, orders, the union's adds, the score
 lookup, the prune), by ``sparse_util.hold`` (8 x the fp32 CPU chain's error against float64) where it sums."""
-import copy
-
 import numpy as np
 import pytest
 import torch
 
 from proxytransformation_amd import _abi, neck, neck_host, sparse
-from proxytransformation_amd.backbone import SparseLevel
 from tests import neck_util as nu
 from tests import sparse_util as su
 
@@ -16,10 +13,7 @@ pytestmark = pytest.mark.gpu
 ELU = neck_host.ACT_ELU
 
 
-def _bits(got: torch.Tensor, ref: np.ndarray):
-    got = got.cpu().numpy()
-    assert got.shape == ref.shape and got.dtype == ref.dtype, (got.shape, ref.shape, got.dtype, ref.dtype)
-    assert np.array_equal(got.view(np.uint32) if got.dtype == np.float32 else got, ref.view(np.uint32) if ref.dtype == np.float32 else ref)
+_bits = nu.bits
 
 
 # ------------------------------------------------------------------------------------------------------------------ convolution + ELU
@@ -170,38 +164,7 @@ def test_end_to_end_shipped_configuration():
     ``hold``; (b) per pruning step the device's mask and the host's own float64 mask differ only on rows within ``NEAR_TIE * max |score|``
     of the step's k-th score, and on no more rows than that step and scene has near-ties (``neck_util.near_ties``, which the host test caps at
     2 % of k)."""
-    levels, m = nu.e2e_levels(), nu.e2e_neck()
-    dev_levels = [SparseLevel(su.dev(lv.feats), su.dev(lv.coords), lv.scene_rows, lv.tensor_stride) for lv in levels]
-    gm = copy.deepcopy(m).to(su.DEV)
-    keep = []
-    with torch.no_grad():
-        feats, scores, points = gm(dev_levels, 3, keep_out=keep)
-    masks = [k.cpu().numpy() for k in keep]
-    trace = []
-    f64, s64, p64 = m.forward_host(levels, 3, np.float64, keep=masks, trace=trace)
-    f32, s32, _ = m.forward_host(levels, 3, np.float32, keep=masks)
-    assert len(masks) == 3 and len(feats) == 3
-    for b in range(3):
-        _bits(points[b], p64[b])
-        assert feats[b].shape == f64[b].shape and scores[b].shape == s64[b].shape == (f64[b].shape[0], 1)
-    cat = lambda parts: np.concatenate([np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p) for p in parts])      # noqa: E731
-    su.hold("neck feats", cat(feats), cat(f32), cat(f64))
-    su.hold("neck scores", cat(scores), cat(s32), cat(s64))
-    for step, (mask, tr) in enumerate(zip(masks, trace)):
-        s = tr["scores"]
-        margin = nu.NEAR_TIE * float(np.abs(s).max())
-        differ = np.nonzero(mask != tr["keep"])[0]
-        ties = {scene: count for scene, count, _ in nu.near_ties(s, tr["scene_rows"], nu.K_PRUNE)}
-        lo = 0
-        for scene, hi in enumerate(tr["scene_rows"]):
-            if hi - lo > nu.K_PRUNE:
-                kth = np.sort(s[lo:hi])[::-1][nu.K_PRUNE - 1]
-                d = differ[(differ >= lo) & (differ < hi)]
-                print(f"step {step} scene {scene}: {len(d)} rows differ, k-th score {kth:+.4f}")
-                assert (np.abs(s[d] - kth) <= margin).all() and len(d) <= ties[scene] <= 0.02 * nu.K_PRUNE
-            else:
-                assert not ((differ >= lo) & (differ < hi)).any()
-            lo = hi
+    nu.end_to_end(nu.e2e_levels(), nu.e2e_neck(), 3, nu.K_PRUNE)             # (the protocol is shared with tests/test_gpu_neck_regimes.py)
 
 
 # ------------------------------------------------------------------------------------------------------------------ raises

@@ -1,7 +1,8 @@
 """The sparse neck (proxytransformation_amd/neck.py, neck_host.py) pinned without a GPU: the numpy restatements in float64 against
 torch's own ``conv_transpose3d`` / ``grid_sample`` / ``topk``, the union order on a hand-written case, the ``state_dict`` of the shipped
 ``MinkNeck`` against a fixture of the reference's names and shapes, the ABI surface of the new entry points, the inference-only and
-no-CPU-path raises, and the near-tie count of the end-to-end inputs of tests/test_gpu_mink_neck.py."""
+no-CPU-path raises, the near-tie count of the end-to-end inputs of tests/test_gpu_mink_neck.py and tests/test_gpu_neck_regimes.py, and
+the preconditions of the latter's inputs (tests/neck_util.py): what makes each of its cases reach the branch it is there for."""
 import ctypes
 import json
 import math
@@ -247,3 +248,81 @@ def test_end_to_end_inputs_have_few_near_ties():
     assert zero_threshold >= 2
     assert all(p.dtype == np.float32 and p.shape == (f.shape[0], 3) for p, f in zip(points, feats))
     assert all(s.shape == (f.shape[0], 1) and float((s < 0).mean()) > 0.5 for s, f in zip(scores, feats))
+
+
+def test_second_end_to_end_inputs_have_few_near_ties():
+    """The inputs of tests/test_gpu_neck_regimes.py's end-to-end test (``neck_util.e2e_levels_b`` / ``e2e_neck_b``: three classes, k = 520,
+    scenes of 1500 / 0 / 40 / 600 rows), under the same cap of 2 % of k near-ties per step and scene.  The float64 chain gives, per step,
+    the rows before the prune and the near-ties of the pruned scenes: step 0: 64 / 0 / 8 / 512 rows, nothing pruned; step 1: 512 / 0 / 64
+    / 4096, scene 3 pruned, 0 near-ties; step 2: 4096 / 0 / 512 / 4673, scenes 0 and 3 pruned, 0 and 0 near-ties.  The empty scene stays
+    empty, the 40-row scene is never pruned, the 600-row scene is pruned at two of the three steps.  If this fails, change the seed of
+    ``neck_util.e2e_levels_b``, not the cap."""
+    levels, m = nu.e2e_levels_b(), nu.e2e_neck_b()
+    assert m.num_classes == 3 and m.pts_prune_threshold == nu.K_PRUNE_B
+    trace = []
+    feats, scores, points = m.forward_host(levels, 4, np.float64, trace=trace)
+    pruned = []
+    for step in trace:
+        ends = [0] + step["scene_rows"]
+        print("rows", np.diff(ends).tolist())
+        ties = nu.near_ties(step["scores"], step["scene_rows"], nu.K_PRUNE_B)
+        pruned.append([scene for scene, _, _ in ties])
+        assert ends[2] == ends[1] and 0 < ends[3] - ends[2] <= nu.K_PRUNE_B
+        for scene, count, kth in ties:
+            print(f"scene {scene}: k-th score {kth:+.4f}, {count} near-ties")
+            assert count <= 0.02 * nu.K_PRUNE_B, (scene, count)
+    assert pruned == [[], [3], [0, 3]]
+    assert len(feats[1]) == 0 and len(feats[2]) == 1 + 8 + 64 + 512 and len(feats[3]) == 64 + 512 + 2 * nu.K_PRUNE_B
+    assert all(s.shape == (f.shape[0], 3) and p.shape == (f.shape[0], 3) for s, f, p in zip(scores, feats, points))
+    best = np.concatenate(scores).argmax(axis=1)
+    assert all((best == c).mean() > 0.1 for c in range(3))   # the maximum over the classes matters
+
+
+# ------------------------------------------------------------------------------------------------------------------ the regimes' inputs
+@pytest.mark.parametrize("kind", ["positive", "negative", "mixed", "normal"])
+def test_low_byte_scores_split_in_the_last_two_radix_passes(kind):
+    """``neck_util.radix_trace`` restates the four passes; in the low-byte inputs the passes at shift 8 and 0 each see >= 2 occupied
+    digits at every k of the device test (N(0, 1): the passes at shift 24 and 16), and the traced threshold is the k-th largest key."""
+    nu.check_low_byte_passes(kind)
+    if kind == "positive":                                   # the existing test's 16 levels, by contrast, are decided after two passes
+        levels = np.linspace(-1.0, 1.0, 16).astype(np.float32)[np.random.default_rng(12).integers(0, 16, 2000)]
+        assert all(p[0] == 1 for p in nu.radix_trace(levels, 0, 2000, 100)[0][2:])
+
+
+def test_special_scores_put_the_threshold_where_they_say():
+    s, ks = nu.special_scores()
+    key = np.sort(neck_host.topk_key(s))[::-1]
+    pos_nan = neck_host.topk_key(np.array([0x7F800001], np.uint32).view(np.float32))[0]
+    at = lambda x: int(neck_host.topk_key(np.array([x], np.float32))[0])      # noqa: E731
+    assert int(key[ks["+inf"] - 1]) == at(np.inf) and key[ks["+inf"] - 2] == pos_nan and key[1] > key[2]
+    assert int(key[ks["-inf"] - 1]) == at(-np.inf) and int(key[ks["zero"] - 1]) == at(0.0) == at(-0.0) == 1 << 31
+    assert int(key[ks["+denormal"] - 1]) == (1 << 31) + 0x1234 and int(key[ks["-denormal"] - 1]) == 0x7FFFFFFF - 0x1234
+    for k in (ks["+inf"], ks["zero"], ks["-inf"]):            # ties straddle these thresholds: the lower row index wins
+        keep = neck_host.topk_keep_host(s, [len(s)], k)
+        tied = neck_host.topk_key(s) == key[k - 1]
+        assert 0 < keep[tied].sum() < tied.sum() and keep[tied][0] and not keep[tied][-1]
+    assert np.isnan(s).sum() == 4 and (np.abs(s[np.isfinite(s)]) < 1.2e-38).sum() == 10
+
+
+def test_union_regime_inputs_hold_every_scene_kind():
+    a, a_ends, b, b_ends = nu.union_regime_case()
+    kinds = nu.union_kinds(a, a_ends, b, b_ends)
+    assert kinds == [nu.UNION_KINDS[i % 7] for i in range(64)] and len(b) > len(a)
+    a, a_ends, b, b_ends = nu.union_key_range_case()
+    c, e, _ = neck_host.union_add_host(a, a_ends, np.ones((len(a), 4), np.float32), b, b_ends, np.ones((len(b), 4), np.float32))
+    assert e == [6, 9] and c[:, 1:].max() == 4 << 18 and c[:, 1:].min() == -(4 << 18) and c[5].tolist() == [0, 0, 0, 4 << 18]
+    assert len(nu.union_key_range_case(True)[0]) == 7
+
+
+@pytest.mark.parametrize("ts", [8, 32768])
+def test_score_queries_have_inexact_products(ts):
+    corners = nu.check_score_query_case(ts)
+    assert corners.shape[1] == 8
+    for axis in range(3):                                    # the range-edge case: the host sees no alias
+        q, s_coords, s_ends, scores = nu.score_edge_case(axis)
+        ref = neck_host.prune_scores_host(q, s_coords, s_ends, 4, scores)
+        assert (scores == 1e6).sum() == 1 and (0 < ref).all() and (ref < 10).all() and q[:, 1 + axis].min() > 4 * nu.M_VOX
+    q, s_coords, s_ends, scores = nu.score_64_case()
+    ref = neck_host.prune_scores_host(q, s_coords, s_ends, 2, scores)
+    empty = np.diff([0] + s_ends)[q[:, 0]] == 0
+    assert len(s_ends) == 64 and empty.sum() == 16 * 20 and (ref[empty] == 0).all() and (ref[~empty] != 0).mean() > 0.5

@@ -642,6 +642,12 @@ PTX_API int ptx_point_sample_bwd(const float *points, int N, const float *dout, 
 PTX_API int ptx_op_gemm(const void *A, const void *B, float *C, int M, int N, int K, long a_rs, long a_cs, long b_rs, long b_cs,
                 long c_rs, long c_cs, int batch, int inner, long a_s1, long a_s2, long b_s1, long b_s2, long c_s1, long c_s2,
                 int a_dtype, int b_dtype, float alpha, int accumulate, int ksplit, long c_sk, void *stream);
+/* The kernel the same ptx_op_gemm call would take, decided on the host (launches nothing, touches no device): 0 = k_bgemm (64 x 64
+ * MFMA tiles), 1 = k_bthin_out, scalar requests, 2 = k_bthin_out, four k per request, 3 = k_bthin_row; PTX_EINVAL where ptx_op_gemm
+ * refuses the arguments.  ptx_op_gemm dispatches on this very function.  (ABI 13, by addition.) */
+PTX_API int ptx_op_gemm_route(const void *A, const void *B, const float *C, int M, int N, int K, long a_rs, long a_cs, long b_rs,
+                long b_cs, long c_rs, long c_cs, int batch, int inner, long a_s1, long a_s2, long b_s1, long b_s2, long c_s1, long c_s2,
+                int a_dtype, int b_dtype, float alpha, int accumulate, int ksplit, long c_sk);
 /* out (cols,rows) = in (rows,cols)^T */
 PTX_API int ptx_op_transpose(const float *in, int rows, int cols, float *out, void *stream);
 /* out[n] (+)= scale * sum_r f(x[r][n]), accumulated in double; mode 0: x, 1: x*y, 2: x*x, 3: (x - y[n])^2 with y a

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "train_rules.h"
 
 namespace ptx {
 
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(512) void k_sn_moments_finish(const double *__restr
     }
 }
 
-// y = relu(bn(h)); pooled over the K slots (mean, or max with the FIRST arg-max like torch.max)
+// y = relu(bn(h)); pooled over the K slots (mean, or max with the FIRST arg-max like torch.max); NaN as torch keeps it (train_rules.h)
 template <int Q>
 __global__ __launch_bounds__(256) void k_sn_apply(SnArgs a)
 {
@@ -216,8 +217,8 @@ __global__ __launch_bounds__(256) void k_sn_apply(SnArgs a)
         sn_conv<Q>(w, x, k, s, h);
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            const float y = fmaxf((h[q] - mu[q]) * rs[q] * ga[q] + be[q], 0.0f);
-            if (a.maxpool) { if (y > best[q]) { best[q] = y; bi[q] = k; } }
+            const float y = relu_nan((h[q] - mu[q]) * rs[q] * ga[q] + be[q]);
+            if (a.maxpool) { if (max_takes(y, best[q])) { best[q] = y; bi[q] = k; } }
             else best[q] += y;
         }
     }

@@ -339,7 +339,7 @@ __global__ void k_eltwise(int op, const float *__restrict__ a, const float *__re
             case 1: v = av * s; break;
             case 2: v = gelu_exact(av); break;
             case 3: v = b[i] * gelu_exact_g(av); break;
-            case 4: v = fmaxf(av, 0.0f); break;
+            case 4: v = relu_nan(av); break;
             case 5: v = av > 0.0f ? b[i] : 0.0f; break;
             case 6: v = av + b[i % ncol]; break;
             case 7: v = fmaf(s, b[i], av); break;
@@ -363,6 +363,24 @@ __global__ void k_dropout(const float *__restrict__ x, long n, long group, float
 
 // ------------------------------------------------------------------------------ LayerNorm (rows of C <= 512, C % 64 == 0)
 constexpr int kLnMax = 8;
+// d[q] = x[c] - mean for this lane's columns c = lane + 64 q (0 beyond C), centred in two steps: a first mean in plain fp32, then the mean
+// of the residuals x - mean0, which are small and carry the digits the first sum dropped.  One fp32 sum alone is off by about
+// sqrt(C) u |mean|; on rows that sit far from zero (mean 1e3, spread 1) that was 5e-5 of the row's spread in y and in xhat.  Forward
+// and backward centre a row through this one function, so the backward's xhat is the forward's bit for bit.
+__device__ __forceinline__ float ln_centre(const float *__restrict__ xr, int C, int lane, float (&d)[kLnMax])
+{
+    float s = 0.0f;
+#pragma unroll
+    for (int q = 0; q < kLnMax; ++q) { const int c = lane + 64 * q; d[q] = c < C ? xr[c] : 0.0f; s += d[q]; }
+    const float mean0 = wave_sum(s) / (float)C;
+    float r = 0.0f;
+#pragma unroll
+    for (int q = 0; q < kLnMax; ++q) { const int c = lane + 64 * q; d[q] = c < C ? d[q] - mean0 : 0.0f; r += d[q]; }
+    const float md = wave_sum(r) / (float)C;
+#pragma unroll
+    for (int q = 0; q < kLnMax; ++q) { const int c = lane + 64 * q; d[q] = c < C ? d[q] - md : 0.0f; }
+    return mean0 + md;
+}
 __global__ __launch_bounds__(256) void k_ln_fwd(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ b,
                                                 const float *__restrict__ add, int add_rows, int R, int C, float eps,
                                                 float *__restrict__ y, float *__restrict__ stats)
@@ -370,26 +388,25 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const float *__restrict__ x, con
     const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (row >= R) return;
     const int lane = lane_id();
-    float v[kLnMax], s = 0.0f;
-#pragma unroll
-    for (int q = 0; q < kLnMax; ++q) { const int c = lane + 64 * q; v[q] = c < C ? x[(size_t)row * C + c] : 0.0f; s += v[q]; }
-    const float mean = wave_sum(s) / (float)C;
+    float d[kLnMax];
+    const float mean = ln_centre(x + (size_t)row * C, C, lane, d);
     float var = 0.0f;
 #pragma unroll
-    for (int q = 0; q < kLnMax; ++q) { const int c = lane + 64 * q; const float d = c < C ? v[q] - mean : 0.0f; var = fmaf(d, d, var); }
+    for (int q = 0; q < kLnMax; ++q) var = fmaf(d[q], d[q], var);
     const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)C + eps);
     if (lane == 0) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 #pragma unroll
     for (int q = 0; q < kLnMax; ++q) {
         const int c = lane + 64 * q;
         if (c < C) {
-            float o = (v[q] - mean) * rstd * w[c] + b[c];
+            float o = d[q] * rstd * w[c] + b[c];
             if (add) o += add[(size_t)(row % add_rows) * C + c];        // per-slot bias table (PRE:215-217)
             y[(size_t)row * C + c] = o;
         }
     }
 }
-// dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)), g = dy w;  xhat_out = xhat (for dgamma = colsum(dy * xhat))
+// dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)), g = dy w;  xhat_out = xhat (for dgamma = colsum(dy * xhat)).  The row is centred
+// again from x (ln_centre): the mean kept in `stats` is rounded to fp32, half an ulp of 1e3 is 3e-5 of a unit spread
 __global__ __launch_bounds__(256) void k_ln_bwd(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ dy,
                                                 const float *__restrict__ stats, int R, int C, float *__restrict__ dx,
                                                 float *__restrict__ xhat_out)
@@ -397,13 +414,14 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const float *__restrict__ x, con
     const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (row >= R) return;
     const int lane = lane_id();
-    const float mean = stats[2 * row], rstd = stats[2 * row + 1];
+    const float rstd = stats[2 * row + 1];
     float xh[kLnMax], g[kLnMax], s1 = 0.0f, s2 = 0.0f;
+    ln_centre(x + (size_t)row * C, C, lane, xh);
 #pragma unroll
     for (int q = 0; q < kLnMax; ++q) {
         const int c = lane + 64 * q;
         if (c < C) {
-            xh[q] = (x[(size_t)row * C + c] - mean) * rstd;
+            xh[q] = xh[q] * rstd;
             g[q] = dy[(size_t)row * C + c] * w[c];
         } else { xh[q] = 0.0f; g[q] = 0.0f; }
         s1 += g[q]; s2 = fmaf(g[q], xh[q], s2);
@@ -443,7 +461,7 @@ __global__ void k_bn_apply(const float *__restrict__ x, const float *__restrict_
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
         float v = (x[i] - mean_rstd[c]) * mean_rstd[C + c] * w[c] + b[c];
-        y[i] = relu ? fmaxf(v, 0.0f) : v;
+        y[i] = relu ? relu_nan(v) : v;
     }
 }
 // backward, two launches around two column reductions:
@@ -543,7 +561,8 @@ __global__ void k_slot_inputs_bwd(const float *__restrict__ dx6, const uint8_t *
         dcenter[cl * 3] = a; dcenter[cl * 3 + 1] = b; dcenter[cl * 3 + 2] = c;
     }
 }
-// pooling over the K slots of a cluster, h (nclus, K, C): mode 0 mean (PRE:102), 1 max with first-arg-max (PRE:140)
+// pooling over the K slots of a cluster, h (nclus, K, C): mode 0 mean (PRE:102), 1 max with first-arg-max (PRE:140; a NaN wins, the
+// first one gives the arg, as torch.max(dim) returns it)
 __global__ void k_slot_pool(const float *__restrict__ h, long nclus, int K, int C, int mode, float *__restrict__ out,
                             int32_t *__restrict__ arg)
 {
@@ -556,7 +575,7 @@ __global__ void k_slot_pool(const float *__restrict__ h, long nclus, int K, int 
             out[i] = s / (float)K;
         } else {
             float best = hp[0]; int bi = 0;
-            for (int k = 1; k < K; ++k) { const float v = hp[(long)k * C]; if (v > best) { best = v; bi = k; } }
+            for (int k = 1; k < K; ++k) { const float v = hp[(long)k * C]; if (max_takes(v, best)) { best = v; bi = k; } }
             out[i] = best; arg[i] = bi;
         }
     }
@@ -570,7 +589,8 @@ __global__ void k_slot_pool_bwd(const float *__restrict__ dout, const int32_t *_
         dh[i] = mode == 0 ? g / (float)K : (arg[cl * C + c] == k ? g : 0.0f);
     }
 }
-// centres after the offset network: off = tanh(raw) margin; new = clamp(c0 + off, min, max)   (PRE:59-62)
+// centres after the offset network: off = tanh(raw) margin; new = clamp(c0 + off, min, max)   (PRE:59-62; a NaN stays NaN, as
+// torch.max(torch.min(c, max), min) keeps it)
 // grad mask gm = 1 where the clamp is inactive (strictly inside the box), 0.5 on exact ties like torch.min / torch.max
 __global__ void k_offset_apply(const float *__restrict__ c0, const float *__restrict__ raw, const float *__restrict__ minmax,
                                long n, int M, float margin, float *__restrict__ cout, float *__restrict__ dcoef)
@@ -580,8 +600,8 @@ __global__ void k_offset_apply(const float *__restrict__ c0, const float *__rest
         const float t = tanhf(raw[i]);
         const float v = c0[i] + t * margin;
         const float mn = minmax[b * 6 + d], mx = minmax[b * 6 + 3 + d];
-        const float lo = fminf(v, mx);
-        cout[i] = fmaxf(lo, mn);
+        const float lo = min_nan(v, mx);
+        cout[i] = max_nan(lo, mn);
         float gm = v < mx ? 1.0f : (v == mx ? 0.5f : 0.0f);
         gm *= lo > mn ? 1.0f : (lo == mn ? 0.5f : 0.0f);
         dcoef[i] = gm * margin * (1.0f - t * t);           // d cout / d raw
@@ -796,42 +816,69 @@ static inline int blocks_for(long n, int per = 256) { long b = (n + per - 1) / p
 
 using namespace ptx;
 
-extern "C" {
-
-int ptx_op_gemm(const void *A, const void *B, float *C, int M, int N, int K, long a_rs, long a_cs, long b_rs, long b_cs,
-                long c_rs, long c_cs, int batch, int inner, long a_s1, long a_s2, long b_s1, long b_s2, long c_s1, long c_s2,
-                int a_dtype, int b_dtype, float alpha, int accumulate, int ksplit, long c_sk, void *stream)
+// The kernel a ptx_op_gemm call takes, as a pure function of its arguments (no launch, no device): 0 k_bgemm, 1 k_bthin_out scalar,
+// 2 k_bthin_out vector (four k per request), 3 k_bthin_row; PTX_EINVAL where the call is refused.  ptx_op_gemm dispatches on it and
+// ptx_op_gemm_route returns it, so a test of a thin kernel can assert that it ran one.
+static int gemm_route(const void *A, const void *B, const float *C, int M, int N, int K, long a_rs, long a_cs, long b_rs, long b_cs,
+                      long c_rs, long c_cs, int batch, int inner, long a_s1, long a_s2, long b_s1, long b_s2, long c_s1, long c_s2,
+                      int a_dtype, int b_dtype, float alpha, int accumulate, int ksplit, long c_sk)
 {
+    (void)c_rs; (void)c_cs; (void)c_s1; (void)c_s2; (void)alpha; (void)c_sk;
     PTX_REQUIRE(A && B && C && M >= 1 && N >= 1 && K >= 1 && batch >= 1 && inner >= 1 && batch % inner == 0,
                 "ptx_op_gemm: bad arguments (M=%d N=%d K=%d batch=%d inner=%d)", M, N, K, batch, inner);
     PTX_REQUIRE(a_dtype >= 0 && a_dtype <= 2 && b_dtype >= 0 && b_dtype <= 2 && batch <= 65535,
                 "ptx_op_gemm: a_dtype=%d b_dtype=%d batch=%d", a_dtype, b_dtype, batch);
     PTX_REQUIRE(ksplit >= 1 && (long)batch * ksplit <= 65535 && (ksplit == 1 || !accumulate), "ptx_op_gemm: ksplit=%d", ksplit);
-    BGemmArgs g{A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch, inner, a_s1, a_s2, b_s1, b_s2, c_s1, c_s2,
-                a_dtype, b_dtype, alpha, accumulate, ksplit, c_sk};
-    const dim3 grid(cdiv(M, 64), cdiv(N, 64), batch * ksplit);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     PTX_REQUIRE(a_dtype == 0 || b_dtype == 0, "ptx_op_gemm: at most one 16-bit operand (a_dtype=%d, b_dtype=%d)", a_dtype, b_dtype);
     if (a_dtype == 0 && b_dtype == 0 && ksplit == 1 && batch >= 64 && (M <= 2 || N <= 2 || K <= 2)) {
         // thin products of many batches: most of a 64 x 64 MFMA tile would be padding
         const bool al16 = ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
-        if (M <= 2 && N == 32 && b_cs == 1 && K <= 256 && K > 64 && al16 && b_rs % 4 == 0 && b_s1 % 4 == 0 && b_s2 % 4 == 0) {
-            const long rows = (long)batch * M;
-            hipLaunchKernelGGL(k_bthin_row, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, g, rows);
-            PTX_LAUNCHED("k_bthin_row");
-            return PTX_OK;
-        }
+        if (M <= 2 && N == 32 && b_cs == 1 && K <= 256 && K > 64 && al16 && b_rs % 4 == 0 && b_s1 % 4 == 0 && b_s2 % 4 == 0) return 3;
         const long total = (long)batch * M * N;
         if (K <= 64 && total < (1l << 31)) {
             const bool kvec = al16 && a_cs == 1 && b_rs == 1 && K % 4 == 0 && a_rs % 4 == 0 && b_cs % 4 == 0 && a_s1 % 4 == 0 &&
                               a_s2 % 4 == 0 && b_s1 % 4 == 0 && b_s2 % 4 == 0;
-            const dim3 tg((unsigned)((total + 255) / 256));
-            if (kvec) hipLaunchKernelGGL(k_bthin_out<true>, tg, dim3(256), 0, st, g, (unsigned)total);
-            else      hipLaunchKernelGGL(k_bthin_out<false>, tg, dim3(256), 0, st, g, (unsigned)total);
-            PTX_LAUNCHED("k_bthin_out");
-            return PTX_OK;
+            return kvec ? 2 : 1;
         }
     }
+    return 0;
+}
+
+extern "C" {
+
+int ptx_op_gemm_route(const void *A, const void *B, const float *C, int M, int N, int K, long a_rs, long a_cs, long b_rs, long b_cs,
+                      long c_rs, long c_cs, int batch, int inner, long a_s1, long a_s2, long b_s1, long b_s2, long c_s1, long c_s2,
+                      int a_dtype, int b_dtype, float alpha, int accumulate, int ksplit, long c_sk)
+{
+    return gemm_route(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch, inner, a_s1, a_s2, b_s1, b_s2, c_s1, c_s2, a_dtype,
+                      b_dtype, alpha, accumulate, ksplit, c_sk);
+}
+
+int ptx_op_gemm(const void *A, const void *B, float *C, int M, int N, int K, long a_rs, long a_cs, long b_rs, long b_cs,
+                long c_rs, long c_cs, int batch, int inner, long a_s1, long a_s2, long b_s1, long b_s2, long c_s1, long c_s2,
+                int a_dtype, int b_dtype, float alpha, int accumulate, int ksplit, long c_sk, void *stream)
+{
+    const int route = gemm_route(A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch, inner, a_s1, a_s2, b_s1, b_s2, c_s1, c_s2,
+                                 a_dtype, b_dtype, alpha, accumulate, ksplit, c_sk);
+    if (route < 0) return route;
+    BGemmArgs g{A, B, C, M, N, K, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch, inner, a_s1, a_s2, b_s1, b_s2, c_s1, c_s2,
+                a_dtype, b_dtype, alpha, accumulate, ksplit, c_sk};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (route == 3) {
+        const long rows = (long)batch * M;
+        hipLaunchKernelGGL(k_bthin_row, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, g, rows);
+        PTX_LAUNCHED("k_bthin_row");
+        return PTX_OK;
+    }
+    if (route == 1 || route == 2) {
+        const long total = (long)batch * M * N;
+        const dim3 tg((unsigned)((total + 255) / 256));
+        if (route == 2) hipLaunchKernelGGL(k_bthin_out<true>, tg, dim3(256), 0, st, g, (unsigned)total);
+        else            hipLaunchKernelGGL(k_bthin_out<false>, tg, dim3(256), 0, st, g, (unsigned)total);
+        PTX_LAUNCHED("k_bthin_out");
+        return PTX_OK;
+    }
+    const dim3 grid(cdiv(M, 64), cdiv(N, 64), batch * ksplit);
     if (a_dtype == 0 && b_dtype == 0) hipLaunchKernelGGL((k_bgemm<0, 0>), grid, dim3(256), 0, st, g);
     else if (a_dtype == 1) hipLaunchKernelGGL((k_bgemm<1, 0>), grid, dim3(256), 0, st, g);
     else if (a_dtype == 2) hipLaunchKernelGGL((k_bgemm<2, 0>), grid, dim3(256), 0, st, g);
@@ -1002,7 +1049,7 @@ int ptx_op_offset_apply(const float *c0, const float *raw, const float *minmax, 
 
 int ptx_op_slotbias_fwd(const float *pb, const float *pc, const float *pr, int Mk, int s, int C, float *table, void *stream)
 {
-    PTX_REQUIRE(pb && pc && pr && table && Mk >= 1 && s >= 1 && C <= s * s, "ptx_op_slotbias_fwd: bad arguments");
+    PTX_REQUIRE(pb && pc && pr && table && Mk >= 1 && s >= 1 && s <= 23 && C >= 1 && C <= s * s, "ptx_op_slotbias_fwd: bad arguments (s=%d C=%d)", s, C);
     hipLaunchKernelGGL(k_slotbias_fwd, dim3(cdiv(Mk * C, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pb, pc, pr, Mk,
                        s, C, table);
     PTX_LAUNCHED("k_slotbias_fwd");
@@ -1012,7 +1059,7 @@ int ptx_op_slotbias_fwd(const float *pb, const float *pc, const float *pr, int M
 int ptx_op_slotbias_bwd(const float *dtable, int Mk, int s, int C, float *dpb, float *dpc, float *dpr, void *stream)
 {
     PTX_REQUIRE(dtable && dpb && dpc && dpr && Mk >= 1, "ptx_op_slotbias_bwd: bad arguments");
-    PTX_REQUIRE(s <= 23 && C <= 512, "ptx_op_slotbias_bwd: s=%d C=%d", s, C);
+    PTX_REQUIRE(s >= 1 && s <= 23 && C >= 1 && C <= 512 && C <= s * s, "ptx_op_slotbias_bwd: s=%d C=%d", s, C);
     hipLaunchKernelGGL(k_slotbias_bwd, dim3(cdiv(Mk, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), dtable, Mk, s, C, dpb,
                        dpc, dpr);
     PTX_LAUNCHED("k_slotbias_bwd");

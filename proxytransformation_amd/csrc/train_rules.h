@@ -1,5 +1,5 @@
 // What train_ops.hip (one launch per operator) and train_fused.hip (the fused block) must agree on bit for bit: the dropout rule and the
-// exact GELU pair of the training step.  A (seed, element) pair draws the same mask in either file because both read it from here.
+// exact GELU pair of the training step, and the NaN rule of ReLU, clamp and max pooling.  A (seed, element) pair draws the same mask in either file because both read it from here.
 #pragma once
 #include "common.h"
 
@@ -42,5 +42,15 @@ __device__ __forceinline__ float gelu_exact_g(float x)
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));
     return cdf + x * 0.3989422804014327f * expf(-0.5f * x * x);
 }
+
+// ------------------------------------------------------------------------------ NaN rule of the forward values
+// fmaxf / fminf return the other operand when one is NaN; nn.ReLU, torch.min / torch.max and torch.max(dim) of the reference return
+// the NaN (and, for the pooling, the index of the first one).  A diverged run must show NaN here as it does there.  On every other
+// input these give the bits fmaxf / fminf and a plain `>` gave.
+__device__ __forceinline__ float relu_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? a + b : fminf(a, b); }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
+// running first-arg-max: does v replace best?  (best stays once it is NaN: the first NaN keeps the arg)
+__device__ __forceinline__ bool max_takes(float v, float best) { return v > best || (v != v && best == best); }
 
 }  // namespace ptx

@@ -550,6 +550,13 @@ def test_returned_transforms_are_differentiable_in_the_one_node_step(monkeypatch
         assert any(float(v.abs().max()) > 0 for k, v in got.items() if "text_trans" in k)
         assert any(float(v.abs().max()) > 0 for k, v in got.items() if "get_offsets" in k)      # through kcenter
         for k in ref:
+            # the biases of a head's LayerNorm and Linear in front of its batch-statistics BatchNorm1d (PRE:329-330): a constant added to
+            # every row leaves with the batch mean, the true gradient is 0 and both evaluations are cancellation noise under the same bound
+            zero_by_bn = k.split(".")[0] in ("text_norm", "img_norm", "text_trans", "img_trans") and k.endswith(".bias")
+            if zero_by_bn:
+                print(f"{k}: |grad| max one-node {float(got[k].abs().max()):.3e}, per-operator {float(ref[k].abs().max()):.3e}")
+                assert float(got[k].abs().max()) < 1e-5 and float(ref[k].abs().max()) < 1e-5, k
+                continue
             if float(ref[k].abs().max()) < 1e-6:            # e.g. the key bias of the attention pool: a rounding-level zero in the reference too
                 assert float(got[k].abs().max()) < 1e-5, k
                 continue

@@ -490,8 +490,8 @@ PTX_API int ptx_sparse_kernel_map_transpose(const int32_t *nbr, int n_out, int k
  *   matrix instruction, each from zero and added to the chunk's running sum, the chunks' partials added in ascending order.
  * Each of dresidual / dbias / dfeats / dweight is optional (NULL: not computed, and its work is not done).  gz (n_out,Cout) is scratch
  * the call writes; it is needed when (relu or scale) and (dfeats or dweight).  scale / shift get no gradient (a folded frozen BatchNorm).
- * Cout: a multiple of 64 up to 512; Cin: a multiple of 64 up to 512, or 3 with kvol 27 (the stem); kvol 1, 8 or 27; anything else is
- * PTX_EINVAL with the numbers.  workspace: ptx_sparse_conv3d_bwd_workspace_bytes(n_out, kvol, Cin, Cout) bytes (0: unsupported), 16-byte
+ * Cout: a multiple of 64 up to 512; Cin: a multiple of 64 up to 1024 (the neck's out_block_3 is 27 x 1024 -> 256), or 3 with kvol 27
+ * (the stem); kvol 1, 8 or 27; anything else is PTX_EINVAL with the numbers.  workspace: ptx_sparse_conv3d_bwd_workspace_bytes(n_out, kvol, Cin, Cout) bytes (0: unsupported), 16-byte
  * aligned; needed for dbias and dweight.  All float buffers 16-byte aligned; the outputs must not alias the inputs. */
 PTX_API size_t ptx_sparse_conv3d_bwd_workspace_bytes(int n_out, int kvol, int Cin, int Cout);
 PTX_API int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, int relu, const float *feats, int n_in,
@@ -535,6 +535,17 @@ PTX_API int ptx_sparse_norm_apply(const float *x, const int32_t *seg_end, int S,
 PTX_API int ptx_sparse_norm_bwd(const float *g, const float *x, const float *out, const int32_t *seg_end, int S, int n, int C,
                         const float *stats, const float *weight, float *dx, float *dweight, float *dbias, float *dresidual,
                         void *workspace, size_t ws_bytes, void *stream);
+/* The same forward and backward with an activation selector in the place of the ReLU flag (ABI 13, by addition; the neck's training
+ * BatchNorms, mink_neck.py:96-104: MinkowskiBatchNorm + MinkowskiELU): act 0 none, 1 ReLU, 2 ELU with alpha = 1, v > 0 ? v : expm1f(v).
+ * Selectors 0 and 1 give ptx_sparse_norm_fwd's / ptx_sparse_norm_bwd's bits.  Backward: out is the forward's result (needed unless
+ * act == 0); behind an ELU gy = g * (out > 0 ? 1 : out + 1) from the saved out -- exactly 0 where out == -1.  THE NaN RULE: a NaN in
+ * out gives a NaN gy (NaN > 0 is false and g * (NaN + 1) is NaN): it is never dropped, unlike behind a ReLU, where [NaN > 0] = 0. */
+PTX_API int ptx_sparse_norm_fwd_act(const float *x, const int32_t *seg_end, int S, int n, int C, float eps, const float *weight,
+                            const float *bias, const float *residual, int act, float *running_mean, float *running_var, float momentum,
+                            float *stats, float *out, void *workspace, size_t ws_bytes, void *stream);
+PTX_API int ptx_sparse_norm_bwd_act(const float *g, const float *x, const float *out, int act, const int32_t *seg_end, int S, int n, int C,
+                            const float *stats, const float *weight, float *dx, float *dweight, float *dbias, float *dresidual,
+                            void *workspace, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------ the sparse neck: MinkNeck, eval forward (ABI 13, by addition)
  * `feats, scores, coords = self.neck_3d(x, batch_size)` (necks/mink_neck.py:142-161): the generative transposed convolution, the sum
@@ -543,8 +554,8 @@ PTX_API int ptx_sparse_norm_bwd(const float *g, const float *x, const float *out
  * restated in numpy (neck_host.py).  fp32; no float atomics and fixed summation orders: two calls on the same inputs give the same bits;
  * everything is ordered on `stream`; the host waits only for the union's row counts (pinned words, ptx_wait_counts) and never
  * synchronises the device; host checks (PTX_EINVAL / PTX_ENOSPACE with the numbers in the message) come before anything is enqueued.
- * Rows, scene ends ([host] arrays of B ints, B <= 64) and tensor strides are ptx_sparse_kernel_map's.  Forward only: no backward, no
- * training BatchNorm, no bf16.
+ * Rows, scene ends ([host] arrays of B ints, B <= 64) and tensor strides are ptx_sparse_kernel_map's.  These are the forward's entry
+ * points; the backward and the training BatchNorm are the next section's.  No bf16.
  *
  * ptx_sparse_conv3d with `act` a selector -- 0 none, 1 ReLU (ptx_sparse_conv3d's bits), 2 ELU alpha = 1: v > 0 ? v : expm1f(v) -- and
  * Cin a multiple of 16 up to 1024 (or the stem's 3).  The same kernel. */
@@ -590,6 +601,42 @@ PTX_API int ptx_neck_topk_prune(const float *scores, const int32_t *scene_end, i
  * to 512; 1 <= num_classes <= 16.  Fixed order: 16 lanes per row, each its channels 4 l + 64 m ascending, then the lanes by halving. */
 PTX_API int ptx_neck_head(const float *feats, int n, int C, const float *weight, const float *bias, int num_classes, float *cls, float *score,
                   void *stream);
+
+/* ------------------------------------------------------------------ the sparse neck in training mode: the backward (ABI 13, by addition)
+ * The reference trains the neck with its BatchNorms in training mode and prunes under torch.no_grad() (necks/mink_neck.py:163-186):
+ * features and cls_preds carry gradient; the prune scores, the trilinear lookup and the top-k do not.  The chain (mink_neck.py:142-161)
+ * is assembled in Python (neck.MinkNeck(differentiable=True)): every block is a raw convolution followed by ptx_sparse_norm_fwd_act with
+ * the ELU; the convolutions' backward is ptx_sparse_conv3d_bwd.  fp32, no float atomics, fixed summation orders: two calls on the same
+ * inputs give the same bits; everything on `stream`, no host wait; host checks (PTX_EINVAL / PTX_ENOSPACE with the numbers) come first.
+ *
+ * Backward of ptx_sparse_conv_transpose_gen without its epilogue (mink_neck.py:90-94; the BatchNorm is separate), g (8 n,Cout):
+ *   dfeats (n,Cin): dfeats[i] = sum_j g[8 i + j] @ weight[j]^T -- the dense (n, 8 Cout) @ (8 Cout, Cin) product, no table;
+ *   dweight (8,Cin,Cout): dweight[j] = feats^T @ g[j::8], split over row chunks into slabs added in ascending order
+ * on the exact-fp32 matrix instruction, in ptx_sparse_conv3d_bwd's kernels and order.  Each output is optional (NULL).  Cin: a multiple
+ * of 64 up to 1024; Cout: a multiple of 64 up to 512; n <= 2^24.  workspace: ptx_sparse_conv_transpose_gen_bwd_workspace_bytes(n, Cin,
+ * Cout) bytes, a function of the shapes only (0: unsupported), needed for dweight. */
+PTX_API size_t ptx_sparse_conv_transpose_gen_bwd_workspace_bytes(int n, int Cin, int Cout);
+PTX_API int ptx_sparse_conv_transpose_gen_bwd(const float *g, const float *feats, int n, const float *weight, int Cin, int Cout, float *dfeats,
+                                      float *dweight, void *workspace, size_t ws_bytes, void *stream);
+/* ptx_neck_union_add (mink_neck.py:149) that also records where every input row went: a_dest (nA) / b_dest (nB) int32 = the row of the
+ * result that holds A[a] resp. B[k] (a matched pair shares one), -1 for a row outside every scene.  Same results, bit for bit. */
+PTX_API int ptx_neck_union_add_dest(const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
+                            const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords,
+                            float *out_feats, int32_t *out_scene_end, int32_t *count_words, int32_t *a_dest, int32_t *b_dest, void *workspace,
+                            size_t ws_bytes, void *stream);
+/* out (n,C): out[i] = 0 <= dest[i] < n_src ? g[dest[i]] : +0.0 with g (n_src,C), C a multiple of 4; 16-byte accesses, pure copies.  The
+ * backward of the three row routings: dA = g[a_dest], dB = g[b_dest] of the union, and dU of MinkowskiPruning (mink_neck.py:186) from the
+ * dest ptx_neck_topk_prune writes (dropped rows get +0.0).  n == 0: no launch. */
+PTX_API int ptx_neck_rows_gather(const float *g, int n_src, const int32_t *dest, int n, int C, float *out, void *stream);
+/* Backward of conv_cls in ptx_neck_head (mink_neck.py:122-126, 200), given dcls (n,num_classes); the prune score is detached (the
+ * reference takes it under no_grad).  dfeats (n,C) = dcls @ weight^T, the classes added in ascending order; dweight (C,num_classes) =
+ * feats^T @ dcls and dbias (num_classes) = sum_rows dcls: partials per 256-row tile (four 64-row groups in ascending row order, the groups
+ * in ascending order), the tiles added in ascending order; these sums over all rows are kept in double (the products are exact there)
+ * and rounded to fp32 once.  Each output optional (NULL).  C: a multiple of 64 up to 512;
+ * 1 <= num_classes <= 16.  workspace: ptx_neck_head_bwd_workspace_bytes(n, C, num_classes) bytes (0: unsupported), for dweight / dbias. */
+PTX_API size_t ptx_neck_head_bwd_workspace_bytes(int n, int C, int num_classes);
+PTX_API int ptx_neck_head_bwd(const float *dcls, const float *feats, const float *weight, int n, int C, int num_classes, float *dfeats,
+                      float *dweight, float *dbias, void *workspace, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/

@@ -197,6 +197,14 @@ SIGNATURES.update({
     "ptx_neck_prune_scores": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _Z, _P]),
     "ptx_neck_topk_prune": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "ptx_neck_head": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "ptx_sparse_norm_fwd_act": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _Z, _P]),
+    "ptx_sparse_norm_bwd_act": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_sparse_conv_transpose_gen_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
+    "ptx_sparse_conv_transpose_gen_bwd": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _Z, _P]),
+    "ptx_neck_union_add_dest": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_neck_rows_gather": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "ptx_neck_head_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
+    "ptx_neck_head_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),

@@ -7,6 +7,8 @@
 //       the unmatched rows of B in B's order (ballot prefix over runs of 256 rows); k_union_write, one thread per (row, 4 channels),
 //       writes A's rows of a scene in A's order (A[a] + B[k] where both exist: one fp32 add), then B's unmatched rows, and publishes the
 //       row count and the scene ends through pinned words like k_sparse_query.
+//       ptx_neck_union_add_dest also records a_dest (nA) / b_dest (nB), the output row of every input row (-1: a row outside every
+//       scene), for the backward (neck_bwd.hip).
 //   ptx_neck_prune_scores   `scores.features_at_coordinates(x.C.float())` (mink_neck.py:175): trilinear lookup of the coarser level's
 //       (m,1) score at the finer level's coordinates: the same table over the score rows, one thread per query, eight probes, the
 //       present corners added in ascending corner index.
@@ -64,6 +66,7 @@ struct UnionArgs {
     int B, ncap, shift, C, nA, nB;
     int32_t *match, *partner, *rank, *extra;               // extra[b]: unmatched rows of B in scene b
     int32_t *out_coords; float *out_feats; int32_t *count_words, *out_scene_end;
+    int32_t *a_dest, *b_dest;                              // (nA) / (nB): the output row of every input row, both or neither
     int32_t a_end[64], b_end[64];
 };
 
@@ -131,6 +134,10 @@ __global__ __launch_bounds__(256) void k_union_write(UnionArgs a)
         v = ld4(a.a_feats + (size_t)r * a.C + c4 * 4);
         const int p = a.partner[r];
         if (p >= 0 && p < a.nB) v = add4(v, ld4(a.b_feats + (size_t)p * a.C + c4 * 4));
+        if (a.a_dest && c4 == 0 && pos >= 0 && pos < a.nA + a.nB) {
+            a.a_dest[r] = pos;
+            if (p >= 0 && p < a.nB) a.b_dest[p] = pos;
+        }
     } else {
         const int k = r - a.nA;
         if (a.match[k] >= 0) return;
@@ -138,6 +145,7 @@ __global__ __launch_bounds__(256) void k_union_write(UnionArgs a)
         if (c.x < 0 || c.x >= a.B) return;
         pos = a.a_end[c.x] + s_before[c.x] + a.rank[k];
         v = ld4(a.b_feats + (size_t)k * a.C + c4 * 4);
+        if (a.b_dest && c4 == 0 && pos >= 0 && pos < a.nA + a.nB) a.b_dest[k] = pos;
     }
     if (pos < 0 || pos >= a.nA + a.nB) return;
     st4(a.out_feats + (size_t)pos * a.C + c4 * 4, v);
@@ -327,19 +335,12 @@ static int neck_stride_shift(const char *who, int B, int tensor_stride, int &shi
 
 using namespace ptx;
 
-extern "C" {
-
-size_t ptx_neck_workspace_bytes(int B, int ncap, int rows)
+// ptx_neck_union_add and, with a_dest / b_dest, ptx_neck_union_add_dest; `who` names the one that was called in its messages
+static int neck_union_add(const char *who, const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
+                          const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords,
+                          float *out_feats, int32_t *out_scene_end, int32_t *count_words, int32_t *a_dest, int32_t *b_dest, void *workspace,
+                          size_t ws_bytes, void *stream)
 {
-    if (B < 1 || ncap < 1 || rows < 0 || B > 64 || (long)B * ncap > (1l << 30) || rows > (1 << 30)) return 0;
-    return neck_layout(B, ncap, rows).total;
-}
-
-int ptx_neck_union_add(const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
-                       const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords, float *out_feats,
-                       int32_t *out_scene_end, int32_t *count_words, void *workspace, size_t ws_bytes, void *stream)
-{
-    const char *who = "ptx_neck_union_add";
     int shift, nA, nB, capA, capB;
     PTX_TRY(neck_stride_shift(who, B, tensor_stride, shift));
     PTX_REQUIRE(C >= 4 && C <= 4096 && C % 4 == 0, "%s: C=%d (a multiple of 4 up to 4096)", who, C);
@@ -359,11 +360,13 @@ int ptx_neck_union_add(const int32_t *a_coords, const int32_t *a_scene_end, cons
     const VoxLayout V = vox_layout(B, capA);
     PTX_TRY(vox_index_rows(a_coords, a_scene_end, B, capA, shift, ws + L.table, st));
     if (nA > 0) PTX_HIP(hipMemsetAsync(ws + L.partner, 0xff, (size_t)nA * 4, st));
+    if (a_dest && nA > 0) PTX_HIP(hipMemsetAsync(a_dest, 0xff, (size_t)nA * 4, st));       // -1: a row outside every scene goes nowhere
+    if (b_dest && nB > 0) PTX_HIP(hipMemsetAsync(b_dest, 0xff, (size_t)nB * 4, st));
     UnionArgs a{a_coords, b_coords, a_feats, b_feats,
                 reinterpret_cast<const unsigned long long *>(ws + L.table + V.keys), reinterpret_cast<const int32_t *>(ws + L.table + V.first),
                 V.slots - 1, reinterpret_cast<const int32_t *>(ws + L.table + V.overflow), B, capA, shift, C, nA, nB,
                 reinterpret_cast<int32_t *>(ws + L.match), reinterpret_cast<int32_t *>(ws + L.partner), reinterpret_cast<int32_t *>(ws + L.rank),
-                reinterpret_cast<int32_t *>(ws + L.extra), out_coords, out_feats, count_words, out_scene_end, {}, {}};
+                reinterpret_cast<int32_t *>(ws + L.extra), out_coords, out_feats, count_words, out_scene_end, a_dest, b_dest, {}, {}};
     for (int b = 0; b < B; ++b) { a.a_end[b] = a_scene_end[b]; a.b_end[b] = b_scene_end[b]; }
     if (nB > 0) {
         hipLaunchKernelGGL(k_union_match, dim3(cdiv(nB, 256)), dim3(256), 0, st, a);
@@ -375,6 +378,32 @@ int ptx_neck_union_add(const int32_t *a_coords, const int32_t *a_scene_end, cons
     hipLaunchKernelGGL(k_union_write, dim3((unsigned)(threads > 0 ? (threads + 255) / 256 : 1)), dim3(256), 0, st, a);
     PTX_LAUNCHED("k_union_write");
     return PTX_OK;
+}
+
+extern "C" {
+
+size_t ptx_neck_workspace_bytes(int B, int ncap, int rows)
+{
+    if (B < 1 || ncap < 1 || rows < 0 || B > 64 || (long)B * ncap > (1l << 30) || rows > (1 << 30)) return 0;
+    return neck_layout(B, ncap, rows).total;
+}
+
+int ptx_neck_union_add(const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
+                       const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords, float *out_feats,
+                       int32_t *out_scene_end, int32_t *count_words, void *workspace, size_t ws_bytes, void *stream)
+{
+    return neck_union_add("ptx_neck_union_add", a_coords, a_scene_end, a_feats, b_coords, b_scene_end, b_feats, B, tensor_stride, C, out_coords,
+                          out_feats, out_scene_end, count_words, nullptr, nullptr, workspace, ws_bytes, stream);
+}
+
+int ptx_neck_union_add_dest(const int32_t *a_coords, const int32_t *a_scene_end, const float *a_feats, const int32_t *b_coords,
+                            const int32_t *b_scene_end, const float *b_feats, int B, int tensor_stride, int C, int32_t *out_coords,
+                            float *out_feats, int32_t *out_scene_end, int32_t *count_words, int32_t *a_dest, int32_t *b_dest, void *workspace,
+                            size_t ws_bytes, void *stream)
+{
+    PTX_REQUIRE(a_dest && b_dest, "ptx_neck_union_add_dest: a_dest / b_dest is null");
+    return neck_union_add("ptx_neck_union_add_dest", a_coords, a_scene_end, a_feats, b_coords, b_scene_end, b_feats, B, tensor_stride, C,
+                          out_coords, out_feats, out_scene_end, count_words, a_dest, b_dest, workspace, ws_bytes, stream);
 }
 
 int ptx_neck_prune_scores(const int32_t *q_coords, int n_q, const int32_t *s_coords, const int32_t *s_scene_end, int B, int tensor_stride,

@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void k_sparse_conv(SpConvArgs a)
     const int row0 = blockIdx.x * 64, col0 = blockIdx.y * 64;
     const int kvol = a.kvol;
     for (int e = tid; NECK != 2 && e < 64 * kvol; e += 256) {
-        int v = row0 + e / kvol < a.n_out ? a.nbr[(size_t)row0 * kvol + e] : -1;
+        int v = -1;
+        // WT without a table: the generative map, row i reads 8 i + j
+        if (row0 + e / kvol < a.n_out) v = (WT && a.nbr == nullptr) ? row0 * kvol + e : a.nbr[(size_t)row0 * kvol + e];
         if (v >= a.n_in) v = -1;                            // (never from ptx_sparse_kernel_map)
         s_nbr[e] = v;
     }

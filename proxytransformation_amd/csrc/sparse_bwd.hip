@@ -15,6 +15,10 @@
 //                            zero, then added to the running sum.  S > 1: every work-group writes its 64 x 64 partial into slab
 //                            blockIdx.x of the workspace (a chunk without a pair writes zeros: no memset), k_sparse_slab_sum adds the
 //                            slabs in ascending order.  Cin = 3: k_sparse_dweight_stem, VALU, 64-row blocks from zero.
+//   ptx_sparse_conv_transpose_gen_bwd the same two products for the generative transposed convolution (kernel 2, stride 2: output row
+//       8 i + j is child j of input row i), without tables: dfeats[i] = sum_j g[8 i + j] @ kernel[j]^T is the dense (n, 8 Cout) @
+//       (8 Cout, Cin) product through k_sparse_conv<WT>, dkernel[j] = feats^T @ g[j::8] through k_sparse_dweight with its slabs; both
+//       kernels form the map from the row index where the table pointer is null.
 //   ptx_sparse_max_pool3d_bwd         routes each gradient to the offset ptx_sparse_max_pool3d_arg (sparse.hip) recorded.
 //
 // No float atomics anywhere: every output is bitwise reproducible.  Everything runs on the caller's stream; no host wait.
@@ -110,7 +114,8 @@ __global__ __launch_bounds__(256) void k_sparse_dweight(SpDwArgs a)
         int cnt = 0;                                        // work-group uniform
         for (int pass = 0; pass < kDwSub / 256 && sub + pass * 256 < r1; ++pass) {
             const int o = sub + pass * 256 + tid;
-            int idx = o < r1 ? a.nbr[(size_t)o * a.kvol + j] : -1;
+            int idx = -1;
+            if (o < r1) idx = a.nbr ? a.nbr[(size_t)o * a.kvol + j] : ((o & 7) == j ? o >> 3 : -1);      // no table: the generative map
             if (idx >= a.n_in) idx = -1;                    // (never from ptx_sparse_kernel_map)
             const unsigned long long vote = __ballot(idx >= 0);
             if (lane == 0) s_wcnt[wid] = __popcll(vote);
@@ -285,7 +290,7 @@ struct DwPlan { int R, S; size_t slab, dw_bytes, part_bytes, total; };
 static bool bwd_widths_ok(int kvol, int Cin, int Cout)
 {
     const bool stem = Cin == 3 && kvol == 27;
-    return (kvol == 1 || kvol == 8 || kvol == 27) && sp_width_ok(Cout) && (stem || sp_width_ok(Cin));
+    return (kvol == 1 || kvol == 8 || kvol == 27) && sp_width_ok(Cout) && (stem || (Cin >= 64 && Cin <= kSpMaxCin && Cin % 64 == 0));
 }
 static DwPlan dw_plan(int n_out, int kvol, int Cin, int Cout)
 {
@@ -337,29 +342,31 @@ size_t ptx_sparse_conv3d_bwd_workspace_bytes(int n_out, int kvol, int Cin, int C
     return dw_plan(n_out, kvol, Cin, Cout).total;
 }
 
-int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, int relu, const float *feats, int n_in, const int32_t *nbr,
-                          const int32_t *nbr_t, int n_out, int kvol, const float *weight, int Cin, int Cout, float *gz, float *dresidual,
-                          float *dbias, float *dfeats, float *dweight, void *workspace, size_t ws_bytes, void *stream)
+// ptx_sparse_conv3d_bwd and, with `gen` (no tables: output row o = 8 i + j is child j of input row i, kvol = 8, no epilogue),
+// ptx_sparse_conv_transpose_gen_bwd; `who` names the one that was called in its messages
+static int conv_bwd(const char *who, bool gen, const float *g, const float *out, const float *scale, int relu, const float *feats, int n_in,
+                    const int32_t *nbr, const int32_t *nbr_t, int n_out, int kvol, const float *weight, int Cin, int Cout, float *gz,
+                    float *dresidual, float *dbias, float *dfeats, float *dweight, void *workspace, size_t ws_bytes, void *stream)
 {
     PTX_REQUIRE(n_in >= 0 && n_out >= 0 && bwd_widths_ok(kvol, Cin, Cout),
-                "ptx_sparse_conv3d_bwd: n_in=%d n_out=%d Cin=%d Cout=%d kvol=%d (kvol: 1, 8 or 27; Cin: 3 with 27 offsets, or a multiple of 64 "
-                "up to 512; Cout: a multiple of 64 up to 512)", n_in, n_out, Cin, Cout, kvol);
-    PTX_REQUIRE((long)n_out * kvol < (1l << 31) && (long)n_in * kvol < (1l << 31), "ptx_sparse_conv3d_bwd: %d / %d rows x %d offsets is out of range",
-                n_out, n_in, kvol);
+                "%s: n_in=%d n_out=%d Cin=%d Cout=%d kvol=%d (kvol: 1, 8 or 27; Cin: 3 with 27 offsets, or a multiple of 64 "
+                "up to %d; Cout: a multiple of 64 up to 512)", who, n_in, n_out, Cin, Cout, kvol, kSpMaxCin);
+    PTX_REQUIRE((long)n_out * kvol < (1l << 31) && (long)n_in * kvol < (1l << 31), "%s: %d / %d rows x %d offsets is out of range", who, n_out,
+                n_in, kvol);
     const bool stem = Cin == 3, epi = relu != 0 || scale != nullptr;
     const bool need_z = dfeats != nullptr || dweight != nullptr;       // the GEMMs read gz
-    PTX_REQUIRE(g || n_out == 0, "ptx_sparse_conv3d_bwd: g is null");
-    PTX_REQUIRE(!relu || out || n_out == 0, "ptx_sparse_conv3d_bwd: relu needs the forward's out");
-    PTX_REQUIRE(!(epi && need_z) || gz || n_out == 0, "ptx_sparse_conv3d_bwd: gz is needed with relu / scale when dfeats or dweight is asked for");
-    PTX_REQUIRE(!dfeats || ((nbr_t && weight) || n_out == 0 || n_in == 0), "ptx_sparse_conv3d_bwd: dfeats needs nbr_t and weight");
-    PTX_REQUIRE(!dweight || ((nbr && feats) || n_out == 0 || n_in == 0), "ptx_sparse_conv3d_bwd: dweight needs nbr and feats");
+    PTX_REQUIRE(g || n_out == 0, "%s: g is null", who);
+    PTX_REQUIRE(!relu || out || n_out == 0, "%s: relu needs the forward's out", who);
+    PTX_REQUIRE(!(epi && need_z) || gz || n_out == 0, "%s: gz is needed with relu / scale when dfeats or dweight is asked for", who);
+    PTX_REQUIRE(!dfeats || (((nbr_t || gen) && weight) || n_out == 0 || n_in == 0), "%s: dfeats needs nbr_t and weight", who);
+    PTX_REQUIRE(!dweight || (((nbr || gen) && feats) || n_out == 0 || n_in == 0), "%s: dweight needs nbr and feats", who);
     PTX_REQUIRE(sp_aligned16({g, out, scale, feats, weight, gz, dresidual, dfeats, dweight, workspace}),
-                "ptx_sparse_conv3d_bwd: every float buffer and the workspace must be 16-byte aligned");
+                "%s: every float buffer and the workspace must be 16-byte aligned", who);
     const DwPlan P = dw_plan(n_out, kvol, Cin, Cout);
     const bool use_ws = dbias != nullptr || (dweight != nullptr && P.S > 1);
     if (use_ws && n_out > 0) {
-        PTX_REQUIRE(workspace, "ptx_sparse_conv3d_bwd: workspace is null");
-        PTX_TRY(sp_workspace_fits("ptx_sparse_conv3d_bwd", ws_bytes, P.total));
+        PTX_REQUIRE(workspace, "%s: workspace is null", who);
+        PTX_TRY(sp_workspace_fits(who, ws_bytes, P.total));
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n_out == 0 || n_in == 0) {                          // no pair anywhere
@@ -408,6 +415,32 @@ int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, 
         }
     }
     return PTX_OK;
+}
+
+int ptx_sparse_conv3d_bwd(const float *g, const float *out, const float *scale, int relu, const float *feats, int n_in, const int32_t *nbr,
+                          const int32_t *nbr_t, int n_out, int kvol, const float *weight, int Cin, int Cout, float *gz, float *dresidual,
+                          float *dbias, float *dfeats, float *dweight, void *workspace, size_t ws_bytes, void *stream)
+{
+    return conv_bwd("ptx_sparse_conv3d_bwd", false, g, out, scale, relu, feats, n_in, nbr, nbr_t, n_out, kvol, weight, Cin, Cout, gz, dresidual,
+                    dbias, dfeats, dweight, workspace, ws_bytes, stream);
+}
+
+// the generative transposed convolution's rows: n parents, 8 n children; 8 n x 8 offsets must stay below 2^31
+static bool gen_rows_ok(int n) { return n >= 0 && n <= (1 << 24); }
+
+size_t ptx_sparse_conv_transpose_gen_bwd_workspace_bytes(int n, int Cin, int Cout)
+{
+    if (!gen_rows_ok(n) || Cin == 3 || !bwd_widths_ok(8, Cin, Cout)) return 0;
+    return dw_plan(8 * n, 8, Cin, Cout).total;
+}
+
+int ptx_sparse_conv_transpose_gen_bwd(const float *g, const float *feats, int n, const float *weight, int Cin, int Cout, float *dfeats,
+                                      float *dweight, void *workspace, size_t ws_bytes, void *stream)
+{
+    PTX_REQUIRE(gen_rows_ok(n) && Cin != 3, "ptx_sparse_conv_transpose_gen_bwd: n=%d Cin=%d (at most 2^24 rows; Cin: a multiple of 64 up to %d)", n,
+                Cin, kSpMaxCin);
+    return conv_bwd("ptx_sparse_conv_transpose_gen_bwd", true, g, nullptr, nullptr, 0, feats, n, nullptr, nullptr, 8 * n, 8, weight, Cin, Cout,
+                    nullptr, nullptr, nullptr, dfeats, dweight, workspace, ws_bytes, stream);
 }
 
 int ptx_sparse_max_pool3d_bwd(const float *g, const uint8_t *arg, const int32_t *nbr_t, int n_in, int n_out, int kvol, int C, float *dfeats,

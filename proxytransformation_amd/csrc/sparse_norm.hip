@@ -18,6 +18,10 @@
 //                                     dbias / dweight = the segments' sums in ascending order;
 //             k_sparse_norm_bwd_apply dx = weight * rstd * ((gy - a) - xhat * b).
 //
+// The _act entry points (the neck's training BatchNorms) put an activation selector in the place of the ReLU flag: 0 none, 1 ReLU,
+// 2 ELU with alpha = 1, v > 0 ? v : expm1f(v).  Backward of the ELU from the saved result: gy = g * (out > 0 ? 1 : out + 1) -- a NaN out
+// gives a NaN gy and is never dropped.  Selectors 0 and 1 run the instantiations the older entry points run.
+//
 // No float atomics, a fixed order everywhere: two calls on the same inputs give the same bits.  The variance is never E[x^2] - E[x]^2.
 // Everything runs on the caller's stream; no host wait.
 #include "sparse.h"
@@ -148,7 +152,15 @@ __global__ __launch_bounds__(256) void k_sparse_norm_finalise(const float *__res
     }
 }
 
-// grid (tiles, C / 64).  weight / bias (C) and residual (n, C) each optional
+// d *= (o > 0 ? 1 : o + 1): the gradient behind an ELU (alpha = 1) whose result was o; a NaN o makes d NaN
+__device__ __forceinline__ void elu_mask4(float4 &d, const float4 &o)
+{
+    d.x = o.x > 0.0f ? d.x : d.x * (o.x + 1.0f); d.y = o.y > 0.0f ? d.y : d.y * (o.y + 1.0f);
+    d.z = o.z > 0.0f ? d.z : d.z * (o.z + 1.0f); d.w = o.w > 0.0f ? d.w : d.w * (o.w + 1.0f);
+}
+
+// grid (tiles, C / 64).  weight / bias (C) and residual (n, C) each optional.  ELU: the activation is the ELU, `relu` is not read
+template <bool ELU>
 __global__ __launch_bounds__(256) void k_sparse_norm_apply(const float *__restrict__ x, SnSegs sg, int C, const float *__restrict__ stats,
                                                            const float *__restrict__ weight, const float *__restrict__ bias,
                                                            const float *__restrict__ residual, int relu, float *__restrict__ out)
@@ -170,14 +182,18 @@ __global__ __launch_bounds__(256) void k_sparse_norm_apply(const float *__restri
         if (weight) scale4(y, w);
         if (bias) acc4(y, b);
         if (residual) acc4(y, ld4(residual + at));
-        if (relu) { y.x = fmaxf(y.x, 0.0f); y.y = fmaxf(y.y, 0.0f); y.z = fmaxf(y.z, 0.0f); y.w = fmaxf(y.w, 0.0f); }
+        if (ELU) {
+            y.x = y.x > 0.0f ? y.x : expm1f(y.x); y.y = y.y > 0.0f ? y.y : expm1f(y.y);
+            y.z = y.z > 0.0f ? y.z : expm1f(y.z); y.w = y.w > 0.0f ? y.w : expm1f(y.w);
+        } else if (relu) { y.x = fmaxf(y.x, 0.0f); y.y = fmaxf(y.y, 0.0f); y.z = fmaxf(y.z, 0.0f); y.w = fmaxf(y.w, 0.0f); }
         st4(out + at, y);
     }
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------
 // grid (tiles, C / 64).  part (tiles, 2, C): sum gy and sum gy * xhat of the tile; out: the forward's result when it had a ReLU, else
-// null; dres (n, C) = gy, optional
+// null; dres (n, C) = gy, optional.  ELU: out is the result of an ELU, gy = g * (out > 0 ? 1 : out + 1)
+template <bool ELU>
 __global__ __launch_bounds__(256) void k_sparse_norm_bwd_sums(const float *__restrict__ g, const float *__restrict__ x,
                                                               const float *__restrict__ out, SnSegs sg, int C,
                                                               const float *__restrict__ stats, float *__restrict__ dres,
@@ -196,7 +212,10 @@ __global__ __launch_bounds__(256) void k_sparse_norm_bwd_sums(const float *__res
         if (r >= t.cnt) break;
         const size_t at = (size_t)(t.row0 + r) * C + col;
         float4 d = ld4(g + at);
-        if (out) relu_mask4(d, ld4(out + at));
+        if (out) {
+            if (ELU) elu_mask4(d, ld4(out + at));
+            else relu_mask4(d, ld4(out + at));
+        }
         if (dres) st4(dres + at, d);
         const float4 v = ld4(x + at);
         sa = add4(sa, d);
@@ -269,6 +288,7 @@ __global__ __launch_bounds__(64) void k_sparse_norm_bwd_total(const float *__res
 }
 
 // grid (tiles, C / 64).  gy: dresidual as k_sparse_norm_bwd_sums wrote it (then g / out are not read), else null
+template <bool ELU>
 __global__ __launch_bounds__(256) void k_sparse_norm_bwd_apply(const float *__restrict__ g, const float *__restrict__ x,
                                                                const float *__restrict__ out, const float *__restrict__ gy, SnSegs sg,
                                                                int C, const float *__restrict__ stats, const float *__restrict__ seg,
@@ -291,7 +311,10 @@ __global__ __launch_bounds__(256) void k_sparse_norm_bwd_apply(const float *__re
             d = ld4(gy + at);
         } else {
             d = ld4(g + at);
-            if (out) relu_mask4(d, ld4(out + at));
+            if (out) {
+                if (ELU) elu_mask4(d, ld4(out + at));
+                else relu_mask4(d, ld4(out + at));
+            }
         }
         const float4 v = ld4(x + at);
         st4(dx + at, mul4(k, sub4(sub4(d, a), mul4(mul4(sub4(v, mu), rs), b))));
@@ -335,6 +358,90 @@ static int sn_segments(const char *who, const int32_t *seg_end, int S, int n, in
 
 using namespace ptx;
 
+// both forward entry points (act: 0 none, 1 ReLU, 2 ELU) and both backward ones; `who` names the one that was called in its messages
+static int sn_fwd(const char *who, const float *x, const int32_t *seg_end, int S, int n, int C, float eps, const float *weight, const float *bias,
+                        const float *residual, int act, float *running_mean, float *running_var, float momentum, float *stats, float *out,
+                        void *workspace, size_t ws_bytes, void *stream)
+{
+    SnSegs sg;
+    PTX_TRY(sn_segments(who, seg_end, S, n, C, sg));
+    PTX_REQUIRE(eps >= 0.0f && eps < 1.0f, "%s: eps = %g is outside [0, 1)", who, (double)eps);
+    PTX_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "%s: running_mean and running_var go together", who);
+    if (running_mean) {
+        PTX_REQUIRE(S == 1 && n >= 2, "%s: running statistics need one segment of at least 2 rows, got S=%d n=%d", who, S, n);
+        PTX_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "%s: momentum = %g is outside [0, 1]", who, (double)momentum);
+    }
+    PTX_REQUIRE(stats != nullptr && ((x && out) || n == 0), "%s: null argument (x, out and stats are needed)", who);
+    PTX_REQUIRE(sp_aligned16({x, weight, bias, residual, stats, out, workspace}),
+                "%s: every float buffer and the workspace must be 16-byte aligned", who);
+    const SnPlan P = sn_plan(n, S, C);
+    const int T = sg.tile0[S];
+    if (T > 0) {
+        PTX_REQUIRE(workspace, "%s: workspace is null", who);
+        PTX_TRY(sp_workspace_fits(who, ws_bytes, P.total));
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *part = static_cast<float *>(workspace);
+    if (T > 0) {
+        hipLaunchKernelGGL(k_sparse_norm_stats, dim3(T, C / 64), dim3(256), 0, st, x, sg, C, part);
+        PTX_LAUNCHED("k_sparse_norm_stats");
+    }
+    hipLaunchKernelGGL(k_sparse_norm_finalise, dim3(S, C / 64), dim3(256), 0, st, part, sg, C, eps, stats, running_mean, running_var, momentum);
+    PTX_LAUNCHED("k_sparse_norm_finalise");
+    if (T > 0) {
+        if (act == 2)
+            hipLaunchKernelGGL(k_sparse_norm_apply<true>, dim3(T, C / 64), dim3(256), 0, st, x, sg, C, stats, weight, bias, residual, 0, out);
+        else
+            hipLaunchKernelGGL(k_sparse_norm_apply<false>, dim3(T, C / 64), dim3(256), 0, st, x, sg, C, stats, weight, bias, residual, act != 0, out);
+        PTX_LAUNCHED("k_sparse_norm_apply");
+    }
+    return PTX_OK;
+}
+
+static int sn_bwd(const char *who, bool elu, const float *g, const float *x, const float *out, const int32_t *seg_end, int S, int n, int C,
+                  const float *stats, const float *weight, float *dx, float *dweight, float *dbias, float *dresidual, void *workspace,
+                  size_t ws_bytes, void *stream)
+{
+    SnSegs sg;
+    PTX_TRY(sn_segments(who, seg_end, S, n, C, sg));
+    PTX_REQUIRE(stats != nullptr && ((g && x) || n == 0), "%s: null argument (g, x and stats are needed)", who);
+    PTX_REQUIRE(sp_aligned16({g, x, out, stats, weight, dx, dweight, dbias, dresidual, workspace}),
+                "%s: every float buffer and the workspace must be 16-byte aligned", who);
+    const SnPlan P = sn_plan(n, S, C);
+    PTX_REQUIRE(workspace, "%s: workspace is null", who);
+    PTX_TRY(sp_workspace_fits(who, ws_bytes, P.total));
+    const int T = sg.tile0[S];
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *part = static_cast<float *>(workspace);
+    float *seg = reinterpret_cast<float *>(static_cast<char *>(workspace) + P.part_bytes);
+    float *tot = reinterpret_cast<float *>(static_cast<char *>(workspace) + P.part_bytes + P.seg_bytes);
+    const bool sums = dx != nullptr || dweight != nullptr || dbias != nullptr;
+    if (T > 0 && (sums || dresidual)) {
+        if (elu) hipLaunchKernelGGL(k_sparse_norm_bwd_sums<true>, dim3(T, C / 64), dim3(256), 0, st, g, x, out, sg, C, stats, dresidual, part);
+        else hipLaunchKernelGGL(k_sparse_norm_bwd_sums<false>, dim3(T, C / 64), dim3(256), 0, st, g, x, out, sg, C, stats, dresidual, part);
+        PTX_LAUNCHED("k_sparse_norm_bwd_sums");
+    }
+    if (sums) {
+        hipLaunchKernelGGL(k_sparse_norm_bwd_finalise, dim3(S, C / 64), dim3(256), 0, st, part, sg, C, seg, tot, dbias, dweight);
+        PTX_LAUNCHED("k_sparse_norm_bwd_finalise");
+        if (S > 1 && (dbias || dweight)) {
+            hipLaunchKernelGGL(k_sparse_norm_bwd_total, dim3(C / 64), dim3(64), 0, st, static_cast<const float *>(tot), S, C, dbias, dweight);
+            PTX_LAUNCHED("k_sparse_norm_bwd_total");
+        }
+    }
+    if (T > 0 && dx) {
+        if (elu)
+            hipLaunchKernelGGL(k_sparse_norm_bwd_apply<true>, dim3(T, C / 64), dim3(256), 0, st, g, x, out, static_cast<const float *>(dresidual), sg,
+                               C, stats, seg, weight, dx);
+        else
+            hipLaunchKernelGGL(k_sparse_norm_bwd_apply<false>, dim3(T, C / 64), dim3(256), 0, st, g, x, out, static_cast<const float *>(dresidual), sg,
+                               C, stats, seg, weight, dx);
+        PTX_LAUNCHED("k_sparse_norm_bwd_apply");
+    }
+    return PTX_OK;
+}
+
+
 extern "C" {
 
 size_t ptx_sparse_norm_workspace_bytes(int n, int S, int C)
@@ -347,36 +454,17 @@ int ptx_sparse_norm_fwd(const float *x, const int32_t *seg_end, int S, int n, in
                         const float *residual, int relu, float *running_mean, float *running_var, float momentum, float *stats, float *out,
                         void *workspace, size_t ws_bytes, void *stream)
 {
-    SnSegs sg;
-    PTX_TRY(sn_segments("ptx_sparse_norm_fwd", seg_end, S, n, C, sg));
-    PTX_REQUIRE(eps >= 0.0f && eps < 1.0f, "ptx_sparse_norm_fwd: eps = %g is outside [0, 1)", (double)eps);
-    PTX_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "ptx_sparse_norm_fwd: running_mean and running_var go together");
-    if (running_mean) {
-        PTX_REQUIRE(S == 1 && n >= 2, "ptx_sparse_norm_fwd: running statistics need one segment of at least 2 rows, got S=%d n=%d", S, n);
-        PTX_REQUIRE(momentum >= 0.0f && momentum <= 1.0f, "ptx_sparse_norm_fwd: momentum = %g is outside [0, 1]", (double)momentum);
-    }
-    PTX_REQUIRE(stats != nullptr && ((x && out) || n == 0), "ptx_sparse_norm_fwd: null argument (x, out and stats are needed)");
-    PTX_REQUIRE(sp_aligned16({x, weight, bias, residual, stats, out, workspace}),
-                "ptx_sparse_norm_fwd: every float buffer and the workspace must be 16-byte aligned");
-    const SnPlan P = sn_plan(n, S, C);
-    const int T = sg.tile0[S];
-    if (T > 0) {
-        PTX_REQUIRE(workspace, "ptx_sparse_norm_fwd: workspace is null");
-        PTX_TRY(sp_workspace_fits("ptx_sparse_norm_fwd", ws_bytes, P.total));
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *part = static_cast<float *>(workspace);
-    if (T > 0) {
-        hipLaunchKernelGGL(k_sparse_norm_stats, dim3(T, C / 64), dim3(256), 0, st, x, sg, C, part);
-        PTX_LAUNCHED("k_sparse_norm_stats");
-    }
-    hipLaunchKernelGGL(k_sparse_norm_finalise, dim3(S, C / 64), dim3(256), 0, st, part, sg, C, eps, stats, running_mean, running_var, momentum);
-    PTX_LAUNCHED("k_sparse_norm_finalise");
-    if (T > 0) {
-        hipLaunchKernelGGL(k_sparse_norm_apply, dim3(T, C / 64), dim3(256), 0, st, x, sg, C, stats, weight, bias, residual, relu != 0, out);
-        PTX_LAUNCHED("k_sparse_norm_apply");
-    }
-    return PTX_OK;
+    return sn_fwd("ptx_sparse_norm_fwd", x, seg_end, S, n, C, eps, weight, bias, residual, relu != 0, running_mean, running_var, momentum, stats, out,
+                  workspace, ws_bytes, stream);
+}
+
+int ptx_sparse_norm_fwd_act(const float *x, const int32_t *seg_end, int S, int n, int C, float eps, const float *weight, const float *bias,
+                            const float *residual, int act, float *running_mean, float *running_var, float momentum, float *stats, float *out,
+                            void *workspace, size_t ws_bytes, void *stream)
+{
+    PTX_REQUIRE(act >= 0 && act <= 2, "ptx_sparse_norm_fwd_act: act=%d (0 none, 1 ReLU, 2 ELU)", act);
+    return sn_fwd("ptx_sparse_norm_fwd_act", x, seg_end, S, n, C, eps, weight, bias, residual, act, running_mean, running_var, momentum, stats, out,
+                  workspace, ws_bytes, stream);
 }
 
 int ptx_sparse_norm_apply(const float *x, const int32_t *seg_end, int S, int n, int C, const float *stats, const float *weight,
@@ -388,7 +476,7 @@ int ptx_sparse_norm_apply(const float *x, const int32_t *seg_end, int S, int n, 
     PTX_REQUIRE(sp_aligned16({x, weight, bias, residual, stats, out}), "ptx_sparse_norm_apply: every float buffer must be 16-byte aligned");
     const int T = sg.tile0[S];
     if (T == 0) return PTX_OK;
-    hipLaunchKernelGGL(k_sparse_norm_apply, dim3(T, C / 64), dim3(256), 0, static_cast<hipStream_t>(stream), x, sg, C, stats, weight, bias,
+    hipLaunchKernelGGL(k_sparse_norm_apply<false>, dim3(T, C / 64), dim3(256), 0, static_cast<hipStream_t>(stream), x, sg, C, stats, weight, bias,
                        residual, relu != 0, out);
     PTX_LAUNCHED("k_sparse_norm_apply");
     return PTX_OK;
@@ -398,38 +486,17 @@ int ptx_sparse_norm_bwd(const float *g, const float *x, const float *out, const 
                         const float *weight, float *dx, float *dweight, float *dbias, float *dresidual, void *workspace, size_t ws_bytes,
                         void *stream)
 {
-    SnSegs sg;
-    PTX_TRY(sn_segments("ptx_sparse_norm_bwd", seg_end, S, n, C, sg));
-    PTX_REQUIRE(stats != nullptr && ((g && x) || n == 0), "ptx_sparse_norm_bwd: null argument (g, x and stats are needed)");
-    PTX_REQUIRE(sp_aligned16({g, x, out, stats, weight, dx, dweight, dbias, dresidual, workspace}),
-                "ptx_sparse_norm_bwd: every float buffer and the workspace must be 16-byte aligned");
-    const SnPlan P = sn_plan(n, S, C);
-    PTX_REQUIRE(workspace, "ptx_sparse_norm_bwd: workspace is null");
-    PTX_TRY(sp_workspace_fits("ptx_sparse_norm_bwd", ws_bytes, P.total));
-    const int T = sg.tile0[S];
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *part = static_cast<float *>(workspace);
-    float *seg = reinterpret_cast<float *>(static_cast<char *>(workspace) + P.part_bytes);
-    float *tot = reinterpret_cast<float *>(static_cast<char *>(workspace) + P.part_bytes + P.seg_bytes);
-    const bool sums = dx != nullptr || dweight != nullptr || dbias != nullptr;
-    if (T > 0 && (sums || dresidual)) {
-        hipLaunchKernelGGL(k_sparse_norm_bwd_sums, dim3(T, C / 64), dim3(256), 0, st, g, x, out, sg, C, stats, dresidual, part);
-        PTX_LAUNCHED("k_sparse_norm_bwd_sums");
-    }
-    if (sums) {
-        hipLaunchKernelGGL(k_sparse_norm_bwd_finalise, dim3(S, C / 64), dim3(256), 0, st, part, sg, C, seg, tot, dbias, dweight);
-        PTX_LAUNCHED("k_sparse_norm_bwd_finalise");
-        if (S > 1 && (dbias || dweight)) {
-            hipLaunchKernelGGL(k_sparse_norm_bwd_total, dim3(C / 64), dim3(64), 0, st, static_cast<const float *>(tot), S, C, dbias, dweight);
-            PTX_LAUNCHED("k_sparse_norm_bwd_total");
-        }
-    }
-    if (T > 0 && dx) {
-        hipLaunchKernelGGL(k_sparse_norm_bwd_apply, dim3(T, C / 64), dim3(256), 0, st, g, x, out, static_cast<const float *>(dresidual), sg, C,
-                           stats, seg, weight, dx);
-        PTX_LAUNCHED("k_sparse_norm_bwd_apply");
-    }
-    return PTX_OK;
+    return sn_bwd("ptx_sparse_norm_bwd", false, g, x, out, seg_end, S, n, C, stats, weight, dx, dweight, dbias, dresidual, workspace, ws_bytes, stream);
+}
+
+int ptx_sparse_norm_bwd_act(const float *g, const float *x, const float *out, int act, const int32_t *seg_end, int S, int n, int C,
+                            const float *stats, const float *weight, float *dx, float *dweight, float *dbias, float *dresidual, void *workspace,
+                            size_t ws_bytes, void *stream)
+{
+    PTX_REQUIRE(act >= 0 && act <= 2, "ptx_sparse_norm_bwd_act: act=%d (0 none, 1 ReLU, 2 ELU)", act);
+    PTX_REQUIRE(act == 0 || out != nullptr || n == 0, "ptx_sparse_norm_bwd_act: act=%d needs the forward's out", act);
+    return sn_bwd("ptx_sparse_norm_bwd_act", act == 2, g, x, act ? out : nullptr, seg_end, S, n, C, stats, weight, dx, dweight, dbias, dresidual,
+                  workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

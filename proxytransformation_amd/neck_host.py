@@ -13,8 +13,9 @@ import numpy as np
 
 from .sparse_host import kernel_offsets, sparse_conv3d_host
 
-__all__ = ["ACT_NONE", "ACT_RELU", "ACT_ELU", "act_host", "conv_transpose_gen_host", "head_host", "prune_host", "prune_scores_host",
-           "sparse_conv3d_act_host", "topk_keep_host", "topk_key", "topk_scene_rows", "union_add_host"]
+__all__ = ["ACT_NONE", "ACT_RELU", "ACT_ELU", "act_host", "conv_transpose_gen_bwd_host", "conv_transpose_gen_host", "head_bwd_host",
+           "head_host", "prune_dest_host", "prune_host", "prune_scores_host", "rows_gather_host", "sparse_conv3d_act_host", "topk_keep_host",
+           "topk_key", "topk_scene_rows", "union_add_host", "union_dest_host"]
 
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
 
@@ -65,6 +66,58 @@ def conv_transpose_gen_host(coords, scene_rows: Sequence[int], tensor_stride: in
         out[:, j] = feats @ kernel[j]
     out = act_host(_affine(out.reshape(8 * n, -1), scale, shift, dt).astype(dt, copy=False), act)
     return out_c.astype(np.int32), [8 * int(e) for e in scene_rows], out
+
+
+def conv_transpose_gen_bwd_host(g, feats, kernel) -> dict:
+    """Backward of the raw generative transposed convolution (no epilogue) in the dtype of ``g (8n, Cout)``: ``dict(dfeats, dkernel)`` with
+    ``dfeats[i] = sum_j g[8 i + j] @ kernel[j].T`` (j ascending) and ``dkernel[j] = feats.T @ g[j::8]``."""
+    g = np.asarray(g)
+    dt = g.dtype
+    feats, kernel = np.asarray(feats, dt), np.asarray(kernel, dt)
+    dfeats = np.zeros_like(feats)
+    dkernel = np.empty_like(kernel)
+    for j in range(8):
+        dfeats = dfeats + g[j::8] @ kernel[j].T
+        dkernel[j] = feats.T @ g[j::8]
+    return dict(dfeats=dfeats.astype(dt, copy=False), dkernel=dkernel)
+
+
+def rows_gather_host(g, dest) -> np.ndarray:
+    """``out[i] = g[dest[i]]`` where ``dest[i] >= 0``, else ``+0.0``: the backward of the row routings (``dA = g[a_dest]``,
+    ``dB = g[b_dest]`` of the union, ``dU = g[dest]`` of the prune).  Pure copies."""
+    g, dest = np.asarray(g), np.asarray(dest).reshape(-1)
+    out = np.zeros((dest.shape[0], g.shape[1]), g.dtype)
+    hit = (dest >= 0) & (dest < g.shape[0])
+    out[hit] = g[dest[hit]]
+    return out
+
+
+def union_dest_host(a_coords, a_rows: Sequence[int], b_coords, b_rows: Sequence[int]):
+    """``(a_dest (nA,), b_dest (nB,))`` int32: the row of ``union_add_host``'s result that holds ``A[a]`` resp. ``B[k]`` -- a matched pair
+    shares one."""
+    ac, bc = np.asarray(a_coords).reshape(-1, 4), np.asarray(b_coords).reshape(-1, 4)
+    a_dest, b_dest = np.full(ac.shape[0], -1, np.int32), np.full(bc.shape[0], -1, np.int32)
+    alo = blo = out0 = 0
+    for ahi, bhi in zip((int(e) for e in a_rows), (int(e) for e in b_rows)):
+        index = {tuple(int(v) for v in row[1:]): alo + i for i, row in enumerate(ac[alo:ahi])}
+        a_dest[alo:ahi] = out0 + np.arange(ahi - alo)
+        extra = 0
+        for k in range(blo, bhi):
+            a = index.get(tuple(int(v) for v in bc[k, 1:]), -1)
+            if a >= 0:
+                b_dest[k] = a_dest[a]
+            else:
+                b_dest[k] = out0 + (ahi - alo) + extra
+                extra += 1
+        out0 += (ahi - alo) + extra
+        alo, blo = ahi, bhi
+    return a_dest, b_dest
+
+
+def prune_dest_host(keep) -> np.ndarray:
+    """``dest (n,)`` int32 of ``MinkowskiPruning``: the place of each kept row among the kept rows, ``-1`` for a dropped one."""
+    keep = np.asarray(keep, bool)
+    return np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
 
 
 def union_add_host(a_coords, a_rows: Sequence[int], a_feats, b_coords, b_rows: Sequence[int], b_feats):
@@ -190,3 +243,13 @@ def head_host(feats, weight, bias=None):
         cls = cls + np.asarray(bias, dt).reshape(1, -1)
     cls = cls.astype(dt, copy=False)
     return cls, cls.max(axis=1)
+
+
+def head_bwd_host(dcls, feats, weight) -> dict:
+    """Backward of ``conv_cls`` in the dtype of ``dcls (n, K)``: ``dict(dfeats = dcls @ weight.T, dweight (C, K) = feats.T @ dcls,
+    dbias (K) = sum_rows dcls)``.  The prune score gets no gradient (the reference takes it under ``torch.no_grad()``)."""
+    dcls = np.asarray(dcls)
+    dt = dcls.dtype
+    feats = np.asarray(feats, dt)
+    w = np.asarray(weight, dt).reshape(feats.shape[1], -1)
+    return dict(dfeats=(dcls @ w.T).astype(dt, copy=False), dweight=(feats.T @ dcls).astype(dt, copy=False), dbias=dcls.sum(axis=0, dtype=dt))

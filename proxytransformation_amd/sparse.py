@@ -38,7 +38,7 @@ eval mode the affine map from the running statistics) are one family of streamin
 normalise -> affine (+ residual)(+ ReLU)", forward and backward, restated in numpy by ``sparse_norm_host`` / ``sparse_norm_bwd_host``.
 The same opt-in rule: inference-only unless ``differentiable=True``.  ``backbone.MinkResNet`` assembles all of this.
 
-``neck_3d`` is ``neck.MinkNeck`` (``neck.py``; eval forward only).  Not here (out of scope): double backward, bf16, gradients to ``scale`` / ``shift``, SyncBatchNorm across ranks.  There is no
+``neck_3d`` is ``neck.MinkNeck`` (``neck.py``; eval forward, and with ``differentiable=True`` the training chain).  Not here (out of scope): double backward, bf16, gradients to ``scale`` / ``shift``, SyncBatchNorm across ranks.  There is no
 CPU path for the layers themselves: tensors must be on the GPU and the library must be built.
 """
 from __future__ import annotations
@@ -322,7 +322,7 @@ def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bi
     caller), ``+ residual (n_out, Cout)``, ReLU.  Cout a multiple of 64 up to 512; Cin a multiple of 16 up to 512, or 3 with a 3x3x3
     kernel (the stem).  Inference-only unless ``differentiable=True``: then, with grad mode on and ``feats`` / ``weight`` / ``bias`` /
     ``residual`` requiring grad, the same launch is recorded for autograd (``ptx_sparse_conv3d_bwd``; same output bits) -- Cin a
-    multiple of 64 up to 512 or the stem's 3; ``scale`` / ``shift`` are constants (a folded frozen BatchNorm) and must not require
+    multiple of 64 up to 1024 or the stem's 3; ``scale`` / ``shift`` are constants (a folded frozen BatchNorm) and must not require
     grad: the gradient passes through multiplied by ``scale``.  ``elu=True`` (the neck's layers: ELU with alpha = 1 instead of the ReLU;
     not both) or ``Cin > 512`` (up to 1024) goes through ``ptx_sparse_conv3d_act``, the same kernel; ``elu`` is inference-only."""
     if elu and relu:
@@ -350,9 +350,9 @@ def sparse_conv3d(feats: torch.Tensor, kmap: KernelMap, weight: torch.Tensor, bi
         raise ValueError(f"sparse_conv3d: residual must be {(n_out, cout)}, got {tuple(residual.shape)}")
     if not train:
         return _conv_forward(feats, kmap, weight, vecs, residual, relu, elu)
-    if not ((cin == 3 and kvol == 27) or (64 <= cin <= 512 and cin % 64 == 0)) or not (64 <= cout <= 512 and cout % 64 == 0):
+    if not ((cin == 3 and kvol == 27) or (64 <= cin <= 1024 and cin % 64 == 0)) or not (64 <= cout <= 512 and cout % 64 == 0):
         raise ValueError(f"sparse_conv3d(differentiable=True): Cin={cin} Cout={cout} with {kvol} offsets -- the backward takes Cin a multiple "
-                         f"of 64 up to 512 (or 3 with 27 offsets) and Cout a multiple of 64 up to 512")
+                         f"of 64 up to 1024 (or 3 with 27 offsets) and Cout a multiple of 64 up to 512")
     if not kmap.nbr.is_contiguous():
         raise ValueError("sparse_conv3d: the kernel map's nbr must be contiguous")
     f_in, w_in, b_in, r_in = (_f32_grad(t) for t in grad_in)     # the validated operands again, this time inside the graph
@@ -392,8 +392,9 @@ def _norm_workspace(n: int, S: int, C: int, dev) -> torch.Tensor:
     return _workspace("norm", nbytes, dev)
 
 
-def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, momentum=0.0):
-    """One call of ``ptx_sparse_norm_fwd`` on the current stream: ``(out, stats)``."""
+def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, momentum=0.0, elu=False):
+    """One call of ``ptx_sparse_norm_fwd`` (``elu``: ``ptx_sparse_norm_fwd_act`` with selector 2) on the current stream:
+    ``(out, stats)``."""
     n, C = int(x.shape[0]), int(x.shape[1])
     S = len(ends)
     dev = x.device
@@ -402,6 +403,11 @@ def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, mome
     stats = torch.empty((S, 2, C), dtype=torch.float32, device=dev)
     seg = _int32_array(ends)
     rm, rv = running if running is not None else (None, None)
+    if elu:
+        _abi.check(_abi.lib().ptx_sparse_norm_fwd_act(x.data_ptr(), seg, S, n, C, float(eps), _ptr(weight), _ptr(bias), _ptr(residual), 2, _ptr(rm),
+                                                      _ptr(rv), float(momentum), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_fwd_act")
+        return out, stats
     _abi.check(_abi.lib().ptx_sparse_norm_fwd(x.data_ptr(), seg, S, n, C, float(eps), _ptr(weight), _ptr(bias), _ptr(residual), int(bool(relu)),
                                               _ptr(rm), _ptr(rv), float(momentum), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                               torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_fwd")
@@ -424,12 +430,12 @@ class _SparseNormFn(torch.autograd.Function):
     ``(running_mean, running_var)`` updated in place by the kernel, or None."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, ends, eps, relu, running, momentum):
+    def forward(ctx, x, weight, bias, residual, ends, eps, relu, running, momentum, elu):
         w = None if weight is None else weight.reshape(-1)
-        out, stats = _norm_forward(x, ends, eps, w, None if bias is None else bias.reshape(-1), residual, relu, running, momentum)
-        ctx.ends, ctx.relu = ends, bool(relu)
+        out, stats = _norm_forward(x, ends, eps, w, None if bias is None else bias.reshape(-1), residual, relu, running, momentum, elu)
+        ctx.ends, ctx.relu, ctx.elu = ends, bool(relu), bool(elu)
         ctx.shapes = (None if weight is None else tuple(weight.shape), None if bias is None else tuple(bias.shape))
-        ctx.save_for_backward(x, stats, w, out if relu else None)
+        ctx.save_for_backward(x, stats, w, out if (relu or elu) else None)
         return out
 
     @staticmethod
@@ -446,9 +452,15 @@ class _SparseNormFn(torch.autograd.Function):
         dw = new(C) if need_w else None
         db = new(C) if need_b else None
         dres = None
-        if need_r:                                           # g * [out > 0]: g itself without ReLU
-            dres = new(n, C) if ctx.relu else g
-        if need_x or need_w or need_b or (need_r and ctx.relu):
+        act = ctx.relu or ctx.elu
+        if need_r:                                           # g * [out > 0] (ELU: g * (out > 0 ? 1 : out + 1)): g itself without activation
+            dres = new(n, C) if act else g
+        if ctx.elu and (need_x or need_w or need_b or need_r):
+            ws = _norm_workspace(n, S, C, dev)
+            _abi.check(_abi.lib().ptx_sparse_norm_bwd_act(g.data_ptr(), x.data_ptr(), _ptr(out), 2, _int32_array(ctx.ends), S, n, C,
+                                                          stats.data_ptr(), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), _ptr(dres), ws.data_ptr(),
+                                                          ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_bwd_act")
+        elif need_x or need_w or need_b or (need_r and ctx.relu):
             ws = _norm_workspace(n, S, C, dev)
             seg = _int32_array(ctx.ends)
             _abi.check(_abi.lib().ptx_sparse_norm_bwd(g.data_ptr(), x.data_ptr(), _ptr(out), seg, S, n, C, stats.data_ptr(), _ptr(w), _ptr(dx),
@@ -458,7 +470,7 @@ class _SparseNormFn(torch.autograd.Function):
             dw = dw.reshape(ctx.shapes[0])
         if db is not None:
             db = db.reshape(ctx.shapes[1])
-        return dx, dw, db, dres, None, None, None, None, None
+        return dx, dw, db, dres, None, None, None, None, None, None
 
 
 def _norm_operands(what: str, feats, weight, bias, residual):
@@ -496,7 +508,7 @@ def sparse_segment_norm(feats: torch.Tensor, seg_end: Sequence[int], eps: float,
     if return_stats:
         raise ValueError("sparse_segment_norm: return_stats is for inference calls")
     return _SparseNormFn.apply(_f32_grad(feats), _f32_grad(weight), _f32_grad(bias), _f32_grad(residual), ends, float(eps), bool(relu), None,
-                               0.0)
+                               0.0, False)
 
 
 def sparse_instance_norm(feats: torch.Tensor, scene_rows: Sequence[int], weight: Optional[torch.Tensor] = None,
@@ -556,14 +568,21 @@ def _check_bn(bn) -> None:
 
 
 def sparse_batch_norm(feats: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor] = None, relu: bool = False,
-                      differentiable: bool = False) -> torch.Tensor:
-    """``relu?(bn(feats) (+ residual))`` for an ``nn.BatchNorm1d`` on the rows ``feats (n, C)`` (C a multiple of 64 up to 512).
+                      differentiable: bool = False, elu: bool = False) -> torch.Tensor:
+    """``act(bn(feats) (+ residual))``, ``act`` the ReLU (``relu``), the ELU with alpha = 1 (``elu``, training mode only: the neck's
+    blocks, ``ptx_sparse_norm_fwd_act`` / ``ptx_sparse_norm_bwd_act``; not both) or nothing, for an ``nn.BatchNorm1d`` on the rows
+    ``feats (n, C)`` (C a multiple of 64 up to 512).
     ``bn.training``: the batch statistics of one segment over all rows; the kernel updates ``bn.running_mean`` / ``bn.running_var`` in
     place by ``nn.BatchNorm1d``'s rule (unbiased variance) and ``bn.num_batches_tracked`` is incremented; ``n == 1`` is refused with
     torch's own ``ValueError``.  Eval: the affine map from the running statistics through the same apply kernel.  Inference-only unless
     ``differentiable=True``; then the training-mode call is recorded for autograd (gradients to ``feats``, ``bn.weight``, ``bn.bias``,
     ``residual``).  An eval-mode BatchNorm is a constant affine map: to train through it fold it into ``sparse_conv3d`` (``bn_fold``)."""
+    if elu and relu:
+        raise ValueError("sparse_batch_norm: elu and relu are one activation slot; pass one of them")
     _check_bn(bn)
+    if elu and not bn.training:
+        raise NotImplementedError("sparse_batch_norm(elu=True) in eval mode: fold the BatchNorm into the convolution's epilogue "
+                                  "(bn_fold, sparse_conv3d(elu=True)), or call bn.train()")
     train = _train("sparse_batch_norm", differentiable, feats, bn.weight, bn.bias, residual)
     if feats.dim() == 2 and bn.num_features != feats.shape[1]:
         raise ValueError(f"sparse_batch_norm: the BatchNorm has {bn.num_features} features, feats has {feats.shape[1]} channels")
@@ -581,9 +600,9 @@ def sparse_batch_norm(feats: torch.Tensor, bn: nn.Module, residual: Optional[tor
         raise ValueError("sparse_batch_norm: running_mean / running_var must be contiguous fp32 tensors on the device of feats")
     if train:
         out = _SparseNormFn.apply(_f32_grad(feats), _f32_grad(bn.weight), _f32_grad(bn.bias), _f32_grad(residual), [n], float(bn.eps),
-                                  bool(relu), running, float(bn.momentum))
+                                  bool(relu), running, float(bn.momentum), bool(elu))
     else:
-        out = _norm_forward(x, [n], float(bn.eps), w, b, res, relu, running, float(bn.momentum))[0]
+        out = _norm_forward(x, [n], float(bn.eps), w, b, res, relu, running, float(bn.momentum), bool(elu))[0]
     for t in running:                                        # written by the kernel: tell torch (the fold cache watches _version)
         torch.autograd.graph.increment_version(t)
     if bn.num_batches_tracked is not None:
@@ -644,7 +663,7 @@ class SparseInstanceNorm(nn.Module):
 
 class SparseBatchNorm(nn.Module):
     """``ME.MinkowskiBatchNorm(num_features, eps, momentum)``: a child ``bn = nn.BatchNorm1d`` as in ME, so the keys are ``bn.weight``,
-    ``bn.bias``, ``bn.running_mean``, ``bn.running_var``, ``bn.num_batches_tracked``.  ``forward(feats, residual=None, relu=False)`` =
+    ``bn.bias``, ``bn.running_mean``, ``bn.running_var``, ``bn.num_batches_tracked``.  ``forward(feats, residual=None, relu=False, elu=False)`` =
     ``sparse_batch_norm``."""
 
     def __init__(self, num_features: int, eps: float = 1e-5, momentum: float = 0.1, differentiable: bool = False):
@@ -652,5 +671,5 @@ class SparseBatchNorm(nn.Module):
         self.differentiable = bool(differentiable)
         self.bn = nn.BatchNorm1d(int(num_features), eps=eps, momentum=momentum)
 
-    def forward(self, feats: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
-        return sparse_batch_norm(feats, self.bn, residual, relu, differentiable=self.differentiable)
+    def forward(self, feats: torch.Tensor, residual: Optional[torch.Tensor] = None, relu: bool = False, elu: bool = False) -> torch.Tensor:
+        return sparse_batch_norm(feats, self.bn, residual, relu, differentiable=self.differentiable, elu=elu)

@@ -161,12 +161,15 @@ def _segments(seg_end: Sequence[int], n: int) -> List[int]:
 
 
 def sparse_norm_host(x, seg_end: Sequence[int], eps: float, weight=None, bias=None, residual=None, relu: bool = False,
-                     return_stats: bool = False, running=None, momentum: float = 0.1):
+                     return_stats: bool = False, running=None, momentum: float = 0.1, elu: bool = False):
     """numpy restatement of the norm kernels' forward in the dtype of ``x``, two-pass: per segment ``[seg_end[s-1], seg_end[s])`` and
     column ``mean``, biased ``var = mean((x - mean)^2)``, ``rstd = 1 / sqrt(var + eps)``;
     ``out = relu?(((x - mean) * rstd) * weight + bias (+ residual))``.  ``return_stats``: also ``stats (S, 2, C) = (mean, rstd)``, an
     empty segment ``(0, 0)``.  ``running = (running_mean, running_var)`` (one segment of at least 2 rows): the two arrays are updated in
-    place as the kernel updates them, ``(1 - momentum) * old + momentum * new`` with the unbiased variance (``nn.BatchNorm1d``'s rule)."""
+    place as the kernel updates them, ``(1 - momentum) * old + momentum * new`` with the unbiased variance (``nn.BatchNorm1d``'s rule).
+    ``elu`` (not with ``relu``): the ELU with alpha = 1, ``v > 0 ? v : expm1(v)``, in the place of the ReLU."""
+    if relu and elu:
+        raise ValueError("relu and elu are one activation slot")
     x = np.asarray(x)
     dt = x.dtype
     ends = _segments(seg_end, x.shape[0])
@@ -196,15 +199,19 @@ def sparse_norm_host(x, seg_end: Sequence[int], eps: float, weight=None, bias=No
         out = out + np.asarray(residual, dt)
     if relu:
         out = np.maximum(out, 0)
+    if elu:
+        out = np.where(out > 0, out, np.expm1(np.minimum(out, 0)))
     out = out.astype(dt, copy=False)
     return (out, stats) if return_stats else out
 
 
-def sparse_norm_bwd_host(g, x, seg_end: Sequence[int], eps: float, weight=None, out=None, relu: bool = False, stats=None) -> dict:
+def sparse_norm_bwd_host(g, x, seg_end: Sequence[int], eps: float, weight=None, out=None, relu: bool = False, stats=None,
+                         elu: bool = False) -> dict:
     """numpy restatement of the norm kernels' backward in the dtype of ``g``: ``dict(dx, dweight, dbias, dresidual)``.  ``gy = g * [out > 0]``
     with the ReLU mask taken from the ``out`` it is handed (``g`` itself without ReLU); ``xhat`` from ``x`` and ``stats`` (default: the
     two-pass statistics of ``x``); ``dresidual = gy``, ``dbias = sum gy``, ``dweight = sum gy * xhat``; per segment ``a = mean gy``,
-    ``b = mean gy * xhat``, ``dx = weight * rstd * (gy - a - xhat * b)``."""
+    ``b = mean gy * xhat``, ``dx = weight * rstd * (gy - a - xhat * b)``.  ``elu``: ``gy = g * (out > 0 ? 1 : out + 1)`` from the ``out`` it
+    is handed -- exactly 0 where ``out == -1``; a NaN ``out`` gives a NaN ``gy`` and is never dropped (behind the ReLU ``[NaN > 0] = 0``)."""
     g = np.asarray(g)
     dt = g.dtype
     x = np.asarray(x, dt)
@@ -213,6 +220,9 @@ def sparse_norm_bwd_host(g, x, seg_end: Sequence[int], eps: float, weight=None, 
         _, stats = sparse_norm_host(x, ends, eps, return_stats=True)
     stats = np.asarray(stats, dt)
     gy = np.where(np.asarray(out) > 0, g, np.zeros((), dt)).astype(dt, copy=False) if relu else g
+    if elu:
+        o = np.asarray(out, dt)
+        gy = np.where(o > 0, g, g * (o + dt.type(1))).astype(dt, copy=False)
     w = np.ones((1, x.shape[1]), dt) if weight is None else np.asarray(weight, dt).reshape(1, -1)
     dx = np.empty_like(x)
     xhat = np.empty_like(x)

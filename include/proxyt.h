@@ -638,6 +638,45 @@ PTX_API size_t ptx_neck_head_bwd_workspace_bytes(int n, int C, int num_classes);
 PTX_API int ptx_neck_head_bwd(const float *dcls, const float *feats, const float *weight, int n, int C, int num_classes, float *dfeats,
                       float *dweight, float *dbias, void *workspace, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ query selection behind the neck (ABI 13, by addition)
+ * `pre_decoder` of the detector (detectors/sparse_featfusion_grounder_preshape.py:498-580): the neck's per-scene lists become the
+ * transformer decoder's operands.  Assembled in Python (proxytransformation_amd/query_select.py), restated in numpy
+ * (query_select_host.py).  fp32; no float atomics and fixed summation orders: two calls on the same inputs give the same bits;
+ * everything on `stream`, no host wait; host checks (PTX_EINVAL with the numbers in the message) come before anything is enqueued.
+ * rows: [host] B ints, the rows L_b of every scene, 0 <= L_b <= Lmax; B <= 64; C a multiple of 64 up to 512; 1 <= T <= 256;
+ * masks are bytes of 0 / 1 (torch.bool).
+ *
+ * Pack: feats / xyz are [host] arrays of B device pointers, (L_b,C) and (L_b,3).  out_feats (B,Lmax,C) and out_coords (B,Lmax,3) get the
+ * rows with zeros behind them, pad_mask (B,Lmax) = 1 on padding, text_attn (B,T) = !text_mask.  One launch. */
+PTX_API int ptx_qs_pack(const float *const *feats, const float *const *xyz, const int32_t *rows, int B, int C, int Lmax,
+                        const uint8_t *text_mask, int T, float *out_feats, float *out_coords, uint8_t *pad_mask, uint8_t *text_attn,
+                        void *stream);
+/* ContrastiveEmbed and its max over the tokens (grounding_head.py:62-99): score (B,Lmax), score[b,r] = max over the tokens t with
+ * text_mask[b,t] of (feats[b,r] . text[b,t]) (/ sqrtf(C) when scaled) (+ bias[0] when bias is given); -inf for r >= rows[b] and for a
+ * scene without a token; NaN where one of the unmasked products is NaN (torch.max's rule).  The product runs on the exact-fp32 matrix
+ * instruction, 64 rows x 64 tokens per step; the (B,L,T) tensor is never materialised.  One launch. */
+PTX_API int ptx_qs_score(const float *feats, const int32_t *rows, int B, int Lmax, int C, const float *text, const uint8_t *text_mask, int T,
+                         int scaled, const float *bias, float *score, void *stream);
+/* torch.topk(score, K, dim=1, sorted=True)[1] over the rows 0 .. rows[b] - 1 of every scene, 1 <= K <= 1024, K <= rows[b]: index (B,K)
+ * int64 in descending order of ptx_neck_topk_prune's key (-0.0 = +0.0; a NaN orders by its bits), the lower row first among equal keys
+ * (torch leaves ties unspecified).  inv (B,Lmax) int32, optional: the place q of a selected row, -1 elsewhere.  A radix select and a
+ * sort of K (key, row) pairs in LDS, one work-group per scene.  One launch. */
+PTX_API int ptx_qs_topk(const float *score, const int32_t *rows, int B, int Lmax, int K, int64_t *index, int32_t *inv, void *stream);
+/* out (B K,Cout) = act(rows @ weight^T + bias) with weight (Cout,Cin) as nn.Linear holds it: row b K + q is x[b Lmax + index[b,q]] (x of
+ * n_src rows; an index outside 0 .. Lmax - 1 reads zeros), or x[b K + q] when index is NULL.  relu: 0 / 1; the ReLU keeps a NaN.  Cin,
+ * Cout: multiples of 64 up to 512.  The gather-GEMM of ptx_sparse_conv3d's transposed-weight form.  One launch. */
+PTX_API int ptx_qs_linear(const float *x, int n_src, const int64_t *index, int B, int K, int Lmax, const float *weight, const float *bias,
+                          int Cin, int Cout, int relu, float *out, void *stream);
+/* The last Linear of the regression branch, weight (9,C) / bias (9), on h (B K,C) (NULL: on the gathered features), the baseline box
+ * decode (grounding_head.py:293-297: center = p[0:3] + coords, size = max(expf(p[3:6]), 0.02) with a NaN kept, euler = p[6:9]) and the
+ * gathers query (B,K,C) = feats[b, index], qcoords (B,K,3) = coords[b, index]; boxes (B,K,9).  One launch. */
+PTX_API int ptx_qs_decode(const float *h, const float *weight, const float *bias, int C, const float *feats, const float *coords,
+                          const int64_t *index, int B, int K, int Lmax, float *query, float *qcoords, float *boxes, void *stream);
+/* The backward of pack + gather: out (sum of rows,C), scene b from row rows[0] + .. + rows[b-1]: out_b[r] = dfeats[b,r] (+ dquery[b,q]
+ * where inv[b,r] = q >= 0: one fp32 add).  dfeats (B,Lmax,C) and dquery (B,K,C) are optional (NULL: zeros).  One launch. */
+PTX_API int ptx_qs_bwd(const float *dfeats, const float *dquery, const int32_t *inv, const int32_t *rows, int B, int Lmax, int K, int C,
+                       float *out, void *stream);
+
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/
  * sparse_featfusion_grounder_preshape.py:428-444 (nearest, zeros padding, align_corners=True, valid_flag=True; bilinear != 0:

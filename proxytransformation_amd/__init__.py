@@ -8,6 +8,7 @@ Only what the path needs lives here:
   the C ABI of ``include/proxyt.h`` (bound with ctypes in ``_abi``);
 * ``backbone.MinkResNet``                    -- the sparse 3D backbone (backbones/mink_resnet.py) on the layers of ``sparse``;
 * ``neck.MinkNeck``                          -- the sparse neck and head (necks/mink_neck.py), eval forward, on ``neck`` / ``sparse``;
+* ``query_select.QuerySelect``               -- the detector's ``pre_decoder`` behind the neck: pad, text scores, sorted top-k, box decode;
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -19,6 +20,7 @@ from .registry import MODELS, REGISTRY_BACKEND
 from .module import ProxyTransformationNormReverse
 from .backbone import MinkResNet
 from .neck import MinkNeck
+from .query_select import QuerySelect
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
 __version__ = "0.1.0"

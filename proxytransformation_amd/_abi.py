@@ -205,6 +205,12 @@ SIGNATURES.update({
     "ptx_neck_rows_gather": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "ptx_neck_head_bwd_workspace_bytes": (_Z, [_I, _I, _I]),
     "ptx_neck_head_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "ptx_qs_pack": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "ptx_qs_score": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "ptx_qs_topk": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "ptx_qs_linear": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "ptx_qs_decode": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "ptx_qs_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),

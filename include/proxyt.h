@@ -677,6 +677,43 @@ PTX_API int ptx_qs_decode(const float *h, const float *weight, const float *bias
 PTX_API int ptx_qs_bwd(const float *dfeats, const float *dquery, const int32_t *inv, const int32_t *rows, int B, int Lmax, int K, int C,
                        float *out, void *stream);
 
+/* ------------------------------------------------------------------ the transformer decoder behind the query selection (ABI 13, by addition)
+ * The eval forward of SparseFeatureFusionTransformerDecoder (models/layers/ground_transformer/decoder.py) and the per-layer text scores of
+ * GroundingHead.forward, assembled in Python (proxytransformation_amd/decoder.py), restated in numpy (decoder_host.py).  fp32 on the
+ * exact-fp32 matrix instruction; no float atomics and fixed summation orders: two calls on the same inputs give the same bits; everything
+ * on `stream`, no host wait; host checks (PTX_EINVAL with the numbers in the message) come before anything is enqueued.  Masks are bytes
+ * of 0 / 1 (torch.bool).
+ *
+ * PositionEmbeddingLearned in eval: out (n,C) = relu(x @ w1^T + b1) @ w2^T + b2 with x (n,cin), 1 <= cin <= 9, w1 (C,cin) / b1 (C) the
+ * first Conv1d with the BatchNorm folded in by the caller, w2 (C,C) / b2 (C) the second; the ReLU keeps a NaN.  One launch. */
+PTX_API int ptx_dec_posembed(const float *x, long n, int cin, const float *w1, const float *b1, const float *w2, const float *b2, int C,
+                             float *out, void *stream);
+/* out (n,Cout) = act((x + add) @ weight^T + bias) (+ residual) with weight (Cout,Cin) as nn.Linear holds it.  add (n,Cin), optional, is
+ * added to x for the output columns below add_cols only (a multiple of 64): one launch gives [q|k|v] with the positions on q and k.
+ * bias (Cout) and residual (n,Cout) are optional; relu: 0 / 1, applied before the residual, keeps a NaN.  Cin: a multiple of 64 up to
+ * 2048; Cout: a multiple of 64 up to 4096.  One launch. */
+PTX_API int ptx_dec_linear(const float *x, const float *add, int add_cols, long n, const float *weight, const float *bias, int Cin, int Cout,
+                           int relu, const float *residual, float *out, void *stream);
+/* Multi-head attention with a key padding mask: out (B,Kq,H hd) = softmax((q / sqrtf(hd)) k^T) v per head.  q (B,Kq,.) / k, v (B,L,.) may
+ * be column ranges of wider rows: ldq / ldk / ldv are the row strides in floats (multiples of 4), scene b starts Kq ldq resp. L ldk / L ldv
+ * floats behind scene b - 1, head h at column h hd.  mask (B,L), optional (NULL: none): 1 = ignore the key; a masked key and its value are never read (a NaN
+ * under them leaves no trace), a query whose every key is masked gets zeros.  hd: 32 or 64; H hd <= 512; Kq <= 1024.  One launch: key
+ * tiles of 64 in ascending order with a running maximum and sum. */
+PTX_API int ptx_dec_attention(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask, int B,
+                              int Kq, int L, int H, int hd, float *out, void *stream);
+/* out (n,C) = LayerNorm(x) with weight / bias (C): the row mean first, then the centred sum of squares.  weight2 / bias2 / out2, optional
+ * (all or none): out2 = LayerNorm2(out).  C: a multiple of 64 up to 512.  One launch. */
+PTX_API int ptx_dec_ln(const float *x, long n, int C, const float *weight, const float *bias, float eps, float *out, const float *weight2,
+                       const float *bias2, float *out2, void *stream);
+/* The last Linear of a regression branch, weight (9,C) / bias (9), on h (n,C) and ptx_qs_decode's baseline box decode against
+ * coords (n,3): boxes (n,9).  One launch. */
+PTX_API int ptx_dec_boxes(const float *h, const float *weight, const float *bias, int C, const float *coords, long n, float *boxes,
+                          void *stream);
+/* ContrastiveEmbed in full (grounding_head.py:62-99): out (NL,B,K,max_text_len), out[l,b,q,t] = hidden[l,b,q] . text[b,t] (/ sqrtf(C) when
+ * scaled) (+ bias[0] when bias is given) for t < T with text_mask[b,t], -inf elsewhere.  One launch. */
+PTX_API int ptx_dec_scores(const float *hidden, int NL, int B, int K, int C, const float *text, const uint8_t *text_mask, int T,
+                           int max_text_len, int scaled, const float *bias, float *out, void *stream);
+
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/
  * sparse_featfusion_grounder_preshape.py:428-444 (nearest, zeros padding, align_corners=True, valid_flag=True; bilinear != 0:

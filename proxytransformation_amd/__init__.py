@@ -9,6 +9,7 @@ Only what the path needs lives here:
 * ``backbone.MinkResNet``                    -- the sparse 3D backbone (backbones/mink_resnet.py) on the layers of ``sparse``;
 * ``neck.MinkNeck``                          -- the sparse neck and head (necks/mink_neck.py), eval forward, on ``neck`` / ``sparse``;
 * ``query_select.QuerySelect``               -- the detector's ``pre_decoder`` behind the neck: pad, text scores, sorted top-k, box decode;
+* ``decoder.GroundingDecoder``               -- the transformer decoder behind it (self, text and scene attention, FFN, box refinement);
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -21,6 +22,7 @@ from .module import ProxyTransformationNormReverse
 from .backbone import MinkResNet
 from .neck import MinkNeck
 from .query_select import QuerySelect
+from .decoder import GroundingDecoder
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "GroundingDecoder", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
 __version__ = "0.1.0"

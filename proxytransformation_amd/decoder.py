@@ -1,0 +1,555 @@
+"""The transformer decoder behind ``QuerySelect``: the eval forward of ``SparseFeatureFusionTransformerDecoder``
+(models/layers/ground_transformer/decoder.py; called by ``forward_decoder``, detectors/sparse_featfusion_grounder_preshape.py:582-621)
+and the per-layer text scores of ``GroundingHead.forward`` (dense_heads/grounding_head.py:427-467) on the device.
+
+Six calls into ``csrc/decoder.hip`` on the current stream -- ``posembed``, ``linear``, ``attention``, ``layer_norm`` (with ``linear``:
+``linear_add_ln``), ``boxes`` and ``contrastive_scores`` -- each restated in numpy by ``decoder_host.py``, which is their specification.
+No device synchronise, no torch op on the data path; fp32 on the exact-fp32 matrix instruction; no float atomics and fixed summation
+orders, so two calls give the same bits.  ``key`` and ``key_pos`` do not change across the layers, so the key and value projections of
+every layer's scene attention leave the layer loop: one ``linear`` launch per group of layers (``[K_0 .. K_n | V_0 .. V_n]``, at most 4096
+columns) ahead of it; the text keys and values likewise unless ``T == K`` (below).
+
+The rules of mmcv's attention wrapper: identity (the query before its positions) plus the attention output; positions on ``q`` and ``k``
+only; when ``key_pos`` is None and ``query_pos.shape == key.shape`` the keys receive ``query_pos`` -- so when ``T == K`` the TEXT keys of
+the text cross attention receive ``query_pos``, as in the reference.
+
+Parity-unpinned against ``nn.MultiheadAttention``: a masked key is never read (a NaN or inf under it leaves no trace; torch multiplies it
+by a zero weight).  A query whose every key is masked gets zeros from the attention, so the layer adds ``out_proj.bias`` only: what torch
+2.10 gives in both grad modes; older releases give NaN.
+
+Out of scope: training and backward, attention masks, bf16, ``num_reg=12`` and the FCAF coder, the loss and ``predict_by_feat``.  There
+is no CPU path: tensors must be on the GPU and the library must be built."""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _abi, decoder_host, query_select
+from .query_select import QuerySelect
+from .sparse import _f32, _ptr
+
+__all__ = ["GroundingDecoder", "attention", "boxes", "contrastive_scores", "layer_norm", "linear", "linear_add_ln", "posembed"]
+
+MAX_SCENES, MAX_QUERIES, MAX_TEXT = 64, 1024, 256
+MAX_CIN, MAX_COUT, MAX_FFN = 2048, 4096, 2048
+LN_EPS = 1e-5
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _gpu(what: str, *tensors) -> None:
+    if not all(t.is_cuda for t in tensors if t is not None):
+        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
+
+
+def _width(what: str, C: int) -> int:
+    C = int(C)
+    if C % 64 or not 64 <= C <= 512:
+        raise ValueError(f"{what}: the feature width must be a multiple of 64 from 64 to 512, got {C}")
+    return C
+
+
+def _bool_bytes(what: str, mask: torch.Tensor, shape) -> torch.Tensor:
+    _gpu(what, mask)
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"{what}: the mask must be {tuple(shape)}, got {tuple(mask.shape)}")
+    if mask.dtype != torch.bool or not mask.is_contiguous():
+        mask = mask.to(torch.bool).contiguous()
+    return mask
+
+
+# ------------------------------------------------------------------------------------------------------------------ the operators
+class _Folded:
+    """A ``PositionEmbeddingLearned`` in eval as ``ptx_dec_posembed`` takes it: the BatchNorm folded into the first Conv1d in float64 on
+    the host, rounded once."""
+
+    def __init__(self, head: nn.Sequential, dev):
+        conv1, bn, conv2 = head[0], head[1], head[3]
+        f64 = lambda t: t.detach().cpu().double().numpy()      # noqa: E731
+        w1, b1 = decoder_host.fold_posembed(f64(conv1.weight), f64(conv1.bias), f64(bn.weight), f64(bn.bias), f64(bn.running_mean),
+                                            f64(bn.running_var), bn.eps)
+        put = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)      # noqa: E731
+        self.cin, self.C = int(w1.shape[1]), int(w1.shape[0])
+        self.w1, self.b1 = put(w1), put(b1)
+        self.w2 = conv2.weight.detach().to(dev, torch.float32).reshape(self.C, self.C).contiguous()
+        self.b2 = conv2.bias.detach().to(dev, torch.float32).contiguous()
+
+
+def _fold(module, dev) -> _Folded:
+    if isinstance(module, _Folded):
+        return module
+    head = module.position_embedding_head if hasattr(module, "position_embedding_head") else module
+    if head[1].training:
+        raise NotImplementedError("posembed: the BatchNorm is in training mode; the eval forward only")
+    return _Folded(head, dev)
+
+
+def posembed(x: torch.Tensor, module) -> torch.Tensor:
+    """``(B,N,C) fp32``: ``PositionEmbeddingLearned`` in eval on ``x (B,N,cin)``, ``cin`` 1 to 9 -- Conv1d, the BatchNorm folded into it,
+    ReLU (a NaN kept), Conv1d (``decoder_host.posembed_host``; ``ptx_dec_posembed``, one launch).  ``module``: the reference's module
+    (or its ``position_embedding_head``)."""
+    _gpu("posembed", x)
+    dev = x.device
+    x = _f32(x, "posembed", dev)
+    f = _fold(module, dev)
+    if x.dim() != 3 or x.shape[2] != f.cin:
+        raise ValueError(f"posembed: x (B,N,{f.cin}) expected, got {tuple(x.shape)}")
+    _width("posembed", f.C)
+    B, N = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty((B, N, f.C), dtype=torch.float32, device=dev)
+    if B * N:
+        _abi.check(_abi.lib().ptx_dec_posembed(x.data_ptr(), B * N, f.cin, f.w1.data_ptr(), f.b1.data_ptr(), f.w2.data_ptr(),
+                                               f.b2.data_ptr(), f.C, out.data_ptr(), _stream(dev)), "ptx_dec_posembed")
+    return out
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor] = None, relu: bool = False,
+           add_cols: Optional[int] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(...,Cout) fp32 = act((x + add) @ weight.T + bias) (+ residual)`` on ``x (...,Cin)``: the add is fused into the operand load and
+    reaches the output columns below ``add_cols`` only (a multiple of 64; default: all).  ``Cin``: a multiple of 64 up to 2048;
+    ``Cout``: a multiple of 64 up to 4096.  The ReLU keeps a NaN (``decoder_host.linear_host``; ``ptx_dec_linear``, one launch)."""
+    _gpu("linear", x, weight, bias, add, residual)
+    dev = x.device
+    x, weight, bias = _f32(x, "linear", dev), _f32(weight, "linear", dev), _f32(bias, "linear", dev)
+    add, residual = _f32(add, "linear", dev), _f32(residual, "linear", dev)
+    if x.dim() < 2 or weight.dim() != 2 or weight.shape[1] != x.shape[-1]:
+        raise ValueError(f"linear: x (...,Cin) and weight (Cout,Cin) expected, got {tuple(x.shape)}, {tuple(weight.shape)}")
+    cin, cout = int(x.shape[-1]), int(weight.shape[0])
+    if cin % 64 or not 64 <= cin <= MAX_CIN or cout % 64 or not 64 <= cout <= MAX_COUT:
+        raise ValueError(f"linear: Cin a multiple of 64 up to {MAX_CIN} and Cout a multiple of 64 up to {MAX_COUT}, got {cin}, {cout}")
+    if add is not None and tuple(add.shape) != tuple(x.shape):
+        raise ValueError(f"linear: add must have x's shape {tuple(x.shape)}, got {tuple(add.shape)}")
+    cols = cout if add_cols is None else int(add_cols)
+    if cols % 64 or not 0 <= cols <= cout:
+        raise ValueError(f"linear: add_cols must be a multiple of 64 from 0 to {cout}, got {cols}")
+    if bias is not None and bias.numel() != cout:
+        raise ValueError(f"linear: bias ({cout}) expected, got {tuple(bias.shape)}")
+    out = torch.empty(tuple(x.shape[:-1]) + (cout,), dtype=torch.float32, device=dev)
+    if residual is not None and tuple(residual.shape) != tuple(out.shape):
+        raise ValueError(f"linear: residual {tuple(out.shape)} expected, got {tuple(residual.shape)}")
+    n = x.numel() // cin
+    if n:
+        _abi.check(_abi.lib().ptx_dec_linear(x.data_ptr(), _ptr(add), cols, n, weight.data_ptr(), _ptr(bias), cin, cout, int(bool(relu)),
+                                             _ptr(residual), out.data_ptr(), _stream(dev)), "ptx_dec_linear")
+    return out
+
+
+def _rows_view(what: str, t: torch.Tensor, dev) -> Tuple[torch.Tensor, int]:
+    """``t (B,n,C)`` as the attention takes it: fp32, unit stride along C, scene b a whole number of rows behind scene b - 1."""
+    if t.device != dev or t.dim() != 3:
+        raise ValueError(f"{what}: (B,n,C) tensors on {dev} expected, got {tuple(t.shape)} on {t.device}")
+    t = t.detach()
+    ok = t.dtype == torch.float32 and t.stride(2) == 1 and t.stride(1) % 4 == 0 and t.stride(1) >= t.shape[2] and \
+        (t.shape[0] == 1 or t.stride(0) == t.shape[1] * t.stride(1)) and t.data_ptr() % 16 == 0
+    if not ok:
+        t = t.to(torch.float32).contiguous()
+    return t, int(t.stride(1))
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], num_heads: int) -> torch.Tensor:
+    """``(B,Kq,C) fp32``: multi-head attention of ``q (B,Kq,C)`` over ``k``, ``v (B,L,C)`` with the key padding mask ``mask (B,L)`` bool,
+    True = ignore (``None``: no key is masked); ``q`` is scaled by ``1/sqrt(hd)``, heads are merged in the output.  The operands may be column ranges of a wider
+    projection output (strided views).  Head dimension 32 or 64.  One flash-style launch: key tiles of 64 in ascending order, an online
+    maximum and sum; a tile that is masked throughout is skipped.  A masked key is never read -- a NaN under it leaves no trace
+    (parity-unpinned: ``nn.MultiheadAttention`` multiplies it by a zero weight).  A query whose every key is masked gets zeros (torch 2.10;
+    older torch gives NaN).  A NaN in an unmasked key or value of a head reaches the outputs of that scene and head
+    (``decoder_host.attention_host``; ``ptx_dec_attention``)."""
+    _gpu("attention", q, k, v, mask)
+    dev = q.device
+    if q.dim() != 3 or k.dim() != 3 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise ValueError(f"attention: q (B,Kq,C), k and v (B,L,C) expected, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    B, Kq, C = (int(s) for s in q.shape)
+    L, H = int(k.shape[1]), int(num_heads)
+    if H < 1 or C % H or C // H not in (32, 64) or C > 512:
+        raise ValueError(f"attention: a head dimension of 32 or 64 and C up to 512, got C={C} with {H} heads")
+    if not 1 <= B <= MAX_SCENES or not 0 <= Kq <= MAX_QUERIES:
+        raise ValueError(f"attention: 1 to {MAX_SCENES} scenes and up to {MAX_QUERIES} queries, got B={B}, Kq={Kq}")
+    if mask is not None:
+        mask = _bool_bytes("attention", mask, (B, L))
+    out = torch.empty((B, Kq, C), dtype=torch.float32, device=dev)
+    if Kq == 0:
+        return out
+    if L == 0:
+        return out.zero_()
+    (q, ldq), (k, ldk), (v, ldv) = _rows_view("attention", q, dev), _rows_view("attention", k, dev), _rows_view("attention", v, dev)
+    _abi.check(_abi.lib().ptx_dec_attention(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, _ptr(mask), B, Kq, L, H, C // H,
+                                            out.data_ptr(), _stream(dev)), "ptx_dec_attention")
+    return out
+
+
+def _ln_pair(ln) -> Tuple[torch.Tensor, torch.Tensor, float]:
+    if isinstance(ln, nn.LayerNorm):
+        return ln.weight, ln.bias, float(ln.eps)
+    return ln[0], ln[1], float(ln[2]) if len(ln) > 2 else LN_EPS
+
+
+def layer_norm(x: torch.Tensor, ln, ln2=None, out2: Optional[torch.Tensor] = None):
+    """``LayerNorm(x)`` over the last axis of ``x (...,C)``; with ``ln2`` also ``LayerNorm2`` of that result: ``(out, out2)``.  ``ln``:
+    an ``nn.LayerNorm`` or ``(weight, bias[, eps])``.  The row mean first, then the centred sum of squares
+    (``decoder_host.layer_norm_host``; ``ptx_dec_ln``, one launch).  ``out2``: a contiguous fp32 tensor of x's shape that receives the
+    second result (a layer's slot of ``hidden_states``)."""
+    _gpu("layer_norm", x)
+    dev = x.device
+    x = _f32(x, "layer_norm", dev)
+    C = _width("layer_norm", x.shape[-1])
+    w, b, eps = _ln_pair(ln)
+    w, b = _f32(w, "layer_norm", dev), _f32(b, "layer_norm", dev)
+    w2 = b2 = None
+    if ln2 is None:
+        out2 = None
+    else:
+        w2, b2, eps2 = _ln_pair(ln2)
+        if eps2 != eps:
+            raise ValueError(f"layer_norm: both norms must share eps, got {eps} and {eps2}")
+        w2, b2 = _f32(w2, "layer_norm", dev), _f32(b2, "layer_norm", dev)
+        if out2 is None:
+            out2 = torch.empty_like(x)
+        elif out2.dtype != torch.float32 or not out2.is_contiguous() or tuple(out2.shape) != tuple(x.shape) or out2.device != dev:
+            raise ValueError(f"layer_norm: out2 must be contiguous fp32 {tuple(x.shape)} on {dev}")
+    if any(t is not None and t.numel() != C for t in (w, b, w2, b2)):
+        raise ValueError(f"layer_norm: weight and bias ({C}) expected")
+    out = torch.empty_like(x)
+    n = x.numel() // C
+    if n:
+        _abi.check(_abi.lib().ptx_dec_ln(x.data_ptr(), n, C, w.data_ptr(), b.data_ptr(), eps, out.data_ptr(), _ptr(w2), _ptr(b2), _ptr(out2),
+                                         _stream(dev)), "ptx_dec_ln")
+    return out if ln2 is None else (out, out2)
+
+
+def linear_add_ln(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], residual: torch.Tensor, ln, ln2=None,
+                  out2: Optional[torch.Tensor] = None):
+    """``LayerNorm(x @ weight.T + bias + residual)``: an attention's out-projection or the FFN's second layer, the identity and the
+    norm behind it; with ``ln2`` also the decoder's ``norm`` of that result, ``(out, out2)``.  Two launches: the residual is added in the
+    GEMM's epilogue, the norm needs whole rows (``decoder_host.linear_add_ln_host``)."""
+    return layer_norm(linear(x, weight, bias, residual=residual), ln, ln2, out2)
+
+
+def boxes(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], coords: torch.Tensor,
+          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(B,K,9)``: the last Linear ``weight (9,C)`` of a regression branch on ``h (B,K,C)`` and the baseline decode against
+    ``coords (B,K,3)`` -- ``center = p[0:3] + coords``, ``size = max(expf(p[3:6]), 0.02)`` with a NaN kept, ``euler = p[6:9]``
+    (``query_select_host.boxes_host``; ``ptx_dec_boxes``, one launch)."""
+    _gpu("boxes", h, weight, bias, coords)
+    dev = h.device
+    h, weight, bias, coords = _f32(h, "boxes", dev), _f32(weight, "boxes", dev), _f32(bias, "boxes", dev), _f32(coords, "boxes", dev)
+    C = _width("boxes", h.shape[-1])
+    if tuple(weight.shape) != (9, C) or (bias is not None and bias.numel() != 9) or tuple(coords.shape) != tuple(h.shape[:-1]) + (3,):
+        raise ValueError(f"boxes: weight (9,{C}), bias (9) and coords {tuple(h.shape[:-1]) + (3,)} expected, got {tuple(weight.shape)}, "
+                         f"{None if bias is None else tuple(bias.shape)}, {tuple(coords.shape)}")
+    if out is None:
+        out = torch.empty(tuple(h.shape[:-1]) + (9,), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != tuple(h.shape[:-1]) + (9,) or out.device != dev:
+        raise ValueError(f"boxes: out must be contiguous fp32 {tuple(h.shape[:-1]) + (9,)} on {dev}")
+    n = h.numel() // C
+    if n:
+        _abi.check(_abi.lib().ptx_dec_boxes(h.data_ptr(), weight.data_ptr(), _ptr(bias), C, coords.data_ptr(), n, out.data_ptr(),
+                                            _stream(dev)), "ptx_dec_boxes")
+    return out
+
+
+def contrastive_scores(hidden_states: torch.Tensor, text_feats: torch.Tensor, text_token_mask: torch.Tensor,
+                       bias: Optional[torch.Tensor] = None, scaled: bool = True, max_text_len: int = 256) -> torch.Tensor:
+    """``(NL,B,K,max_text_len) fp32``: ``ContrastiveEmbed`` in full on every layer's ``hidden_states (NL,B,K,C)`` --
+    ``hidden . text[b,t] (/ sqrtf(C)) (+ bias)`` on the tokens with ``text_token_mask[b,t]``, ``-inf`` on masked tokens and on the columns
+    from ``T`` on (``decoder_host.contrastive_scores_host``; ``ptx_dec_scores``, one launch)."""
+    _gpu("contrastive_scores", hidden_states, text_feats, text_token_mask, bias)
+    dev = hidden_states.device
+    hs, text, bias = _f32(hidden_states, "contrastive_scores", dev), _f32(text_feats, "contrastive_scores", dev), \
+        _f32(bias, "contrastive_scores", dev)
+    if hs.dim() != 4 or text.dim() != 3 or text.shape[0] != hs.shape[1] or text.shape[2] != hs.shape[3]:
+        raise ValueError(f"contrastive_scores: hidden_states (NL,B,K,C) and text_feats (B,T,C) expected, got {tuple(hs.shape)}, "
+                         f"{tuple(text.shape)}")
+    NL, B, K, C = (int(s) for s in hs.shape)
+    _width("contrastive_scores", C)
+    T, M = int(text.shape[1]), int(max_text_len)
+    if not 1 <= T <= M <= MAX_TEXT or not 1 <= B <= MAX_SCENES or not 0 <= K <= MAX_QUERIES or NL > 64:
+        raise ValueError(f"contrastive_scores: 1 <= T <= max_text_len <= {MAX_TEXT}, 1 to {MAX_SCENES} scenes, up to {MAX_QUERIES} queries and "
+                         f"64 layers, got T={T}, max_text_len={M}, B={B}, K={K}, NL={NL}")
+    mask = _bool_bytes("contrastive_scores", text_token_mask, (B, T))
+    out = torch.empty((NL, B, K, M), dtype=torch.float32, device=dev)
+    if NL * K:
+        _abi.check(_abi.lib().ptx_dec_scores(hs.data_ptr(), NL, B, K, C, text.data_ptr(), mask.data_ptr(), T, M, int(bool(scaled)), _ptr(bias),
+                                             out.data_ptr(), _stream(dev)), "ptx_dec_scores")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ the module
+class _PositionEmbeddingLearned(nn.Module):
+    def __init__(self, input_channel: int, embed_dims: int):
+        super().__init__()
+        self.position_embedding_head = nn.Sequential(nn.Conv1d(input_channel, embed_dims, kernel_size=1), nn.BatchNorm1d(embed_dims),
+                                                     nn.ReLU(inplace=True), nn.Conv1d(embed_dims, embed_dims, kernel_size=1))
+
+
+class _Attention(nn.Module):
+    """The place of mmcv's ``MultiheadAttention``: its parameters live below ``attn`` (an ``nn.MultiheadAttention``, never called)."""
+
+    def __init__(self, embed_dims: int = 256, num_heads: int = 8, attn_drop: float = 0.0, proj_drop: float = 0.0, dropout=None,
+                 dropout_layer=None, init_cfg=None, batch_first: bool = True, **kwargs):
+        super().__init__()
+        self.embed_dims, self.num_heads = _width("GroundingDecoder", embed_dims), int(num_heads)
+        if self.num_heads < 1 or self.embed_dims % self.num_heads or self.embed_dims // self.num_heads not in (32, 64):
+            raise ValueError(f"GroundingDecoder: the head dimension must be 32 or 64, got embed_dims={embed_dims} with {num_heads} heads")
+        if not batch_first:
+            raise ValueError("GroundingDecoder: batch_first must be True")
+        self.attn = nn.MultiheadAttention(self.embed_dims, self.num_heads, 0.0, **kwargs)
+
+
+class _FFN(nn.Module):
+    def __init__(self, embed_dims: int = 256, feedforward_channels: int = 1024, num_fcs: int = 2, act_cfg=None, ffn_drop: float = 0.0,
+                 dropout_layer=None, add_identity: bool = True, init_cfg=None, layer_scale_init_value: float = 0.0, **kwargs):
+        super().__init__()
+        act = "ReLU" if act_cfg is None else act_cfg.get("type", "ReLU")
+        if int(num_fcs) != 2 or act != "ReLU" or not add_identity or layer_scale_init_value:
+            raise NotImplementedError(f"GroundingDecoder: the FFN with num_fcs=2, ReLU and the identity is implemented, got num_fcs={num_fcs}, "
+                                      f"act {act!r}, add_identity={add_identity}, layer_scale_init_value={layer_scale_init_value}")
+        F = int(feedforward_channels)
+        if F % 64 or not 64 <= F <= MAX_FFN:
+            raise ValueError(f"GroundingDecoder: feedforward_channels must be a multiple of 64 up to {MAX_FFN}, got {F}")
+        self.embed_dims, self.feedforward_channels = _width("GroundingDecoder", embed_dims), F
+        self.layers = nn.Sequential(nn.Sequential(nn.Linear(self.embed_dims, F), nn.ReLU(inplace=True), nn.Dropout(ffn_drop)),
+                                    nn.Linear(F, self.embed_dims), nn.Dropout(ffn_drop))
+
+
+class _Layer(nn.Module):
+    def __init__(self, self_attn_cfg=None, cross_attn_cfg=None, cross_attn_text_cfg=None, ffn_cfg=None, norm_cfg=None, init_cfg=None):
+        super().__init__()
+        if norm_cfg is not None and norm_cfg.get("type", "LN") != "LN":
+            raise NotImplementedError(f"GroundingDecoder: norm_cfg type 'LN' is implemented, got {norm_cfg!r}")
+        self.self_attn = _Attention(**(self_attn_cfg or {}))
+        self.cross_attn_text = _Attention(**(cross_attn_text_cfg or {}))
+        self.cross_attn = _Attention(**(cross_attn_cfg or {}))
+        self.embed_dims = self.self_attn.embed_dims
+        self.ffn = _FFN(**(ffn_cfg or {}))
+        widths = {self.cross_attn_text.embed_dims, self.cross_attn.embed_dims, self.ffn.embed_dims}
+        if widths != {self.embed_dims}:
+            raise ValueError(f"GroundingDecoder: every part of a layer must share embed_dims={self.embed_dims}, got {sorted(widths)}")
+        self.norms = nn.ModuleList([nn.LayerNorm(self.embed_dims) for _ in range(4)])
+        self.self_posembed = _PositionEmbeddingLearned(3, self.embed_dims)          # constructed by the reference, never called
+
+
+class GroundingDecoder(nn.Module):
+    """``SparseFeatureFusionTransformerDecoder(num_layers, layer_cfg, post_norm_cfg=None, return_intermediate=True, init_cfg=None,
+    with_cp=None)``, eval forward.  ``layer_cfg`` holds ``self_attn_cfg``, ``cross_attn_text_cfg``, ``cross_attn_cfg`` (``embed_dims``,
+    ``num_heads``; dropout rates are accepted: dropout is the identity in eval) and ``ffn_cfg`` (``embed_dims``, ``feedforward_channels``,
+    ``num_fcs=2``, ReLU), the reference's defaults where a key is missing.  The ``state_dict`` carries the reference's names, so a
+    checkpoint's ``decoder.*`` loads with ``strict=True``; the per-layer ``layers.{i}.self_posembed`` loads and is never read, as in the
+    reference.  ``with_cp`` is accepted and ignored.
+
+    ``forward(query, key, value, key_padding_mask, self_attn_mask, cross_attn_mask, query_coords, key_coords, pred_bboxes, text_feats,
+    text_attention_mask, bbox_head, **kwargs)`` takes what ``forward_decoder`` passes -- ``**QuerySelect(...)[0]`` after the detector's
+    renaming (``feats -> key`` and ``value``, ``feats_attention_mask -> key_padding_mask``, ``feats_coords -> key_coords``) -- and returns
+    ``(hidden_states (NL,B,K,C), all_layers_pred_bboxes (NL,B,K,9))``, or the last layer's ``(query, boxes)`` when
+    ``return_intermediate=False``.  ``bbox_head``: an object with an indexable ``reg_branches``, a sequence of ``num_layers`` regression
+    branches, or a ``QuerySelect``, whose ``reg_branch`` then serves every layer (``share_pred_layer=True``).
+
+    Accepted: ``embed_dims`` a multiple of 64 from 64 to 512, head dimension 32 or 64, ``feedforward_channels`` a multiple of 64 up to
+    2048, ``1 <= B <= 64``, ``0 <= K <= 1024``, ``1 <= T <= 256``; ``K = 0`` or ``Lmax = 0`` returns correctly shaped empties and launches
+    nothing.  Refused: ``post_norm_cfg`` (ValueError, as in the reference), attention masks and ``value is not key``
+    (NotImplementedError), training mode or an input that requires grad with grad mode on (NotImplementedError), ``bbox_head=None``
+    (ValueError; the reference fails on an undefined name there)."""
+
+    def __init__(self, num_layers: int, layer_cfg: dict, post_norm_cfg=None, return_intermediate: bool = True, init_cfg=None, with_cp=None):
+        super().__init__()
+        self.layer_cfg, self.num_layers = layer_cfg, int(num_layers)
+        self.post_norm_cfg, self.return_intermediate, self.with_cp = post_norm_cfg, bool(return_intermediate), with_cp
+        if not 1 <= self.num_layers <= 64:
+            raise ValueError(f"GroundingDecoder: num_layers must be 1 to 64, got {num_layers}")
+        self.layers = nn.ModuleList([_Layer(**{k: (dict(v) if isinstance(v, dict) else v) for k, v in dict(layer_cfg or {}).items()})
+                                     for _ in range(self.num_layers)])
+        self.embed_dims = self.layers[0].embed_dims
+        if post_norm_cfg is not None:
+            raise ValueError(f"There is not post_norm in {type(self).__name__}")
+        self.self_posembed = _PositionEmbeddingLearned(9, self.embed_dims)
+        self.cross_posembed = _PositionEmbeddingLearned(3, self.embed_dims)
+        self.norm = nn.LayerNorm(self.embed_dims)
+        self._prepared = None
+
+    # -- the operands the launches take, rebuilt when a parameter changes
+    def _apply(self, fn, *args, **kwargs):
+        self._prepared = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def _state_key(self, dev):
+        return (str(dev),) + tuple(t._version for t in self._tensors())
+
+    def _tensors(self):
+        return list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
+
+    def _prepare(self, dev) -> dict:
+        key = self._state_key(dev)
+        if self._prepared is not None and self._prepared["key"] == key:
+            return self._prepared
+        C, NL = self.embed_dims, self.num_layers
+        group = max(1, MAX_COUT // (2 * C))                  # layers per hoisted key/value projection
+        f = lambda t: t.detach().to(dev, torch.float32)       # noqa: E731
+        prep = dict(key=key, self_pos=_fold(self.self_posembed, dev), cross_pos=_fold(self.cross_posembed, dev), groups=[], layers=[])
+        with torch.no_grad():
+            for lo in range(0, NL, group):
+                ids = list(range(lo, min(lo + group, NL)))
+                entry = dict(ids=ids)
+                for name in ("cross_attn", "cross_attn_text"):
+                    ws = [f(getattr(self.layers[i], name).attn.in_proj_weight) for i in ids]
+                    bs = [f(getattr(self.layers[i], name).attn.in_proj_bias) for i in ids]
+                    entry[name] = (torch.cat([w[C:2 * C] for w in ws] + [w[2 * C:] for w in ws]).contiguous(),
+                                   torch.cat([b[C:2 * C] for b in bs] + [b[2 * C:] for b in bs]).contiguous())
+                prep["groups"].append(entry)
+            for layer in self.layers:
+                d = {}
+                for name in ("self_attn", "cross_attn_text", "cross_attn"):
+                    a = getattr(layer, name).attn
+                    w, b = f(a.in_proj_weight).contiguous(), f(a.in_proj_bias).contiguous()
+                    d[name] = dict(w=w, b=b, wq=w[:C], bq=b[:C], wkv=w[C:], bkv=b[C:], wo=f(a.out_proj.weight).contiguous(),
+                                   bo=f(a.out_proj.bias).contiguous(), H=getattr(layer, name).num_heads)
+                prep["layers"].append(d)
+        self._prepared = prep
+        return prep
+
+    @staticmethod
+    def _branches(bbox_head, num_layers: int) -> List[List[nn.Linear]]:
+        if bbox_head is None:
+            raise ValueError("GroundingDecoder: bbox_head is None; the decoder refines its boxes with the head's regression branches")
+        if isinstance(bbox_head, QuerySelect):
+            branches = [bbox_head.reg_branch] * num_layers
+        elif hasattr(bbox_head, "reg_branches"):
+            branches = [bbox_head.reg_branches[i] for i in range(num_layers)]
+        else:
+            branches = list(bbox_head)
+            if len(branches) < num_layers:
+                raise ValueError(f"GroundingDecoder: {num_layers} regression branches expected, got {len(branches)}")
+        out = []
+        for br in branches[:num_layers]:
+            lins = [m for m in (br if isinstance(br, (nn.Sequential, list, tuple)) else [br]) if isinstance(m, nn.Linear)]
+            if not lins or lins[-1].out_features != 9:
+                raise NotImplementedError("GroundingDecoder: a regression branch of Linear (+ ReLU) layers ending in 9 values expected "
+                                          "(num_reg=12 is not implemented)")
+            out.append(lins)
+        return out
+
+    def _check(self, query, key, value, key_padding_mask, self_attn_mask, cross_attn_mask, query_coords, key_coords, pred_bboxes, text_feats,
+               text_attention_mask):
+        if self_attn_mask is not None or cross_attn_mask is not None:
+            raise NotImplementedError("GroundingDecoder: self_attn_mask and cross_attn_mask are not implemented; pass None")
+        if value is not key:
+            raise NotImplementedError("GroundingDecoder: value must be key (the detector passes the same tensor)")
+        tensors = [query, key, key_padding_mask, query_coords, key_coords, pred_bboxes, text_feats, text_attention_mask]
+        if not all(isinstance(t, torch.Tensor) for t in tensors):
+            raise TypeError("GroundingDecoder: the operands must be tensors")
+        if self.training:
+            raise NotImplementedError("GroundingDecoder: the eval forward only; call .eval() (training through the decoder is not implemented)")
+        if torch.is_grad_enabled() and any(t.is_floating_point() and t.requires_grad for t in tensors):
+            raise NotImplementedError("GroundingDecoder is inference-only: an input requires grad; call it under torch.no_grad() or detach")
+        C = self.embed_dims
+        if query.dim() != 3 or query.shape[2] != C:
+            raise ValueError(f"GroundingDecoder: query (B,K,{C}) expected, got {tuple(query.shape)}")
+        B, K = int(query.shape[0]), int(query.shape[1])
+        if key.dim() != 3 or key.shape[0] != B or key.shape[2] != C:
+            raise ValueError(f"GroundingDecoder: key ({B},Lmax,{C}) expected, got {tuple(key.shape)}")
+        L = int(key.shape[1])
+        if text_feats.dim() != 3 or text_feats.shape[0] != B or text_feats.shape[2] != C:
+            raise ValueError(f"GroundingDecoder: text_feats ({B},T,{C}) expected, got {tuple(text_feats.shape)}")
+        T = int(text_feats.shape[1])
+        if not 1 <= B <= MAX_SCENES or not 0 <= K <= MAX_QUERIES or not 1 <= T <= MAX_TEXT:
+            raise ValueError(f"GroundingDecoder: 1 to {MAX_SCENES} scenes, 0 to {MAX_QUERIES} queries and 1 to {MAX_TEXT} text tokens, got B={B}, "
+                             f"K={K}, T={T}")
+        for name, t, shape in (("key_padding_mask", key_padding_mask, (B, L)), ("query_coords", query_coords, (B, K, 3)),
+                               ("key_coords", key_coords, (B, L, 3)), ("pred_bboxes", pred_bboxes, (B, K, 9)),
+                               ("text_attention_mask", text_attention_mask, (B, T))):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"GroundingDecoder: {name} {shape} expected, got {tuple(t.shape)}")
+        if not all(t.is_cuda for t in tensors):
+            raise RuntimeError("GroundingDecoder (HIP) needs GPU tensors: there is no CPU path")
+        return B, K, L, T
+
+    def forward(self, query, key, value, key_padding_mask, self_attn_mask, cross_attn_mask, query_coords, key_coords, pred_bboxes, text_feats,
+                text_attention_mask, bbox_head, **kwargs):
+        branches = self._branches(bbox_head, self.num_layers)
+        B, K, L, T = self._check(query, key, value, key_padding_mask, self_attn_mask, cross_attn_mask, query_coords, key_coords, pred_bboxes,
+                                 text_feats, text_attention_mask)
+        dev, C, NL = query.device, self.embed_dims, self.num_layers
+        if K == 0 or L == 0:                                 # nothing to decode: the shapes, no launch
+            if self.return_intermediate:
+                return (torch.zeros((NL, B, K, C), dtype=torch.float32, device=dev), torch.zeros((NL, B, K, 9), dtype=torch.float32, device=dev))
+            return torch.zeros((B, K, C), dtype=torch.float32, device=dev), torch.zeros((B, K, 9), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            return self._run(branches, _f32(query, "GroundingDecoder", dev), _f32(key, "GroundingDecoder", dev), key_padding_mask,
+                             _f32(query_coords, "GroundingDecoder", dev), _f32(key_coords, "GroundingDecoder", dev),
+                             _f32(pred_bboxes, "GroundingDecoder", dev), _f32(text_feats, "GroundingDecoder", dev), text_attention_mask)
+
+    def _run(self, branches, query, key, pad, qcoords, kcoords, bboxes, text, tmask):
+        dev, C, NL = query.device, self.embed_dims, self.num_layers
+        B, K, T = int(query.shape[0]), int(query.shape[1]), int(text.shape[1])
+        prep = self._prepare(dev)
+        pad, tmask = _bool_bytes("GroundingDecoder", pad, tuple(key.shape[:2])), _bool_bytes("GroundingDecoder", tmask, (B, T))
+        text_keys_take_pos = T == K                          # mmcv: key_pos = query_pos when the shapes agree
+        key_pos = posembed(kcoords, prep["cross_pos"])
+        scene_kv, text_kv = {}, {}
+        for g in prep["groups"]:                             # every layer's scene (and text) keys and values, ahead of the layer loop
+            n = len(g["ids"])
+            w, b = g["cross_attn"]
+            kv = linear(key, w, b, add=key_pos, add_cols=n * C)
+            for j, lid in enumerate(g["ids"]):
+                scene_kv[lid] = (kv[:, :, j * C:(j + 1) * C], kv[:, :, (n + j) * C:(n + j + 1) * C])
+            if not text_keys_take_pos:
+                w, b = g["cross_attn_text"]
+                kv = linear(text, w, b)
+                for j, lid in enumerate(g["ids"]):
+                    text_kv[lid] = (kv[:, :, j * C:(j + 1) * C], kv[:, :, (n + j) * C:(n + j + 1) * C])
+        hidden = torch.empty((NL, B, K, C), dtype=torch.float32, device=dev) if self.return_intermediate else None
+        all_boxes = torch.empty((NL, B, K, 9), dtype=torch.float32, device=dev) if self.return_intermediate else None
+        for lid, (layer, p) in enumerate(zip(self.layers, prep["layers"])):
+            query_pos = posembed(bboxes, prep["self_pos"])
+            a = p["self_attn"]
+            qkv = linear(query, a["w"], a["b"], add=query_pos, add_cols=2 * C)
+            o = attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], None, a["H"])
+            query = linear_add_ln(o, a["wo"], a["bo"], query, layer.norms[0])
+            a = p["cross_attn_text"]
+            q = linear(query, a["wq"], a["bq"], add=query_pos)
+            if text_keys_take_pos:
+                kv = linear(text, a["wkv"], a["bkv"], add=query_pos, add_cols=C)
+                tk, tv = kv[:, :, :C], kv[:, :, C:]
+            else:
+                tk, tv = text_kv[lid]
+            query = linear_add_ln(attention(q, tk, tv, tmask, a["H"]), a["wo"], a["bo"], query, layer.norms[1])
+            a = p["cross_attn"]
+            q = linear(query, a["wq"], a["bq"], add=query_pos)
+            query = linear_add_ln(attention(q, *scene_kv[lid], pad, a["H"]), a["wo"], a["bo"], query, layer.norms[2])
+            fc1, fc2 = layer.ffn.layers[0][0], layer.ffn.layers[1]
+            h = linear(query, fc1.weight, fc1.bias, relu=True)
+            if self.return_intermediate:
+                query, _ = linear_add_ln(h, fc2.weight, fc2.bias, query, layer.norms[3], self.norm, out2=hidden[lid])
+            else:
+                query = linear_add_ln(h, fc2.weight, fc2.bias, query, layer.norms[3])
+            lins = branches[lid]
+            h = query
+            for lin in lins[:-1]:
+                h = query_select.linear(h, lin.weight, lin.bias, None, relu=True)
+            bboxes = boxes(h, lins[-1].weight, lins[-1].bias, qcoords, out=all_boxes[lid] if self.return_intermediate else None)
+        if self.return_intermediate:
+            return hidden, all_boxes
+        return query, bboxes
+
+    def head_scores(self, hidden_states: torch.Tensor, head_inputs_dict: dict, query_select: QuerySelect) -> torch.Tensor:
+        """``GroundingHead.forward``'s ``all_layers_cls_scores (NL,B,K,max_text_len)`` with the ``QuerySelect``'s ``cls_branch``."""
+        qs = query_select
+        return contrastive_scores(hidden_states, head_inputs_dict["text_feats"], head_inputs_dict["text_token_mask"],
+                                  qs.cls_branch.bias if qs.has_bias else None, qs.scaled, qs.max_text_len)
+
+    def forward_host(self, query, key, key_padding_mask, query_coords, key_coords, pred_bboxes, text_feats, text_attention_mask, bbox_head,
+                     dtype=np.float64, **kw):
+        """The same chain from ``decoder_host.py`` in numpy ``dtype`` with this module's parameters."""
+        dt = np.dtype(dtype)
+        arr = lambda t, d=dt: (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(d)      # noqa: E731
+        branches = self._branches(bbox_head, self.num_layers)
+        layer = self.layers[0]
+        return decoder_host.forward_host(
+            {k: arr(v, np.float64) for k, v in self.state_dict().items()}, self.num_layers,
+            (layer.self_attn.num_heads, layer.cross_attn_text.num_heads, layer.cross_attn.num_heads), arr(query), arr(key),
+            arr(key_padding_mask, bool), arr(query_coords), arr(key_coords), arr(pred_bboxes), arr(text_feats), arr(text_attention_mask, bool),
+            [[arr(m.weight) for m in lins] for lins in branches], [[arr(m.bias) for m in lins] for lins in branches], dtype=dt,
+            return_intermediate=self.return_intermediate, **kw)

@@ -1,6 +1,6 @@
 """Query selection behind ``MinkNeck``: the detector's ``pre_decoder`` (detectors/sparse_featfusion_grounder_preshape.py:498-580, the same
 body in sparse_featfusion_grounder.py:325-407) on the device.  It turns the three lists ``MinkNeck.forward`` returns into the operands of
-the (plain torch) transformer decoder: pad to a batch, score every row against the text tokens (``ContrastiveEmbed`` and its maximum
+the transformer decoder (``decoder.py``): pad to a batch, score every row against the text tokens (``ContrastiveEmbed`` and its maximum
 over the tokens), take the per-scene top ``num_queries`` rows in sorted order, run the regression branch and decode 9-value boxes on the
 selected rows, gather queries and coordinates.
 
@@ -18,7 +18,7 @@ Training (``QuerySelect(..., differentiable=True)``): one autograd node covers `
 detached values, as ``torch.topk(...)[1]`` does; the text, the coordinates and the regression branch get no gradient from this stage
 (``pred_bboxes.detach()``).
 
-Out of scope: the decoder layers and the head's loss, ``num_reg=12``, the FCAF coder, a learnable ``log_scale``, double backward, bf16.
+Out of scope: the head's loss (the decoder layers are ``decoder.py``), ``num_reg=12``, the FCAF coder, a learnable ``log_scale``, double backward, bf16.
 There is no CPU path: tensors must be on the GPU and the library must be built."""
 from __future__ import annotations
 

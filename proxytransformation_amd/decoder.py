@@ -352,7 +352,11 @@ class GroundingDecoder(nn.Module):
     2048, ``1 <= B <= 64``, ``0 <= K <= 1024``, ``1 <= T <= 256``; ``K = 0`` or ``Lmax = 0`` returns correctly shaped empties and launches
     nothing.  Refused: ``post_norm_cfg`` (ValueError, as in the reference), attention masks and ``value is not key``
     (NotImplementedError), training mode or an input that requires grad with grad mode on (NotImplementedError), ``bbox_head=None``
-    (ValueError; the reference fails on an undefined name there)."""
+    (ValueError; the reference fails on an undefined name there).
+
+    The operands the launches take (concatenated projections, folded position embeddings) are prepared once and rebuilt when a parameter
+    or buffer is replaced or its ``_version`` changes (``load_state_dict``, in-place updates).  A write through ``.data`` bumps no
+    version and is not seen: move the module (``.to``) or write in place under ``no_grad`` instead."""
 
     def __init__(self, num_layers: int, layer_cfg: dict, post_norm_cfg=None, return_intermediate: bool = True, init_cfg=None, with_cp=None):
         super().__init__()
@@ -376,7 +380,9 @@ class GroundingDecoder(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
     def _state_key(self, dev):
-        return (str(dev),) + tuple(t._version for t in self._tensors())
+        """The device and every tensor's identity and ``_version``: a parameter REPLACED by another one of the same version is a change
+        too.  ``_prepare`` keeps the tensors it was built from alive, so that no new tensor can take the ``id`` of a freed one."""
+        return (str(dev),) + tuple((id(t), t.data_ptr(), t._version) for t in self._tensors())
 
     def _tensors(self):
         return list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
@@ -388,7 +394,8 @@ class GroundingDecoder(nn.Module):
         C, NL = self.embed_dims, self.num_layers
         group = max(1, MAX_COUT // (2 * C))                  # layers per hoisted key/value projection
         f = lambda t: t.detach().to(dev, torch.float32)       # noqa: E731
-        prep = dict(key=key, self_pos=_fold(self.self_posembed, dev), cross_pos=_fold(self.cross_posembed, dev), groups=[], layers=[])
+        prep = dict(key=key, tensors=self._tensors(), self_pos=_fold(self.self_posembed, dev), cross_pos=_fold(self.cross_posembed, dev),
+                    groups=[], layers=[])
         with torch.no_grad():
             for lo in range(0, NL, group):
                 ids = list(range(lo, min(lo + group, NL)))

@@ -13,11 +13,35 @@ from tests import query_select_util as qu
 DEC_ENTRY_POINTS = ("ptx_dec_posembed", "ptx_dec_linear", "ptx_dec_attention", "ptx_dec_ln", "ptx_dec_boxes", "ptx_dec_scores")
 SMALL = dict(C=64, heads=2, ffn=128, layers=2)
 E2E = dict(C=256, heads=8, ffn=2048, layers=6)
+# more than one group of hoisted key/value projections (4096 // 2C layers per group): 4 + 1 at C = 512 with a head count per attention
+# (self, text, scene), 8 + 1 at C = 256
+WIDE = dict(C=512, heads=(8, 16, 8), ffn=64, layers=5)
+DEEP = dict(C=256, heads=8, ffn=64, layers=9)
+GROUP_ROWS, GROUP_K = (65, 1, 130), 3
+
+
+def group_operands(C, T, seed):
+    """The operands of the hoisted-group cases: rows (65, 1, 130), K = 3, ``T`` text tokens, two tokens of scene 1 masked."""
+    tm = np.zeros((len(GROUP_ROWS), T), bool)
+    tm[1, [0, T - 1]] = True
+    return operands(GROUP_ROWS, GROUP_K, T, C, seed, tm)
+
+
+def scene_alone(ops, b):
+    """Scene ``b`` of ``ops`` as a batch of one with its keys cut to its own length."""
+    n = int((~ops["key_padding_mask"][b]).sum())
+    assert n >= 1 and not ops["key_padding_mask"][b, :n].any()
+    cut = lambda a: np.ascontiguousarray(a[b:b + 1, :n])      # noqa: E731
+    out = {k: np.ascontiguousarray(v[b:b + 1]) for k, v in ops.items()}
+    out.update(key=cut(ops["key"]), key_padding_mask=cut(ops["key_padding_mask"]), key_coords=cut(ops["key_coords"]))
+    return out
 
 
 def layer_cfg(C, heads, ffn):
-    return dict(self_attn_cfg=dict(embed_dims=C, num_heads=heads, dropout=0.0), cross_attn_text_cfg=dict(embed_dims=C, num_heads=heads),
-                cross_attn_cfg=dict(embed_dims=C, num_heads=heads), ffn_cfg=dict(embed_dims=C, feedforward_channels=ffn, ffn_drop=0.0))
+    """``heads``: one count for the three attentions, or ``(self, text, scene)``."""
+    hs, ht, hc = (heads,) * 3 if isinstance(heads, int) else tuple(heads)
+    return dict(self_attn_cfg=dict(embed_dims=C, num_heads=hs, dropout=0.0), cross_attn_text_cfg=dict(embed_dims=C, num_heads=ht),
+                cross_attn_cfg=dict(embed_dims=C, num_heads=hc), ffn_cfg=dict(embed_dims=C, feedforward_channels=ffn, ffn_drop=0.0))
 
 
 def module(C=256, heads=8, ffn=2048, layers=6, seed=21, **kw):

@@ -184,6 +184,67 @@ def test_refusals():
             call()
 
 
+def test_host_chain_with_two_groups_of_hoisted_projections_is_the_torch_stage():
+    """C = 512, heads (self 8, text 16, scene 8), FFN 64, 5 layers -- the module tests/test_gpu_decoder_edges.py runs because its key /
+    value projections leave the layer loop in two groups (4 + 1 layers) -- on rows (65, 1, 130), K = 3, at T = 5 and at T = K = 3: the
+    float64 host chain is the torch stage, and the fp32 host chain is a yardstick (within 1e-5 of float64); the latter also for the
+    C = 256 module of 9 layers (8 + 1)."""
+    m, br = du.module(**du.WIDE), du.reg_branches(512, 5)
+    layer = m.layers[0]
+    assert (layer.self_attn.num_heads, layer.cross_attn_text.num_heads, layer.cross_attn.num_heads) == (8, 16, 8)
+    assert [g["ids"] for g in m._prepare(torch.device("cpu"))["groups"]] == [[0, 1, 2, 3], [4]]
+    deep, dbr = du.module(**du.DEEP), du.reg_branches(256, 9)
+    assert [g["ids"] for g in deep._prepare(torch.device("cpu"))["groups"]] == [list(range(8)), [8]]
+    for T in (5, 3):
+        ops = du.group_operands(512, T, 11)
+        assert ops["text_attention_mask"].sum() == 2 and ops["key"].shape == (3, 130, 512)
+        h64, b64 = du.host(m, ops, br, np.float64)
+        th, tb = du.torch_stage(m, ops, br)
+        _close(h64, th)
+        _close(b64, tb)
+        cases = [("C=512", du.host(m, ops, br, np.float32), (h64, b64))]
+        dops = du.group_operands(256, T, 12)
+        cases.append(("C=256", du.host(deep, dops, dbr, np.float32), du.host(deep, dops, dbr, np.float64)))
+        for name, r32, r64 in cases:
+            for a32, a64 in zip(r32, r64):
+                assert a32.dtype == np.float32 and a64.dtype == np.float64
+                for lid in range(len(a64)):
+                    assert su.rel(a32[lid], a64[lid]) < 1e-5, (name, T, lid)
+
+
+def test_prepared_operands_are_rebuilt_when_a_parameter_is_replaced_or_changed():
+    """``_prepare`` returns the same object while nothing changed, and a new one after ``load_state_dict``, an in-place update under
+    ``no_grad`` (a parameter, a BatchNorm buffer) and after a parameter is REPLACED by a new ``nn.Parameter`` of the same ``_version`` --
+    the version alone does not identify a tensor."""
+    cpu = torch.device("cpu")
+    m = du.module(**du.SMALL)
+    first = m._prepare(cpu)
+    assert m._prepare(cpu) is first
+    attn = m.layers[0].cross_attn.attn
+    old = attn.in_proj_weight
+    new = torch.nn.Parameter(old.detach().clone() * 2)
+    with torch.no_grad():
+        while new._version < old._version:
+            new.add_(0.0)
+    assert new._version == old._version and new is not old
+    attn.in_proj_weight = new
+    second = m._prepare(cpu)
+    assert second is not first and m._prepare(cpu) is second
+    assert torch.equal(second["layers"][0]["cross_attn"]["w"], new.detach())
+    assert torch.equal(second["groups"][0]["cross_attn"][0][:64], new.detach()[64:128])          # the hoisted [K_0 K_1 | V_0 V_1]
+    assert torch.equal(first["groups"][0]["cross_attn"][0][:64], old.detach()[64:128])
+    last = second
+    changes = (lambda: new.mul_(0.5), lambda: m.cross_posembed.position_embedding_head[1].running_var.mul_(1.5),
+               lambda: m.load_state_dict(du.module(**du.SMALL, seed=5).state_dict()))
+    for change in changes:
+        with torch.no_grad():
+            change()
+        again = m._prepare(cpu)
+        assert again is not last and m._prepare(cpu) is again
+        last = again
+    assert torch.equal(last["layers"][0]["cross_attn"]["w"], du.module(**du.SMALL, seed=5).layers[0].cross_attn.attn.in_proj_weight.detach())
+
+
 # ------------------------------------------------------------------------------------------------------------------ the ABI
 def test_header_binding_and_exports_declare_the_entry_points():
     lib = _abi.lib()

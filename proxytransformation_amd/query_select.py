@@ -131,9 +131,9 @@ def topk_sorted(scores: torch.Tensor, rows: Sequence[int], k: int, return_invers
         raise RuntimeError("topk_sorted (HIP) needs GPU tensors: there is no CPU path")
     dev = scores.device
     scores = _f32(scores, "topk_sorted", dev)
-    B, Lmax, k = int(scores.shape[0]), int(scores.shape[1]), int(k)
-    if scores.dim() != 2 or len(rows) != B or not 1 <= B <= MAX_SCENES:
+    if scores.dim() != 2 or len(rows) != scores.shape[0] or not 1 <= scores.shape[0] <= MAX_SCENES:
         raise ValueError(f"topk_sorted: scores (B,Lmax) of 1 to {MAX_SCENES} scenes with one row count each, got {tuple(scores.shape)}, {len(rows)}")
+    B, Lmax, k = int(scores.shape[0]), int(scores.shape[1]), int(k)
     if not 1 <= k <= MAX_QUERIES or k > min(int(r) for r in rows):
         raise ValueError(f"topk_sorted: k={k} must be 1 to {MAX_QUERIES} and at most the smallest scene's {min(int(r) for r in rows)} rows")
     index = torch.empty((B, k), dtype=torch.int64, device=dev)
@@ -178,6 +178,8 @@ def decode(h: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch
     dev = feats.device
     h, weight, bias = _f32(h, "decode", dev), _f32(weight, "decode", dev), _f32(bias, "decode", dev)
     feats, coords = _f32(feats, "decode", dev), _f32(coords, "decode", dev)
+    if feats.dim() != 3:
+        raise ValueError(f"decode: feats (B,Lmax,C) expected, got {tuple(feats.shape)}")
     B, Lmax, C = (int(v) for v in feats.shape)
     _width("decode", C)
     if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != B or not index.is_contiguous():

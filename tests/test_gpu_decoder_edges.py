@@ -31,6 +31,7 @@ from torch import nn
 from proxytransformation_amd import decoder, decoder_host as dh, query_select_host as qh
 from tests import decoder_util as du
 from tests import sparse_util as su
+from tests.sparse_util import hold_pooled
 from tests.test_gpu_decoder import _attn_refs, _hold_finite, _hold_layers, _ln_params, bits_equal, dev, f64, host, ints
 
 pytestmark = pytest.mark.gpu
@@ -47,22 +48,6 @@ def both(fn, *arrays, **kw):
     r32 = fn(*arrays, **kw)
     assert (r32[0] if isinstance(r32, tuple) else r32).dtype == np.float32
     return r32, fn(*[f64(a) if a is not None and a.dtype == np.float32 else a for a in arrays], **kw)
-
-
-MIN_SAMPLE = 64
-
-
-def hold_pooled(name, size, draw, call, refs, rule=su.hold):
-    """``hold`` compares two maxima, and a maximum over a handful of values is no yardstick: the fp32 host's only value can be exact by
-    luck while the device's is one ulp off (seen at K = T = 1: 9.5e-9 against 1.2e-7, one value).  So a call with fewer than 64 results
-    (``size``) is repeated on fresh draws of the SAME shape until 64 are pooled, and the rule is applied to the pool.  Returns the first
-    draw and its device result."""
-    parts = []
-    for _ in range(max(1, -(-MIN_SAMPLE // max(size, 1)))):
-        ops = draw()
-        parts.append((ops, call(*ops)) + tuple(refs(*ops)))
-    rule(name, *(np.concatenate([p[i].ravel() for p in parts]) for i in (1, 2, 3)))
-    return parts[0][0], parts[0][1]
 
 
 def same_rows_but(a, b, row):

@@ -135,6 +135,38 @@ def test_sorted_topk_rule():
         qh.topk_sorted_host(s, [3], 4)
 
 
+def test_sorted_topk_rule_where_a_scene_has_no_order_and_where_it_takes_every_row():
+    """What tests/test_gpu_query_select_edges.py relies on.  A scene of one value, all ``-inf`` or all NaN of one sign is one tie: the rows
+    0 .. k - 1 in order (the stated rule; torch leaves ties open).  k = rows on tie-free scores: ``torch.topk``'s permutation."""
+    pos, neg = qu.nan_signs()
+    for value in (np.float32(0.5), np.float32(-np.inf), pos, neg, np.float32(-0.0)):
+        s = np.full((1, 9), np.inf, np.float32)
+        s[0, :7] = value
+        for k in (1, 5, 7):
+            assert qh.topk_sorted_host(s, [7], k).tolist() == [list(range(k))]
+    s = np.random.default_rng(8).standard_normal((2, 300)).astype(np.float32)
+    got = qh.topk_sorted_host(s, [300, 300], 300)
+    assert np.array_equal(got, torch.topk(torch.from_numpy(s), 300, dim=1)[1].numpy()) and sorted(got[1].tolist()) == list(range(300))
+    mixed = np.array([[neg, 1.0, pos, -np.inf, pos, np.inf]], np.float32)          # +NaN above +inf, -NaN below -inf, equal NaNs by row
+    mixed[0, [0, 2, 4]] = neg, pos, pos
+    assert qh.topk_sorted_host(mixed, [6], 6).tolist() == [[2, 4, 5, 1, 3, 0]]
+
+
+def test_score_with_a_leading_tile_of_masked_tokens_is_the_torch_stage():
+    """T = 70 with the first 64 tokens masked in scene 0, only the last token in scene 1, only token 40 in scene 2: the maximum starts
+    behind a whole 64-token tile."""
+    feats, xyz, text, mask = qu.inputs((90, 41, 130), 70, 64, seed=9)
+    mask[:] = False
+    mask[0, 64:], mask[1, 69], mask[2, 40] = True, True, True
+    m = qu.module(C=64, num_queries=40)
+    keep = {}
+    m.forward_host(feats, None, xyz, text, mask, np.float64, keep_out=keep)
+    ref = torch_stage(m, feats, xyz, text, mask, torch.float64)
+    _close(keep["score"], ref["score"])
+    assert np.isfinite(keep["score"][0, :90]).all() and np.isneginf(keep["score"][0, 90:]).all()
+    assert np.array_equal(keep["index"], ref["index"].numpy())
+
+
 def test_backward_restatement_is_autograd_in_float64():
     rng = np.random.default_rng(6)
     rows, C, K = (9, 4, 12), 5, 4

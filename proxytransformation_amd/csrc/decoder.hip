@@ -12,32 +12,21 @@
 //       never read (predicated loads), a key tile that is masked throughout is skipped, a query without a key gets zeros.
 //   ptx_dec_ln         LayerNorm over rows of width C: the mean first, then the centred sum of squares; optionally a second LayerNorm of
 //       the first one's result (the decoder's `norm` behind `norms[3]`), both written.
-//   ptx_dec_boxes      the last Linear (C -> 9) of a regression branch and the baseline box decode against the query coordinates.
+//   ptx_dec_boxes      the last Linear (C -> 9) of a regression branch and the baseline box decode against the query coordinates:
+//       k_head_boxes<false> (head.h).
 //   ptx_dec_scores     ContrastiveEmbed in full: (NL,B,K,max_text_len) with -inf on masked tokens and behind T.
+//
+// posembed, linear and scores are instantiations of head.h's tile64_nt, accumulating straight through (the query selection's launches
+// add per 64-wide block: both orders are recorded behaviour); the Linear epilogue, ContrastiveEmbed's value rule and the 16-lane row sums
+// are head.h's too.
 //
 // fp32, no float atomics, fixed summation orders (bitwise reproducible), everything on the caller's stream, no host wait.  Held to the
 // numpy restatements of proxytransformation_amd/decoder_host.py.
-#include "sparse.h"
-#include "train_rules.h"
+#include "head.h"
 
 namespace ptx {
 
-constexpr int kDecMaxScenes = 64, kDecMaxK = 1024, kDecMaxText = 256, kDecReg = 9;
 constexpr int kDecMaxCin = 2048, kDecMaxCout = 4096, kDecMaxPos = 9;
-
-// one 32-wide k step of a wave's 32 x 32 accumulator: A[buf][arow][k], W[buf][wrow][k] (mfma64.h's fragment order)
-__device__ __forceinline__ void dec_step(const float (*A)[64][LDT], const float (*W)[64][LDT], int buf, int arow, int wrow, int hh, f32x16 &acc)
-{
-#pragma unroll
-    for (int kk = 0; kk < BK / 8; ++kk) {
-        const float4 a4 = *reinterpret_cast<const float4 *>(&A[buf][arow][kk * 8 + hh * 4]);
-        const float4 b4 = *reinterpret_cast<const float4 *>(&W[buf][wrow][kk * 8 + hh * 4]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-    }
-}
 
 // ---- the 64 x 64 NT tile: linear, posembed, scores ------------------------------------------------------------------------------------
 enum { DEC_LINEAR = 0, DEC_POSEMBED = 1, DEC_SCORES = 2 };
@@ -59,11 +48,9 @@ struct DecGemmArgs {
 template <int MODE>
 __global__ __launch_bounds__(256) void k_dec_gemm(DecGemmArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float As[2][64][LDT];
-    __shared__ __attribute__((aligned(16))) float Ws[2][64][LDT];
     __shared__ float s_x[MODE == DEC_POSEMBED ? 64 : 1][kDecMaxPos + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wr = wid >> 1, wc = wid & 1, li = lane & 31, hh = lane >> 5;
+    const Tile64 t;
+    const int tid = t.tid;
     const int row0 = blockIdx.x * 64, col0 = blockIdx.y * 64;
     const int z = MODE == DEC_SCORES ? blockIdx.z : 0;
     const int nrows = MODE == DEC_SCORES ? a.K : a.n;
@@ -85,19 +72,16 @@ __global__ __launch_bounds__(256) void k_dec_gemm(DecGemmArgs a)
         }
         __syncthreads();
     }
-    const int nsteps = a.Cin >> 6;
-    const int ar = tid >> 4, kq = (tid & 15) * 4;          // staging: thread (ar + 16 i, kq .. kq + 3), 16 lanes = one 256-B row piece
-    float4 av[4], wv[4];
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
 
-    auto fetch = [&](int s) {
-        const int c0 = s << 6;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = ar + 16 * i, grow = row0 + row;
-            if (MODE == DEC_POSEMBED) {
+    tile64_nt<false>(
+        t, a.Cin >> 6, acc,
+        [](int s) { return s << 6; },                       // the first channel of step s
+        [&](float4 &v, int c0, int row, int kq) {
+            const int grow = row0 + row;
+            if (MODE == DEC_POSEMBED) {                     // the first layer's 4 hidden channels of this row, cin0 products each
                 float h[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -106,58 +90,32 @@ __global__ __launch_bounds__(256) void k_dec_gemm(DecGemmArgs a)
                     for (int j = 0; j < a.cin0; ++j) v = v + s_x[row][j] * a.w1[k * a.cin0 + j];
                     h[q] = relu_nan(v + a.b1[k]);
                 }
-                av[i] = make_float4(h[0], h[1], h[2], h[3]);
+                v = make_float4(h[0], h[1], h[2], h[3]);
             } else {
-                av[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (grow < nrows) {
-                    av[i] = ld4(a.x + (rbase + grow) * a.Cin + c0 + kq);
-                    if (use_add) av[i] = add4(av[i], ld4(a.add + (size_t)grow * a.Cin + c0 + kq));
+                    v = ld4(a.x + (rbase + grow) * a.Cin + c0 + kq);
+                    if (use_add) v = add4(v, ld4(a.add + (size_t)grow * a.Cin + c0 + kq));
                 }
             }
-            wv[i] = col0 + row < ncols ? ld4(wbase + (size_t)(col0 + row) * a.Cin + c0 + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-
-    fetch(0);
-    for (int s = 0; s < nsteps; ++s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            st4(&As[kq >> 5][ar + 16 * i][kq & 31], av[i]);
-            st4(&Ws[kq >> 5][ar + 16 * i][kq & 31], wv[i]);
-        }
-        __syncthreads();
-        if (s + 1 < nsteps) fetch(s + 1);                   // in flight behind this step's matrix instructions
-        dec_step(As, Ws, 0, wr * 32 + li, wc * 32 + li, hh, acc);
-        dec_step(As, Ws, 1, wr * 32 + li, wc * 32 + li, hh, acc);
-        __syncthreads();
-    }
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const int n = col0 + wc * 32 + li;
+        },
+        [&](float4 &v, int c0, int row, int kq) {
+            v = col0 + row < ncols ? ld4(wbase + (size_t)(col0 + row) * a.Cin + c0 + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
+        },
+        [](int) {});
+    const int n = col0 + t.col();
     if (MODE == DEC_SCORES) {
         if (n >= a.ldo) return;
         const bool valid = n < a.T && a.mask[(size_t)(z % a.B) * a.T + n] != 0;
         const float bias = a.bias ? a.bias[0] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            float v = acc[r];
-            if (a.scaled) v = v / a.divisor;
-            if (a.bias) v = v + bias;
-            if (row < nrows) a.out[(rbase + row) * a.ldo + n] = valid ? v : -INFINITY;
+            const int row = row0 + t.row(r);
+            if (row < nrows) a.out[(rbase + row) * a.ldo + n] = contrastive_value(acc[r], valid, a.scaled, a.divisor, a.bias != nullptr, bias);
         }
         return;
     }
-    const float bias = a.bias ? a.bias[n] : 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = row0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        if (row >= nrows) continue;
-        float v = acc[r];
-        if (a.bias) v = v + bias;
-        if (a.relu) v = relu_nan(v);
-        if (a.residual) v = v + a.residual[(size_t)row * a.Cout + n];
-        a.out[(size_t)row * a.Cout + n] = v;
-    }
+    linear_store(t, acc, row0, nrows, n, a.Cout, a.bias, a.relu, a.residual, a.out);
 }
 
 // ---- attention ------------------------------------------------------------------------------------------------------------------------
@@ -241,9 +199,9 @@ __global__ __launch_bounds__(256) void k_dec_attn(DecAttnArgs a)
 #pragma unroll
             for (int i = 0; i < 16; ++i) s[i] = 0.0f;
 #pragma unroll
-            for (int h2 = 0; h2 < NB; ++h2) dec_step(Qs, Ks, h2, wr * 32 + li, wc * 32 + li, hh, s);
+            for (int h2 = 0; h2 < NB; ++h2) g64_step(Qs, Ks, h2, wr * 32 + li, wc * 32 + li, hh, s);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) Ps[wc][wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh][li] = s[r];
+            for (int r = 0; r < 16; ++r) Ps[wc][tile_row(r, wr, hh)][li] = s[r];
         }
         __syncthreads();
         {
@@ -298,21 +256,21 @@ __global__ __launch_bounds__(256) void k_dec_attn(DecAttnArgs a)
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[r] = o[r] * s_alpha[wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh] + pv[r];
+            for (int r = 0; r < 16; ++r) o[r] = o[r] * s_alpha[tile_row(r, wr, hh)] + pv[r];
         }
         __syncthreads();
     }
     if (qd == 0) s_l[srow] = l_run;
     if (HD == 32 && wc == 1) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) Ps[0][wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh][li] = o[r];
+        for (int r = 0; r < 16; ++r) Ps[0][tile_row(r, wr, hh)][li] = o[r];
     }
     __syncthreads();
     if (HD == 32 && wc == 1) return;
     const int col = (HD == 64 ? wc * 32 : 0) + li;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int row = tile_row(r, wr, hh);
         float v = o[r];
         if (HD == 32) v = v + Ps[0][row][li];
         const float l = s_l[row];
@@ -329,16 +287,15 @@ struct DecLnArgs {
     float eps;
 };
 
-// 16 lanes hold a row: lane l the channels 64 m + 4 l .. + 3.  mean = (sum in ascending channel order per lane, lanes by xor 8, 4, 2, 1)
-// / C, then the centred squares the same way: never E[x^2] - E[x]^2.
+// 16 lanes hold a row (head.h's layout).  mean = (sum in ascending channel order per lane, then sum16) / C, then the centred squares the
+// same way: never E[x^2] - E[x]^2.
 __device__ __forceinline__ void dec_ln_row(float4 (&x)[8], int nm, int C, float eps, const float *w, const float *b, int l)
 {
     float s = 0.0f;
 #pragma unroll
     for (int m = 0; m < 8; ++m)
         if (m < nm) { s = s + x[m].x; s = s + x[m].y; s = s + x[m].z; s = s + x[m].w; }
-    s = s + __shfl_xor(s, 8, 16); s = s + __shfl_xor(s, 4, 16); s = s + __shfl_xor(s, 2, 16); s = s + __shfl_xor(s, 1, 16);
-    const float mean = s / (float)C;
+    const float mean = sum16(s) / (float)C;
     float ss = 0.0f;
 #pragma unroll
     for (int m = 0; m < 8; ++m)
@@ -346,8 +303,7 @@ __device__ __forceinline__ void dec_ln_row(float4 (&x)[8], int nm, int C, float 
             x[m].x = x[m].x - mean; x[m].y = x[m].y - mean; x[m].z = x[m].z - mean; x[m].w = x[m].w - mean;
             ss = ss + x[m].x * x[m].x; ss = ss + x[m].y * x[m].y; ss = ss + x[m].z * x[m].z; ss = ss + x[m].w * x[m].w;
         }
-    ss = ss + __shfl_xor(ss, 8, 16); ss = ss + __shfl_xor(ss, 4, 16); ss = ss + __shfl_xor(ss, 2, 16); ss = ss + __shfl_xor(ss, 1, 16);
-    const float den = sqrtf(ss / (float)C + eps);
+    const float den = sqrtf(sum16(ss) / (float)C + eps);
 #pragma unroll
     for (int m = 0; m < 8; ++m)
         if (m < nm) {
@@ -376,47 +332,6 @@ __global__ __launch_bounds__(256) void k_dec_ln(DecLnArgs a)
 #pragma unroll
     for (int m = 0; m < 8; ++m)
         if (m < nm && have) st4(a.out2 + (size_t)row * a.C + 64 * m + 4 * l, x[m]);
-}
-
-// ---- boxes ----------------------------------------------------------------------------------------------------------------------------
-// k_qs_decode's arithmetic without its gathers: 16 rows x 16 lanes, lane l < 9 finishes box value l.
-struct DecBoxArgs {
-    const float *h, *weight, *bias, *coords;                // (n,C), (9,C), (9) or null, (n,3)
-    float *boxes;                                           // (n,9)
-    int n, C;
-};
-
-__global__ __launch_bounds__(256) void k_dec_boxes(DecBoxArgs a)
-{
-    __shared__ __attribute__((aligned(16))) float s_w[kDecReg * 512];
-    for (int e = threadIdx.x; e < kDecReg * a.C; e += 256) s_w[e] = a.weight[e];
-    __syncthreads();
-    const int l = threadIdx.x & 15;
-    const long row = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int nm = a.C >> 6;
-    const bool have = row < a.n;
-    float4 x[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-        x[m] = (m < nm && have) ? ld4(a.h + (size_t)row * a.C + 64 * m + 4 * l) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float mine = 0.0f;
-    for (int k = 0; k < kDecReg; ++k) {
-        float s = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            if (m < nm) {
-                const float4 w = ld4(&s_w[k * a.C + 64 * m + 4 * l]);
-                s = s + x[m].x * w.x; s = s + x[m].y * w.y; s = s + x[m].z * w.z; s = s + x[m].w * w.w;
-            }
-        }
-        s = s + __shfl_xor(s, 8, 16); s = s + __shfl_xor(s, 4, 16); s = s + __shfl_xor(s, 2, 16); s = s + __shfl_xor(s, 1, 16);
-        if (a.bias) s = s + a.bias[k];
-        if (k == l) mine = s;
-    }
-    if (!have || l >= kDecReg) return;
-    if (l < 3) mine = mine + a.coords[(size_t)row * 3 + l];
-    else if (l < 6) mine = max_nan(expf(mine), 0.02f);
-    a.boxes[(size_t)row * kDecReg + l] = mine;
 }
 
 static int dec_rows_ok(const char *who, long n)
@@ -470,7 +385,7 @@ int ptx_dec_attention(const float *q, long ldq, const float *k, long ldk, const 
                       int H, int hd, float *out, void *stream)
 {
     const char *who = "ptx_dec_attention";
-    PTX_REQUIRE(B >= 1 && B <= kDecMaxScenes && Kq >= 1 && Kq <= kDecMaxK && L >= 1 && L <= (1 << 24),
+    PTX_REQUIRE(B >= 1 && B <= kHeadMaxScenes && Kq >= 1 && Kq <= kHeadMaxK && L >= 1 && L <= (1 << 24),
                 "%s: B=%d Kq=%d L=%d (B: 1 to 64; Kq: 1 to 1024; L: 1 to 2^24)", who, B, Kq, L);
     PTX_REQUIRE((hd == 32 || hd == 64) && H >= 1 && H * hd <= 512, "%s: H=%d hd=%d (hd: 32 or 64; H hd up to 512)", who, H, hd);
     const long C = (long)H * hd;
@@ -512,9 +427,9 @@ int ptx_dec_boxes(const float *h, const float *weight, const float *bias, int C,
     PTX_REQUIRE(sp_width_ok(C), "%s: C=%d (a multiple of 64 up to 512)", who, C);
     PTX_REQUIRE(h && weight && coords && boxes, "%s: null argument", who);
     PTX_REQUIRE(sp_aligned16({h}), "%s: h must be 16-byte aligned", who);
-    const DecBoxArgs a{h, weight, bias, coords, boxes, (int)n, C};
-    hipLaunchKernelGGL(k_dec_boxes, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    PTX_LAUNCHED("k_dec_boxes");
+    const HeadBoxArgs a{h, weight, bias, nullptr, coords, nullptr, nullptr, nullptr, boxes, (int)n, 0, 0, C};
+    hipLaunchKernelGGL((k_head_boxes<false>), dim3((unsigned)((n + 15) / 16)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    PTX_LAUNCHED("k_head_boxes");
     return PTX_OK;
 }
 
@@ -522,10 +437,10 @@ int ptx_dec_scores(const float *hidden, int NL, int B, int K, int C, const float
                    int scaled, const float *bias, float *out, void *stream)
 {
     const char *who = "ptx_dec_scores";
-    PTX_REQUIRE(NL >= 1 && NL <= 64 && B >= 1 && B <= kDecMaxScenes && K >= 1 && K <= kDecMaxK && sp_width_ok(C),
+    PTX_REQUIRE(NL >= 1 && NL <= 64 && B >= 1 && B <= kHeadMaxScenes && K >= 1 && K <= kHeadMaxK && sp_width_ok(C),
                 "%s: NL=%d B=%d K=%d C=%d (NL, B: 1 to 64; K: 1 to 1024; C: a multiple of 64 up to 512)", who, NL, B, K, C);
-    PTX_REQUIRE(T >= 1 && T <= max_text_len && max_text_len <= kDecMaxText && (scaled == 0 || scaled == 1),
-                "%s: T=%d max_text_len=%d scaled=%d (1 <= T <= max_text_len <= %d; scaled: 0 or 1)", who, T, max_text_len, scaled, kDecMaxText);
+    PTX_REQUIRE(T >= 1 && T <= max_text_len && max_text_len <= kHeadMaxText && (scaled == 0 || scaled == 1),
+                "%s: T=%d max_text_len=%d scaled=%d (1 <= T <= max_text_len <= %d; scaled: 0 or 1)", who, T, max_text_len, scaled, kHeadMaxText);
     PTX_REQUIRE(hidden && text && text_mask && out, "%s: null argument", who);
     PTX_REQUIRE(sp_aligned16({hidden, text}), "%s: hidden and text must be 16-byte aligned", who);
     DecGemmArgs a{};

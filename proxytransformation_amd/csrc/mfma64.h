@@ -8,10 +8,25 @@ namespace ptx {
 
 constexpr int BK = 32, LDT = BK + 4;   // 144-B LDS rows: 16-B aligned, b128 fragment reads conflict-free
 
+// one BK-wide step of a wave's 32 x 32 accumulator from LDS buffer `buf`: A[buf][arow][k], W[buf][wrow][k], hh = lane >> 5.
+// C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) (head.h: tile_row)
+__device__ __forceinline__ void g64_step(const float (*A)[64][LDT], const float (*W)[64][LDT], int buf, int arow, int wrow, int hh, f32x16 &acc)
+{
+#pragma unroll
+    for (int kk = 0; kk < BK / 8; ++kk) {
+        const float4 a4 = *reinterpret_cast<const float4 *>(&A[buf][arow][kk * 8 + hh * 4]);
+        const float4 b4 = *reinterpret_cast<const float4 *>(&W[buf][wrow][kk * 8 + hh * 4]);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
+    }
+}
+
 }  // namespace ptx
 
-// one BK-wide step from LDS buffer buf_ into `acc`; needs As, Ws, wr, wc, li = lane & 31, hh = lane >> 5 in scope.
-// C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+// The same step as a macro over As, Ws, acc, wr, wc, li, hh in scope, for gemm.hip, sparse.hip and sparse_bwd.hip: expressed through
+// g64_step, k_sparse_conv and k_sparse_dweight compile to other instructions (profiles/head_refactor.txt), so the macro stays.
 #define PTX_G64_COMPUTE(buf_)                                                              \
     do {                                                                                   \
         _Pragma("unroll") for (int kk = 0; kk < BK / 8; ++kk) {                            \

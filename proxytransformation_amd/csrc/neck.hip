@@ -13,16 +13,16 @@
 //       (m,1) score at the finer level's coordinates: the same table over the score rows, one thread per query, eight probes, the
 //       present corners added in ascending corner index.
 //   ptx_neck_topk_prune     the per-scene top-k of mink_neck.py:178-185 and MinkowskiPruning: one work-group per scene runs a radix
-//       select (4 passes of 8 bits over an order-preserving integer key, LDS histograms of integer counts) for the k-th largest score,
+//       select (head.h's topk_threshold over its order-preserving integer key topk_key) for the k-th largest score,
 //       then ranks the kept rows in their order: everything above the threshold, and of the rows AT the threshold the first few by row
 //       index.  k_prune_copy moves coordinates and features to their ranks.  The new scene ends are min(rows, k) accumulated: host knowledge.
 //   ptx_neck_head           conv_cls (kernel 1, with bias) and the prune score max over the classes in one kernel: 16 lanes per row, each
-//       with a fixed share of the channels, combined by a fixed shuffle tree.
+//       with a fixed share of the channels, combined by a fixed shuffle tree (head.h's row_dot16).
 //
 // fp32, no float atomics, fixed summation orders (bitwise reproducible), everything ordered on the caller's stream; the host waits only
 // for the union's row counts.  Held to the numpy restatements of proxytransformation_amd/neck_host.py.
 #include "voxel.h"
-#include "sparse.h"
+#include "head.h"
 
 namespace ptx {
 
@@ -188,15 +188,6 @@ __global__ __launch_bounds__(256) void k_prune_scores(ScoreArgs a)
 }
 
 // ---- top-k prune --------------------------------------------------------------------------------------------------------------
-// the order of the scores as unsigned integers: larger score, larger key; -0.0 and +0.0 share one.  A NaN orders by its bits: above +inf
-// with the sign bit clear, below -inf with it set (neck_host.topk_key restates it)
-__device__ __forceinline__ uint32_t topk_key(float s)
-{
-    uint32_t u = __float_as_uint(s);
-    if ((u << 1) == 0u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 struct TopkArgs {
     const float *scores; int B, k;
     int32_t *dest;                                          // (n): the row's place among the kept rows, or -1
@@ -205,10 +196,7 @@ struct TopkArgs {
 
 __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a)
 {
-    __shared__ int s_hist[256];
-    __shared__ int s_w[4];
-    __shared__ uint32_t s_prefix;
-    __shared__ int s_need;
+    __shared__ TopkLds s_topk;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int lo = b > 0 ? a.in_end[b - 1] : 0, hi = a.in_end[b];
     int out0 = 0;                                           // kept rows of the scenes before
@@ -220,26 +208,8 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a)
         for (int i = lo + tid; i < hi; i += 256) a.dest[i] = out0 + (i - lo);
         return;
     }
-    uint32_t prefix = 0u, known = 0u;                       // the threshold key's bits found so far
-    int need = a.k;                                         // rows still to take among those that match `prefix`
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        s_hist[tid] = 0;
-        __syncthreads();
-        for (int i = lo + tid; i < hi; i += 256) {
-            const uint32_t key = topk_key(a.scores[i]);
-            if ((key & known) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int d = 255, left = need;
-            while (d > 0 && s_hist[d] < left) { left -= s_hist[d]; --d; }
-            s_prefix = prefix | ((uint32_t)d << shift);
-            s_need = left;
-        }
-        __syncthreads();
-        prefix = s_prefix; need = s_need; known |= 255u << shift;
-        __syncthreads();
-    }
+    int need;
+    const uint32_t prefix = topk_threshold(a.scores, lo, hi, a.k, s_topk, need);
     // prefix: the k-th largest key; need >= 1 of the rows that carry it are kept, the lowest row indices first
     int run_eq = 0, run_keep = 0;
     for (int base = lo; base < hi; base += 256) {
@@ -247,10 +217,10 @@ __global__ __launch_bounds__(256) void k_topk_select(TopkArgs a)
         const uint32_t key = i < hi ? topk_key(a.scores[i]) : 0u;
         const bool eq = i < hi && key == prefix;
         int total;
-        const int r_eq = block_rank(eq, s_w, total);
+        const int r_eq = block_rank(eq, s_topk.w, total);
         const bool keep = i < hi && (key > prefix || (eq && run_eq + r_eq < need));
         run_eq += total;
-        const int r_keep = block_rank(keep, s_w, total);
+        const int r_keep = block_rank(keep, s_topk.w, total);
         if (i < hi) a.dest[i] = keep ? out0 + run_keep + r_keep : -1;
         run_keep += total;
     }
@@ -271,8 +241,7 @@ __global__ __launch_bounds__(256) void k_prune_copy(const int32_t *__restrict__ 
 }
 
 // ---- head ---------------------------------------------------------------------------------------------------------------------
-// work-group = 16 rows x 16 lanes; lane l of a row holds channels 4 l + 64 m .. + 3 (m ascending: one 256-B piece of the row per 16
-// lanes and m).  Per class: the lane's products added in ascending channel order, the 16 lanes by xor 8, 4, 2, 1; + bias.
+// work-group = 16 rows x 16 lanes in head.h's row layout.  Per class: row_dot16 + bias.
 // score = max over the classes as neck_host.head_host's cls.max(axis=1) has it: a NaN class score, in whichever class, makes the score
 // NaN (fmaxf alone would drop it and hand the prune a finite score, or -inf, for a row whose features went NaN); the maximum of
 // NaN-free class scores is fmaxf's, bit for bit.
@@ -290,15 +259,7 @@ __global__ __launch_bounds__(256) void k_neck_head(const float *__restrict__ fea
     float best = -INFINITY;
     bool any_nan = false;
     for (int k = 0; k < K; ++k) {
-        float s = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            if (m < nm) {
-                const float4 w = ld4(&s_w[k * C + 64 * m + 4 * l]);
-                s = s + x[m].x * w.x; s = s + x[m].y * w.y; s = s + x[m].z * w.z; s = s + x[m].w * w.w;
-            }
-        }
-        s = s + __shfl_xor(s, 8, 16); s = s + __shfl_xor(s, 4, 16); s = s + __shfl_xor(s, 2, 16); s = s + __shfl_xor(s, 1, 16);
+        float s = row_dot16(x, nm, &s_w[k * C], l);
         if (bias) s = s + bias[k];
         best = fmaxf(best, s);
         any_nan = any_nan || s != s;

@@ -6,33 +6,31 @@
 //       counts travel by value in the kernel-argument struct.
 //   ptx_qs_score    ContrastiveEmbed and its max over the tokens (grounding_head.py:62-99, `enc_outputs_class.max(-1)[0]`): one
 //       work-group per (scene, 64-row tile) multiplies the tile by the scene's text rows on the exact-fp32 matrix instruction, 64 tokens at
-//       a time (the staging and the blocked step of k_sparse_conv), and keeps the running maximum of the unmasked columns in registers:
+//       a time (head.h's tile64_nt in its blocked order), and keeps the running maximum of the unmasked columns in registers:
 //       the (B,L,max_text_len) tensor never exists.  Division by a positive constant and addition of a constant are monotone, so the
 //       maximum is taken of the raw products and scale and bias are applied once; a NaN among the unmasked products makes the score NaN
 //       (torch.max's rule; k_neck_head's flag), padded rows and scenes without a token get -inf.
-//   ptx_qs_topk     torch.topk(score, K, dim=1, sorted=True)[1]: one work-group per scene runs k_topk_select's radix select (neck.hip) for
+//   ptx_qs_topk     torch.topk(score, K, dim=1, sorted=True)[1]: one work-group per scene runs topk_threshold (head.h) for
 //       the K-th key, collects the K kept rows as (key, ~row) pairs in LDS and sorts them (bitonic, at most 1024): descending key, the
 //       lower row first among equal keys (integer LDS counters only; the sort makes the result independent of their order).  Also
 //       writes the inverse index (B,Lmax) of the backward.
-//   ptx_qs_linear   one Linear (+ ReLU) of the regression branch over the K selected rows only: the gather-GEMM of k_sparse_conv's
-//       transposed-weight form (nn.Linear's (out,in) weight has k contiguous already), rows gathered through the index; ReLU keeps a NaN.
-//   ptx_qs_decode   the last Linear (C -> 9), `_bbox_pred_to_bbox` (baseline coder, 9 values) and the gathers of query / query_coords.
+//   ptx_qs_linear   one Linear (+ ReLU) of the regression branch over the K selected rows only: the same tile and order (nn.Linear's
+//       (out,in) weight has k contiguous already), rows gathered through the index; head.h's linear_store, ReLU keeps a NaN.
+//   ptx_qs_decode   the last Linear (C -> 9), `_bbox_pred_to_bbox` (baseline coder, 9 values) and the gathers of query / query_coords:
+//       k_head_boxes<true> (head.h).
 //   ptx_qs_bwd      dfeats_b[r] = dfeats_padded[b,r] (+ dquery[b,q] where index[b,q] = r) through the inverse index: no atomics.
 //
 // fp32, no float atomics, fixed summation orders (bitwise reproducible), everything on the caller's stream, no host wait.  Held to the
 // numpy restatements of proxytransformation_amd/query_select_host.py.
-#include "sparse.h"
-#include "train_rules.h"
+#include "head.h"
 
 namespace ptx {
 
-constexpr int kQsMaxScenes = 64, kQsMaxK = 1024, kQsMaxText = 256, kQsReg = 9;
-
-struct QsRows { int32_t n[kQsMaxScenes]; };
+struct QsRows { int32_t n[kHeadMaxScenes]; };
 
 // ---- pack ---------------------------------------------------------------------------------------------------------------------
 struct QsPackArgs {
-    const float *feats[kQsMaxScenes]; const float *xyz[kQsMaxScenes]; QsRows rows;
+    const float *feats[kHeadMaxScenes]; const float *xyz[kHeadMaxScenes]; QsRows rows;
     const uint8_t *text_mask;                               // (B,T), 1 = a token
     float *out_feats, *out_coords; uint8_t *pad_mask, *text_attn;
     int B, C, Lmax, T;
@@ -77,13 +75,11 @@ struct QsGemmArgs {
 template <bool SCORE>
 __global__ __launch_bounds__(256) void k_qs_gemm(QsGemmArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float As[2][64][LDT];
-    __shared__ __attribute__((aligned(16))) float Ws[2][64][LDT];
     __shared__ int s_src[64];
     __shared__ float s_max[2][64];
     __shared__ int s_nan[2][64];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wr = wid >> 1, wc = wid & 1, li = lane & 31, hh = lane >> 5;
+    const Tile64 t;
+    const int tid = t.tid;
     const int row0 = blockIdx.x * 64;
     const int b = SCORE ? blockIdx.y : 0, col0 = SCORE ? 0 : blockIdx.y * 64;
     const int Lb = SCORE ? a.rows.n[b] : 0;
@@ -111,63 +107,38 @@ __global__ __launch_bounds__(256) void k_qs_gemm(QsGemmArgs a)
     const int ncols = SCORE ? a.T : a.Cout;
     const int nsteps = (SCORE ? (a.T + 63) >> 6 : 1) * nchunk;
     const float *wbase = a.w + (SCORE ? (size_t)b * a.T * a.C : 0);
-    const int ar = tid >> 4, kq = (tid & 15) * 4;          // staging: thread (ar + 16 i, kq .. kq + 3), 16 lanes = one 256-B row piece
-    float4 av[4], wv[4];
-    float tot[16], best[16];
+    f32x16 tot;
+    float best[16];
     int nan = 0;                                            // bit r: a NaN among the unmasked columns of accumulator row r
 #pragma unroll
     for (int i = 0; i < 16; ++i) { tot[i] = 0.0f; best[i] = -INFINITY; }
 
-    auto fetch = [&](int s) {
-        const int c0 = (s % nchunk) << 6, n0 = col0 + ((s / nchunk) << 6);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = ar + 16 * i;
+    tile64_nt<true>(
+        t, nsteps, tot,
+        [&](int s) { return make_int2((s % nchunk) << 6, col0 + ((s / nchunk) << 6)); },       // (first channel, first column) of step s
+        [&](float4 &v, int2 p, int row, int kq) {
             const int src = s_src[row];
-            av[i] = src >= 0 ? ld4(a.x + (size_t)src * a.C + c0 + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
-            wv[i] = n0 + row < ncols ? ld4(wbase + (size_t)(n0 + row) * a.C + c0 + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stash = [&]() {
+            v = src >= 0 ? ld4(a.x + (size_t)src * a.C + p.x + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
+        },
+        [&](float4 &v, int2 p, int row, int kq) {
+            v = p.y + row < ncols ? ld4(wbase + (size_t)(p.y + row) * a.C + p.x + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
+        },
+        [&](int s) {
+            if (SCORE && (s + 1) % nchunk == 0) {           // a token tile is complete: fold its unmasked columns into the running maximum
+                const int tok = ((s / nchunk) << 6) + t.col();
+                const bool valid = tok < a.T && a.text_mask[(size_t)b * a.T + tok] != 0;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            st4(&As[kq >> 5][ar + 16 * i][kq & 31], av[i]);
-            st4(&Ws[kq >> 5][ar + 16 * i][kq & 31], wv[i]);
-        }
-    };
-
-    fetch(0);
-    for (int s = 0; s < nsteps; ++s) {
-        stash();
-        __syncthreads();
-        if (s + 1 < nsteps) fetch(s + 1);                   // in flight behind this step's matrix instructions
-        PTX_SPARSE_STEP(tot, true);
-        __syncthreads();
-        if (SCORE && (s + 1) % nchunk == 0) {               // a token tile is complete: fold its unmasked columns into the running maximum
-            const int tok = ((s / nchunk) << 6) + wc * 32 + li;
-            const bool valid = tok < a.T && a.text_mask[(size_t)b * a.T + tok] != 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                if (valid) {
-                    best[r] = fmaxf(best[r], tot[r]);
-                    nan |= (tot[r] != tot[r]) ? (1 << r) : 0;
+                for (int r = 0; r < 16; ++r) {
+                    if (valid) {
+                        best[r] = fmaxf(best[r], tot[r]);
+                        nan |= (tot[r] != tot[r]) ? (1 << r) : 0;
+                    }
+                    tot[r] = 0.0f;
                 }
-                tot[r] = 0.0f;
             }
-        }
-    }
+        });
     if (!SCORE) {
-        // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-        const int n = col0 + wc * 32 + li;
-        const float bias = a.bias ? a.bias[n] : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            float v = tot[r];
-            if (a.bias) v = v + bias;
-            if (a.relu) v = relu_nan(v);
-            if (row < a.n_out) a.out[(size_t)row * a.Cout + n] = v;
-        }
+        linear_store(t, tot, row0, a.n_out, col0 + t.col(), a.Cout, a.bias, a.relu, nullptr, a.out);
         return;
     }
     // the 32 columns of a wave half by xor 16, 8, 4, 2, 1 (the maximum and the flags are order-free), the two column halves through LDS
@@ -178,54 +149,39 @@ __global__ __launch_bounds__(256) void k_qs_gemm(QsGemmArgs a)
     }
 #pragma unroll
     for (int d = 16; d >= 1; d >>= 1) nan |= __shfl_xor(nan, d, 64);
-    if (li == 0) {
+    if (t.li == 0) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            s_max[wc][row] = best[r];
-            s_nan[wc][row] = (nan >> r) & 1;
+            s_max[t.wc][t.row(r)] = best[r];
+            s_nan[t.wc][t.row(r)] = (nan >> r) & 1;
         }
     }
     __syncthreads();
     if (tid < 64 && row0 + tid < a.Lmax) {
-        float v = fmaxf(s_max[0][tid], s_max[1][tid]);
-        if (a.scaled) v = v / a.divisor;
-        if (a.bias) v = v + a.bias[0];
-        if (s_nan[0][tid] | s_nan[1][tid]) v = __builtin_nanf("");
-        a.out[(size_t)b * a.Lmax + row0 + tid] = row0 + tid < Lb ? v : -INFINITY;
+        const bool valid = row0 + tid < Lb;
+        const float v = contrastive_value(fmaxf(s_max[0][tid], s_max[1][tid]), valid, a.scaled, a.divisor, a.bias != nullptr,
+                                          a.bias ? a.bias[0] : 0.0f);
+        a.out[(size_t)b * a.Lmax + row0 + tid] = valid && (s_nan[0][tid] | s_nan[1][tid]) ? __builtin_nanf("") : v;
     }
 }
 
 // ---- sorted top-k -----------------------------------------------------------------------------------------------------------------
-// neck.hip's order of the scores as unsigned integers (neck_host.topk_key): larger score, larger key; -0.0 and +0.0 share one; a NaN
-// orders by its bits
-__device__ __forceinline__ uint32_t qs_key(float s)
-{
-    uint32_t u = __float_as_uint(s);
-    if ((u << 1) == 0u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 struct QsTopkArgs {
     const float *score; long long *index; int32_t *inv;     // (B,Lmax), (B,K), (B,Lmax) or null
     QsRows rows;
     int B, Lmax, K;
 };
 
-// One work-group per scene.  (1) k_topk_select's radix select (neck.hip: 4 passes of 8 bits, LDS histograms of integer counts) for the
-// K-th largest key; the digit of a pass is found by all 256 threads at once -- thread d owns digit d and takes the count of the larger
-// digits from a suffix scan (shuffles inside a wave, the four wave totals through LDS).  (2) Every thread walks a contiguous run of rows:
+// One work-group per scene.  (1) topk_threshold (head.h) finds the K-th largest key.  (2) Every thread walks a contiguous run of rows:
 // rows above the threshold key take a slot from an integer LDS counter (there are exactly K - need of them; their order in LDS is
 // arbitrary, the sort below puts them in place), rows AT the threshold are counted, a prefix scan over the threads ranks them in row
 // order and the first `need` follow.  (3) The K pairs key << 32 | ~row are distinct: a bitonic sort of the next power of two, descending,
 // gives larger key first and the lower row first among equal keys whatever the order they arrived in.
 __global__ __launch_bounds__(256) void k_qs_topk(QsTopkArgs a)
 {
-    __shared__ int s_hist[256];
-    __shared__ int s_w[4];
-    __shared__ uint32_t s_prefix;
-    __shared__ int s_need, s_cnt;
-    __shared__ unsigned long long s_pair[kQsMaxK];          // key << 32 | ~row: descending = larger key first, lower row first
+    __shared__ TopkLds s_topk;
+    __shared__ int s_cnt;
+    __shared__ unsigned long long s_pair[kHeadMaxK];        // key << 32 | ~row: descending = larger key first, lower row first
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int hi = a.rows.n[b];                             // >= K (the host checks)
     const float *sc = a.score + (size_t)b * a.Lmax;
@@ -235,40 +191,14 @@ __global__ __launch_bounds__(256) void k_qs_topk(QsTopkArgs a)
     while (P < a.K) P <<= 1;
     for (int p = tid; p < P; p += 256) s_pair[p] = 0ull;    // below every real pair (~row > 0)
     if (tid == 0) s_cnt = 0;
-    uint32_t prefix = 0u, known = 0u;                       // the threshold key's bits found so far
-    int need = a.K;                                         // rows still to take among those that match `prefix`
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        s_hist[tid] = 0;
-        __syncthreads();
-        for (int i = tid; i < hi; i += 256) {
-            const uint32_t key = qs_key(sc[i]);
-            if ((key & known) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        const int h = s_hist[tid];
-        int suf = h;                                        // candidates with a digit >= tid inside this wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_down(suf, d, 64);
-            if (lane + d < 64) suf += o;
-        }
-        if (lane == 0) s_w[wid] = suf;
-        __syncthreads();
-        int above = suf - h;                                // candidates with a larger digit
-        for (int w = wid + 1; w < 4; ++w) above += s_w[w];
-        if (above < need && need <= above + h) {            // exactly one digit: the candidates are at least `need`
-            s_prefix = prefix | ((uint32_t)tid << shift);
-            s_need = need - above;
-        }
-        __syncthreads();
-        prefix = s_prefix; need = s_need; known |= 255u << shift;
-    }
+    int need;
+    const uint32_t prefix = topk_threshold(sc, 0, hi, a.K, s_topk, need);
     // prefix: the K-th largest key; K - need rows lie above it, `need` of the rows that carry it follow, the lowest row indices first
     const int per = (hi + 255) >> 8, lo_t = min(tid * per, hi), hi_t = min(lo_t + per, hi);
     const int n_above = a.K - need;
     int eq = 0;
     for (int i = lo_t; i < hi_t; ++i) {
-        const uint32_t key = qs_key(sc[i]);
+        const uint32_t key = topk_key(sc[i]);
         if (key > prefix) {
             const int slot = atomicAdd(&s_cnt, 1);
             if (slot < n_above) s_pair[slot] = ((unsigned long long)key << 32) | (uint32_t)~(uint32_t)i;
@@ -281,14 +211,14 @@ __global__ __launch_bounds__(256) void k_qs_topk(QsTopkArgs a)
         const int o = __shfl_up(inc, d, 64);
         if (lane >= d) inc += o;
     }
-    __syncthreads();                                        // (the last pass's reads of s_w are done)
-    if (lane == 63) s_w[wid] = inc;
+    __syncthreads();                                        // (the last pass's reads of s_topk.w are done)
+    if (lane == 63) s_topk.w[wid] = inc;
     __syncthreads();
     int rank = inc - eq;
-    for (int w = 0; w < wid; ++w) rank += s_w[w];
+    for (int w = 0; w < wid; ++w) rank += s_topk.w[w];
     if (eq > 0 && rank < need) {
         for (int i = lo_t; i < hi_t && rank < need; ++i) {
-            if (qs_key(sc[i]) != prefix) continue;
+            if (topk_key(sc[i]) != prefix) continue;
             s_pair[n_above + rank] = ((unsigned long long)prefix << 32) | (uint32_t)~(uint32_t)i;
             ++rank;
         }
@@ -313,69 +243,11 @@ __global__ __launch_bounds__(256) void k_qs_topk(QsTopkArgs a)
     }
 }
 
-// ---- decode -------------------------------------------------------------------------------------------------------------------
-// work-group = 16 selected rows x 16 lanes; lane l holds channels 4 l + 64 m .. + 3 of the row's hidden vector (k_neck_head's layout and
-// order: the lane's products in ascending channel order, the 16 lanes by xor 8, 4, 2, 1; + bias).  Lane l < 9 finishes box value l:
-// center = p + coords, size = max(expf(p), 0.02) with a NaN kept, euler = p.  The same 16 lanes copy the row's features and coordinates.
-struct QsDecodeArgs {
-    const float *h, *weight, *bias;                         // (B K,C) or null (the gathered features themselves), (9,C), (9)
-    const float *feats, *coords; const long long *index;    // (B,Lmax,C), (B,Lmax,3), (B,K)
-    float *query, *qcoords, *boxes;
-    int B, K, Lmax, C;
-};
-
-__global__ __launch_bounds__(256) void k_qs_decode(QsDecodeArgs a)
-{
-    __shared__ __attribute__((aligned(16))) float s_w[kQsReg * 512];
-    for (int e = threadIdx.x; e < kQsReg * a.C; e += 256) s_w[e] = a.weight[e];
-    __syncthreads();
-    const int l = threadIdx.x & 15, row = blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int n = a.B * a.K, nm = a.C >> 6;
-    long src = -1;
-    if (row < n) {
-        const long long i = a.index[row];
-        if (i >= 0 && i < a.Lmax) src = (long)(row / a.K) * a.Lmax + i;
-    }
-    float4 x[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        x[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (m < nm && src >= 0) {
-            const float4 f = ld4(a.feats + (size_t)src * a.C + 64 * m + 4 * l);
-            st4(a.query + (size_t)row * a.C + 64 * m + 4 * l, f);
-            x[m] = a.h ? ld4(a.h + (size_t)row * a.C + 64 * m + 4 * l) : f;
-        }
-    }
-    float mine = 0.0f;
-    for (int k = 0; k < kQsReg; ++k) {
-        float s = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            if (m < nm) {
-                const float4 w = ld4(&s_w[k * a.C + 64 * m + 4 * l]);
-                s = s + x[m].x * w.x; s = s + x[m].y * w.y; s = s + x[m].z * w.z; s = s + x[m].w * w.w;
-            }
-        }
-        s = s + __shfl_xor(s, 8, 16); s = s + __shfl_xor(s, 4, 16); s = s + __shfl_xor(s, 2, 16); s = s + __shfl_xor(s, 1, 16);
-        if (a.bias) s = s + a.bias[k];
-        if (k == l) mine = s;
-    }
-    if (src < 0 || l >= kQsReg) return;
-    if (l < 3) {
-        const float c = a.coords[(size_t)src * 3 + l];
-        a.qcoords[(size_t)row * 3 + l] = c;
-        mine = mine + c;
-    } else if (l < 6) {
-        mine = max_nan(expf(mine), 0.02f);
-    }
-    a.boxes[(size_t)row * kQsReg + l] = mine;
-}
-
 // ---- backward -------------------------------------------------------------------------------------------------------------------
 struct QsBwdArgs {
     const float *dfeats, *dquery; const int32_t *inv;       // (B,Lmax,C) or null, (B,K,C) or null, (B,Lmax)
     float *out;                                             // (sum of the rows, C): scene b at row start[b]
-    QsRows rows; int32_t start[kQsMaxScenes];
+    QsRows rows; int32_t start[kHeadMaxScenes];
     int B, Lmax, K, C;
 };
 
@@ -395,7 +267,7 @@ __global__ __launch_bounds__(256) void k_qs_bwd(QsBwdArgs a)
 // the shape every entry point shares; the row counts: B ints of 0 .. Lmax
 static int qs_shape(const char *who, int B, int Lmax, int C, const int32_t *rows, QsRows &out, long &total)
 {
-    PTX_REQUIRE(B >= 1 && B <= kQsMaxScenes && Lmax >= 1 && Lmax <= (1 << 24) && sp_width_ok(C),
+    PTX_REQUIRE(B >= 1 && B <= kHeadMaxScenes && Lmax >= 1 && Lmax <= (1 << 24) && sp_width_ok(C),
                 "%s: B=%d Lmax=%d C=%d (B: 1 to 64; Lmax: 1 to 2^24; C: a multiple of 64 up to 512)", who, B, Lmax, C);
     PTX_REQUIRE(rows != nullptr, "%s: rows is null", who);
     total = 0;
@@ -409,7 +281,7 @@ static int qs_shape(const char *who, int B, int Lmax, int C, const int32_t *rows
 
 static int qs_select_shape(const char *who, int B, int K, int Lmax, int C)
 {
-    PTX_REQUIRE(B >= 1 && B <= kQsMaxScenes && K >= 1 && K <= kQsMaxK && Lmax >= K && Lmax <= (1 << 24) && sp_width_ok(C),
+    PTX_REQUIRE(B >= 1 && B <= kHeadMaxScenes && K >= 1 && K <= kHeadMaxK && Lmax >= K && Lmax <= (1 << 24) && sp_width_ok(C),
                 "%s: B=%d K=%d Lmax=%d C=%d (B: 1 to 64; K: 1 to 1024 and at most Lmax; Lmax up to 2^24; C: a multiple of 64 up to 512)", who,
                 B, K, Lmax, C);
     return PTX_OK;
@@ -428,7 +300,7 @@ int ptx_qs_pack(const float *const *feats, const float *const *xyz, const int32_
     QsPackArgs a{};
     long total;
     PTX_TRY(qs_shape(who, B, Lmax, C, rows, a.rows, total));
-    PTX_REQUIRE(T >= 1 && T <= kQsMaxText, "%s: T=%d (1 to %d text tokens)", who, T, kQsMaxText);
+    PTX_REQUIRE(T >= 1 && T <= kHeadMaxText, "%s: T=%d (1 to %d text tokens)", who, T, kHeadMaxText);
     PTX_REQUIRE(feats && xyz && text_mask && out_feats && out_coords && pad_mask && text_attn, "%s: null argument", who);
     for (int b = 0; b < B; ++b) {
         PTX_REQUIRE(rows[b] == 0 || (feats[b] && xyz[b]), "%s: scene %d has %d rows and a null pointer", who, b, rows[b]);
@@ -451,8 +323,8 @@ int ptx_qs_score(const float *feats, const int32_t *rows, int B, int Lmax, int C
     QsGemmArgs a{};
     long total;
     PTX_TRY(qs_shape(who, B, Lmax, C, rows, a.rows, total));
-    PTX_REQUIRE(T >= 1 && T <= kQsMaxText && (scaled == 0 || scaled == 1), "%s: T=%d scaled=%d (1 to %d text tokens; scaled: 0 or 1)", who, T,
-                scaled, kQsMaxText);
+    PTX_REQUIRE(T >= 1 && T <= kHeadMaxText && (scaled == 0 || scaled == 1), "%s: T=%d scaled=%d (1 to %d text tokens; scaled: 0 or 1)", who, T,
+                scaled, kHeadMaxText);
     PTX_REQUIRE(feats && text && text_mask && score, "%s: null argument", who);
     PTX_REQUIRE(sp_aligned16({feats, text}), "%s: feats and text must be 16-byte aligned", who);
     a.x = feats; a.w = text; a.bias = bias; a.out = score; a.text_mask = text_mask;
@@ -502,9 +374,9 @@ int ptx_qs_decode(const float *h, const float *weight, const float *bias, int C,
     PTX_TRY(qs_select_shape(who, B, K, Lmax, C));
     PTX_REQUIRE(weight && feats && coords && index && query && qcoords && boxes, "%s: null argument", who);
     PTX_REQUIRE(sp_aligned16({h, feats, query}), "%s: h, feats and query must be 16-byte aligned", who);
-    const QsDecodeArgs a{h, weight, bias, feats, coords, reinterpret_cast<const long long *>(index), query, qcoords, boxes, B, K, Lmax, C};
-    hipLaunchKernelGGL(k_qs_decode, dim3(cdiv(B * K, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    PTX_LAUNCHED("k_qs_decode");
+    const HeadBoxArgs a{h, weight, bias, feats, coords, reinterpret_cast<const long long *>(index), query, qcoords, boxes, B * K, K, Lmax, C};
+    hipLaunchKernelGGL((k_head_boxes<true>), dim3(cdiv(B * K, 16)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    PTX_LAUNCHED("k_head_boxes");
     return PTX_OK;
 }
 

@@ -29,38 +29,12 @@ from torch import nn
 
 from . import _abi, decoder_host, query_select
 from .query_select import QuerySelect
-from .sparse import _f32, _ptr
+from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _gpu, _mask_bytes, _np, _ptr, _stream, _width
 
 __all__ = ["GroundingDecoder", "attention", "boxes", "contrastive_scores", "layer_norm", "linear", "linear_add_ln", "posembed"]
 
-MAX_SCENES, MAX_QUERIES, MAX_TEXT = 64, 1024, 256
 MAX_CIN, MAX_COUT, MAX_FFN = 2048, 4096, 2048
 LN_EPS = 1e-5
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _gpu(what: str, *tensors) -> None:
-    if not all(t.is_cuda for t in tensors if t is not None):
-        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
-
-
-def _width(what: str, C: int) -> int:
-    C = int(C)
-    if C % 64 or not 64 <= C <= 512:
-        raise ValueError(f"{what}: the feature width must be a multiple of 64 from 64 to 512, got {C}")
-    return C
-
-
-def _bool_bytes(what: str, mask: torch.Tensor, shape) -> torch.Tensor:
-    _gpu(what, mask)
-    if tuple(mask.shape) != tuple(shape):
-        raise ValueError(f"{what}: the mask must be {tuple(shape)}, got {tuple(mask.shape)}")
-    if mask.dtype != torch.bool or not mask.is_contiguous():
-        mask = mask.to(torch.bool).contiguous()
-    return mask
 
 
 # ------------------------------------------------------------------------------------------------------------------ the operators
@@ -170,7 +144,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[
     if not 1 <= B <= MAX_SCENES or not 0 <= Kq <= MAX_QUERIES:
         raise ValueError(f"attention: 1 to {MAX_SCENES} scenes and up to {MAX_QUERIES} queries, got B={B}, Kq={Kq}")
     if mask is not None:
-        mask = _bool_bytes("attention", mask, (B, L))
+        mask = _mask_bytes("attention", "the mask", mask, (B, L))
     out = torch.empty((B, Kq, C), dtype=torch.float32, device=dev)
     if Kq == 0:
         return out
@@ -270,7 +244,7 @@ def contrastive_scores(hidden_states: torch.Tensor, text_feats: torch.Tensor, te
     if not 1 <= T <= M <= MAX_TEXT or not 1 <= B <= MAX_SCENES or not 0 <= K <= MAX_QUERIES or NL > 64:
         raise ValueError(f"contrastive_scores: 1 <= T <= max_text_len <= {MAX_TEXT}, 1 to {MAX_SCENES} scenes, up to {MAX_QUERIES} queries and "
                          f"64 layers, got T={T}, max_text_len={M}, B={B}, K={K}, NL={NL}")
-    mask = _bool_bytes("contrastive_scores", text_token_mask, (B, T))
+    mask = _mask_bytes("contrastive_scores", "the mask", text_token_mask, (B, T))
     out = torch.empty((NL, B, K, M), dtype=torch.float32, device=dev)
     if NL * K:
         _abi.check(_abi.lib().ptx_dec_scores(hs.data_ptr(), NL, B, K, C, text.data_ptr(), mask.data_ptr(), T, M, int(bool(scaled)), _ptr(bias),
@@ -469,8 +443,7 @@ class GroundingDecoder(nn.Module):
                                ("text_attention_mask", text_attention_mask, (B, T))):
             if tuple(t.shape) != shape:
                 raise ValueError(f"GroundingDecoder: {name} {shape} expected, got {tuple(t.shape)}")
-        if not all(t.is_cuda for t in tensors):
-            raise RuntimeError("GroundingDecoder (HIP) needs GPU tensors: there is no CPU path")
+        _gpu("GroundingDecoder", *tensors)
         return B, K, L, T
 
     def forward(self, query, key, value, key_padding_mask, self_attn_mask, cross_attn_mask, query_coords, key_coords, pred_bboxes, text_feats,
@@ -492,7 +465,8 @@ class GroundingDecoder(nn.Module):
         dev, C, NL = query.device, self.embed_dims, self.num_layers
         B, K, T = int(query.shape[0]), int(query.shape[1]), int(text.shape[1])
         prep = self._prepare(dev)
-        pad, tmask = _bool_bytes("GroundingDecoder", pad, tuple(key.shape[:2])), _bool_bytes("GroundingDecoder", tmask, (B, T))
+        pad = _mask_bytes("GroundingDecoder", "the mask", pad, tuple(key.shape[:2]))
+        tmask = _mask_bytes("GroundingDecoder", "the mask", tmask, (B, T))
         text_keys_take_pos = T == K                          # mmcv: key_pos = query_pos when the shapes agree
         key_pos = posembed(kcoords, prep["cross_pos"])
         scene_kv, text_kv = {}, {}
@@ -551,7 +525,7 @@ class GroundingDecoder(nn.Module):
                      dtype=np.float64, **kw):
         """The same chain from ``decoder_host.py`` in numpy ``dtype`` with this module's parameters."""
         dt = np.dtype(dtype)
-        arr = lambda t, d=dt: (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(d)      # noqa: E731
+        arr = lambda t, d=dt: _np(t, d)      # noqa: E731
         branches = self._branches(bbox_head, self.num_layers)
         layer = self.layers[0]
         return decoder_host.forward_host(

@@ -42,13 +42,9 @@ from . import _abi, neck_host, sparse
 from .backbone import SparseLevel
 from .neck_host import ACT_ELU, ACT_NONE
 from .registry import MODELS, REGISTRY_BACKEND
-from .sparse import SparseBatchNorm, SparseConv3d, _channel_vectors, _f32, _f32_grad, _int32_array, _ptr, _train, _workspace
+from .sparse import SparseBatchNorm, SparseConv3d, _channel_vectors, _f32, _f32_grad, _int32_array, _np, _ptr, _stream, _train, _workspace
 
 __all__ = ["GenerativeConvTranspose", "MinkNeck", "conv_transpose_gen", "neck_head", "prune_scores", "rows_gather", "topk_prune", "union_add"]
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _rows(what: str, coords: torch.Tensor, n: int) -> torch.Tensor:
@@ -381,10 +377,6 @@ class _ELU(nn.Module):
 
     def forward(self, x):
         return x
-
-
-def _np(t, dt):
-    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
 
 
 def _fold_host(bn, dt):

@@ -31,36 +31,13 @@ import torch
 from torch import nn
 
 from . import _abi, query_select_host
-from .sparse import _f32, _f32_grad, _int32_array, _ptr, _train
+from .sparse import (MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _index, _int32_array, _mask_bytes, _np, _ptr, _stream, _train,
+                     _width)
 
 __all__ = ["QuerySelect", "decode", "linear", "pack", "score", "select_bwd", "topk_sorted"]
 
-MAX_SCENES, MAX_QUERIES, MAX_TEXT = 64, 1024, 256
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _width(what: str, C: int) -> int:
-    C = int(C)
-    if C % 64 or not 64 <= C <= 512:
-        raise ValueError(f"{what}: the feature width must be a multiple of 64 from 64 to 512, got {C}")
-    return C
-
-
 def _pointers(tensors: Sequence[torch.Tensor]):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() if t.numel() else None for t in tensors])
-
-
-def _mask_bytes(what: str, mask: torch.Tensor, shape) -> torch.Tensor:
-    if not mask.is_cuda:
-        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
-    if tuple(mask.shape) != tuple(shape):
-        raise ValueError(f"{what}: text_token_mask must be {tuple(shape)}, got {tuple(mask.shape)}")
-    if mask.dtype != torch.bool or not mask.is_contiguous():
-        mask = mask.to(torch.bool).contiguous()
-    return mask
 
 
 def pack(feats_list: Sequence[torch.Tensor], xyz_list: Sequence[torch.Tensor], text_token_mask: torch.Tensor):
@@ -70,8 +47,7 @@ def pack(feats_list: Sequence[torch.Tensor], xyz_list: Sequence[torch.Tensor], t
     B = len(feats_list)
     if not 1 <= B <= MAX_SCENES or len(xyz_list) != B:
         raise ValueError(f"pack: 1 to {MAX_SCENES} scenes with one coordinate tensor each, got {B} and {len(xyz_list)}")
-    if not all(t.is_cuda for t in list(feats_list) + list(xyz_list)):
-        raise RuntimeError("pack (HIP) needs GPU tensors: there is no CPU path")
+    _gpu("pack", *feats_list, *xyz_list)
     dev = feats_list[0].device
     feats_list = [_f32(f, "pack", dev) for f in feats_list]
     xyz_list = [_f32(p, "pack", dev) for p in xyz_list]
@@ -84,7 +60,7 @@ def pack(feats_list: Sequence[torch.Tensor], xyz_list: Sequence[torch.Tensor], t
     if Lmax < 1:
         raise ValueError("pack: every scene is empty")
     T = int(text_token_mask.shape[-1])
-    mask = _mask_bytes("pack", text_token_mask, (B, T))
+    mask = _mask_bytes("pack", "text_token_mask", text_token_mask, (B, T))
     if not 1 <= T <= MAX_TEXT:
         raise ValueError(f"pack: 1 to {MAX_TEXT} text tokens, got {T}")
     feats = torch.empty((B, Lmax, C), dtype=torch.float32, device=dev)
@@ -102,8 +78,7 @@ def score(feats: torch.Tensor, rows: Sequence[int], text_feats: torch.Tensor, te
     ``max_t (feats[b,r] . text[b,t]) (/ sqrtf(C)) (+ bias)`` over the unmasked tokens, ``-inf`` on the rows behind ``rows[b]`` and in a
     scene without a token, NaN where an unmasked product is NaN (``query_select_host.score_host``; ``ptx_qs_score``, one launch; the
     ``(B,L,T)`` tensor is never materialised)."""
-    if not (feats.is_cuda and text_feats.is_cuda):
-        raise RuntimeError("score (HIP) needs GPU tensors: there is no CPU path")
+    _gpu("score", feats, text_feats)
     dev = feats.device
     feats, text = _f32(feats, "score", dev), _f32(text_feats, "score", dev)
     if feats.dim() != 3 or text.dim() != 3 or text.shape[0] != feats.shape[0] or text.shape[2] != feats.shape[2]:
@@ -114,7 +89,7 @@ def score(feats: torch.Tensor, rows: Sequence[int], text_feats: torch.Tensor, te
     if not 1 <= T <= MAX_TEXT or not 1 <= B <= MAX_SCENES or len(rows) != B:
         raise ValueError(f"score: 1 to {MAX_TEXT} text tokens and 1 to {MAX_SCENES} scenes with one row count each, got T={T}, B={B}, "
                          f"{len(rows)} row counts")
-    mask = _mask_bytes("score", text_token_mask, (B, T))
+    mask = _mask_bytes("score", "text_token_mask", text_token_mask, (B, T))
     bias = _f32(bias, "score", dev)
     out = torch.empty((B, Lmax), dtype=torch.float32, device=dev)
     _abi.check(_abi.lib().ptx_qs_score(feats.data_ptr(), _int32_array(rows), B, Lmax, C, text.data_ptr(), mask.data_ptr(), T, int(bool(scaled)),
@@ -127,8 +102,7 @@ def topk_sorted(scores: torch.Tensor, rows: Sequence[int], k: int, return_invers
     descending ``neck_host.topk_key`` with the lower row first among equal keys (``query_select_host.topk_sorted_host``, bit for bit;
     ``ptx_qs_topk``, one launch).  ``1 <= k <= 1024`` and ``k <= rows[b]``.  ``return_inverse``: also ``inv (B,Lmax) int32``, the place
     of every selected row, ``-1`` elsewhere."""
-    if not scores.is_cuda:
-        raise RuntimeError("topk_sorted (HIP) needs GPU tensors: there is no CPU path")
+    _gpu("topk_sorted", scores)
     dev = scores.device
     scores = _f32(scores, "topk_sorted", dev)
     if scores.dim() != 2 or len(rows) != scores.shape[0] or not 1 <= scores.shape[0] <= MAX_SCENES:
@@ -147,8 +121,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     """``(B,K,Cout) fp32 = act(rows @ weight.T + bias)``: with ``index (B,K) int64`` the rows are ``x[b, index[b,q]]`` of ``x (B,Lmax,Cin)``
     -- the gather is fused -- else ``x (B,K,Cin)`` itself.  ``weight (Cout,Cin)`` as ``nn.Linear`` holds it; the ReLU keeps a NaN
     (``ptx_qs_linear``, one launch on the exact-fp32 matrix instruction)."""
-    if not x.is_cuda:
-        raise RuntimeError("linear (HIP) needs GPU tensors: there is no CPU path")
+    _gpu("linear", x)
     dev = x.device
     x, weight, bias = _f32(x, "linear", dev), _f32(weight, "linear", dev), _f32(bias, "linear", dev)
     if x.dim() != 3 or weight.dim() != 2 or weight.shape[1] != x.shape[2]:
@@ -156,11 +129,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     B, L, cin = (int(v) for v in x.shape)
     cout = _width("linear", weight.shape[0])
     _width("linear", cin)
-    K = L
-    if index is not None:
-        if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != B or not index.is_contiguous():
-            raise ValueError(f"linear: index must be contiguous int64 (B,K), got {index.dtype} {tuple(index.shape)}")
-        K = int(index.shape[1])
+    K = L if index is None else _index("linear", index, B)
     out = torch.empty((B, K, cout), dtype=torch.float32, device=dev)
     _abi.check(_abi.lib().ptx_qs_linear(x.data_ptr(), B * L, _ptr(index), B, K, L, weight.data_ptr(), _ptr(bias), cin, cout, int(bool(relu)),
                                         out.data_ptr(), _stream(dev)), "ptx_qs_linear")
@@ -173,8 +142,7 @@ def decode(h: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch
     for bit, and the last Linear ``weight (9,C)`` of the regression branch on ``h (B,K,C)`` (``None``: on the gathered rows) decoded by
     the baseline coder -- ``center = p[0:3] + coords``, ``size = max(expf(p[3:6]), 0.02)`` with a NaN kept, ``euler = p[6:9]``
     (``query_select_host.boxes_host``; ``ptx_qs_decode``, one launch)."""
-    if not (feats.is_cuda and coords.is_cuda and index.is_cuda):
-        raise RuntimeError("decode (HIP) needs GPU tensors: there is no CPU path")
+    _gpu("decode", feats, coords, index)
     dev = feats.device
     h, weight, bias = _f32(h, "decode", dev), _f32(weight, "decode", dev), _f32(bias, "decode", dev)
     feats, coords = _f32(feats, "decode", dev), _f32(coords, "decode", dev)
@@ -182,9 +150,7 @@ def decode(h: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch
         raise ValueError(f"decode: feats (B,Lmax,C) expected, got {tuple(feats.shape)}")
     B, Lmax, C = (int(v) for v in feats.shape)
     _width("decode", C)
-    if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != B or not index.is_contiguous():
-        raise ValueError(f"decode: index must be contiguous int64 (B,K), got {index.dtype} {tuple(index.shape)}")
-    K = int(index.shape[1])
+    K = _index("decode", index, B)
     if tuple(weight.shape) != (9, C) or (bias is not None and bias.numel() != 9) or tuple(coords.shape) != (B, Lmax, 3) or \
             (h is not None and tuple(h.shape) != (B, K, C)):
         raise ValueError(f"decode: weight (9,{C}), bias (9), coords ({B},{Lmax},3) and h ({B},{K},{C}) expected, got {tuple(weight.shape)}, "
@@ -274,10 +240,6 @@ class _ClsBranch(nn.Module):
         super().__init__()
         if bias:
             self.bias = nn.Parameter(torch.tensor([-math.log((1 - 0.01) / 0.01)], dtype=torch.float32))
-
-
-def _np(t, dt):
-    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
 
 
 class QuerySelect(nn.Module):
@@ -370,8 +332,7 @@ class QuerySelect(nn.Module):
             raise ValueError(f"QuerySelect: 1 to max_text_len={self.max_text_len} text tokens, got {T}")
         if tuple(text_token_mask.shape) != (B, T):
             raise ValueError(f"QuerySelect: text_token_mask ({B},{T}) expected, got {tuple(text_token_mask.shape)}")
-        if not all(t.is_cuda for t in tensors):
-            raise RuntimeError("QuerySelect (HIP) needs GPU tensors: there is no CPU path")
+        _gpu("QuerySelect", *tensors)
 
     def forward(self, feats_list, scores_list, xyz_list, text_feats, text_token_mask, keep_out: Optional[dict] = None):
         train = _train("QuerySelect", self.differentiable, *[f for f in feats_list if isinstance(f, torch.Tensor)])

@@ -47,6 +47,7 @@ import ctypes
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -181,6 +182,46 @@ def _ptr(t: Optional[torch.Tensor]):
 def _int32_array(values: Sequence[int]):
     """Scene / segment ends as the host array the entry points take."""
     return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
+MAX_SCENES, MAX_QUERIES, MAX_TEXT = 64, 1024, 256     # the limits of the stages behind the neck (csrc/head.h)
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _gpu(what: str, *tensors) -> None:
+    if not all(t.is_cuda for t in tensors if t is not None):
+        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
+
+
+def _width(what: str, C: int) -> int:
+    C = int(C)
+    if C % 64 or not 64 <= C <= 512:
+        raise ValueError(f"{what}: the feature width must be a multiple of 64 from 64 to 512, got {C}")
+    return C
+
+
+def _mask_bytes(what: str, name: str, mask: torch.Tensor, shape) -> torch.Tensor:
+    """``mask`` (the operand ``name`` of ``what``) as the contiguous bool tensor of ``shape`` the entry points read as bytes."""
+    _gpu(what, mask)
+    if tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {tuple(mask.shape)}")
+    if mask.dtype != torch.bool or not mask.is_contiguous():
+        mask = mask.to(torch.bool).contiguous()
+    return mask
+
+
+def _index(what: str, index: torch.Tensor, B: int) -> int:
+    """``K`` of a selection ``index (B,K)``: contiguous int64, as the entry points read it."""
+    if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != B or not index.is_contiguous():
+        raise ValueError(f"{what}: index must be contiguous int64 (B,K), got {index.dtype} {tuple(index.shape)}")
+    return int(index.shape[1])
+
+
+def _np(t, dt):
+    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
 
 
 def _wants_grad(*tensors) -> bool:

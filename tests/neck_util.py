@@ -206,7 +206,7 @@ def e2e_neck_b(seed=22):
 
 # ------------------------------------------------------------------------------------------------------------------ top-k
 def radix_trace(scores, lo, hi, k):
-    """The four 8-bit passes of k_topk_select over ``topk_key(scores[lo:hi])`` restated: per pass (shift 24, 16, 8, 0)
+    """The four 8-bit passes of topk_threshold (csrc/head.h) over ``topk_key(scores[lo:hi])`` restated: per pass (shift 24, 16, 8, 0)
     ``(occupied digits among the candidates, need behind the pass)``; then the threshold key.  ``need``: rows still to take among those
     that match the prefix."""
     key = neck_host.topk_key(np.asarray(scores, np.float32)[lo:hi]).astype(np.uint64)

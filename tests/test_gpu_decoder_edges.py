@@ -36,7 +36,7 @@ from tests.test_gpu_decoder import _attn_refs, _hold_finite, _hold_layers, _ln_p
 
 pytestmark = pytest.mark.gpu
 DEV = su.DEV
-EDGE_ROWS = (1, 15, 16, 17, 257)                             # k_dec_ln and k_dec_boxes: 16 rows per work-group
+EDGE_ROWS = (1, 15, 16, 17, 257)                             # k_dec_ln and k_head_boxes: 16 rows per work-group
 
 
 def normal(rng, *shape):

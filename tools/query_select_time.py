@@ -158,7 +158,7 @@ def main():
                  ("top-k (k_qs_topk)", lambda: qs.topk_sorted(score, ROWS, K, return_inverse=True)),
                  ("linear 0, gathered (k_qs_gemm<linear>)", lambda: qs.linear(pf, lins[0].weight, lins[0].bias, index)),
                  ("linear 1 (k_qs_gemm<linear>)", lambda: qs.linear(h1, lins[1].weight, lins[1].bias)),
-                 ("decode (k_qs_decode)", lambda: qs.decode(h2, lins[2].weight, lins[2].bias, pf, pc, index)),
+                 ("decode (k_head_boxes<gather>)", lambda: qs.decode(h2, lins[2].weight, lins[2].bias, pf, pc, index)),
                  ("backward (k_qs_bwd)", lambda: qs.select_bwd(G1, G2, inv, ROWS, K, C))]
         lines.append(f"per call of the HIP stage (one launch each, through its Python wrapper), median of {args.blocks} blocks of {args.reps}:")
         total = 0.0

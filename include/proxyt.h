@@ -714,6 +714,44 @@ PTX_API int ptx_dec_boxes(const float *h, const float *weight, const float *bias
 PTX_API int ptx_dec_scores(const float *hidden, int NL, int B, int K, int C, const float *text, const uint8_t *text_mask, int T,
                            int max_text_len, int scaled, const float *bias, float *out, void *stream);
 
+/* ------------------------------------------------------------------ the grounding loss behind the decoder (ABI 13, by addition)
+ * GroundingHead.loss as the shipped configuration runs it (dense_heads/grounding_head.py:606-824): the matching costs of
+ * HungarianAssigner3D, the sigmoid focal loss over the unmasked text tokens and the decoupled corner (Chamfer) loss of the matched boxes,
+ * forward and backward; assembled in Python (proxytransformation_amd/grounding_loss.py), restated in numpy (grounding_loss_host.py).
+ * fp32; no float atomics and fixed summation orders: two calls on the same inputs give the same bits; everything on `stream`, no host
+ * wait; host checks (PTX_EINVAL with the numbers in the message) come before anything is enqueued.  A box is (cx,cy,cz, sx,sy,sz,
+ * a0,a1,a2) with R = Rz(a0) Rx(a1) Ry(a2) and the corners c + R (+-s/2).  Masks are bytes of 0 / 1 (torch.bool): 1 = a real token.
+ *
+ * out (N,M) = vol(A n B) / (vol A + vol B - vol(A n B)) of boxes1 (N,9) against boxes2 (M,9): the exact intersection volume of the two
+ * hexahedra, coplanar faces decided once per pair of faces (grounding_loss_host.py states the rule); NaN for a box with a NaN, an inf or
+ * a non-positive size.  One launch. */
+PTX_API int ptx_gl_iou(const float *boxes1, int N, const float *boxes2, int M, float *out, void *stream);
+/* cost (NL,K,SG): cost[l,q,g] = w_cls BinaryFocalLossCost(scores[l,b,q], positive_maps[g]) + w_l1 |boxes[l,b,q] - gt_boxes[g]|_1
+ * - w_iou IoU(boxes[l,b,q], gt_boxes[g]) with b = gt_scene[g]: scores (NL,B,K,M), boxes (NL,B,K,9), text_mask (B,T), gt_boxes (SG,9),
+ * positive_maps (SG,M), gt_scene (SG) on the device.  The focal cost runs over the tokens t < T with text_mask[b,t]; a masked token or a
+ * column from T on is never read.  One launch. */
+PTX_API int ptx_gl_cost(const float *scores, const float *boxes, int NL, int B, int K, int M, const uint8_t *text_mask, int T,
+                        const float *gt_boxes, const float *positive_maps, const int32_t *gt_scene, int SG, float alpha, float gamma,
+                        float w_cls, float w_l1, float w_iou, float *cost, void *stream);
+/* losses (2,NL): losses[0][l] = cls_scale sum of the focal loss of layer l over its queries and unmasked tokens, with the target row
+ * positive_maps[gt_offset[b] + assign[l,b,q]] or zeros where assign (NL,B,K) is -1; losses[1][l] = box_weight / (8 P_l) times the sum
+ * over the P_l matched queries of the four Chamfer terms weighted by decouple_weights (4 floats on the host).  gt_offset (B+1) on the
+ * device: scene b's boxes are the rows gt_offset[b] .. gt_offset[b+1] - 1.  rows: 2 NL B K floats of scratch; counts (NL): P_l.  Two
+ * launches. */
+PTX_API int ptx_gl_loss_fwd(const float *scores, const float *boxes, int NL, int B, int K, int M, const uint8_t *text_mask, int T,
+                            const float *gt_boxes, const float *positive_maps, const int32_t *gt_offset, int SG, const int32_t *assign,
+                            float alpha, float gamma, const float *decouple_weights, float cls_scale, float box_weight, float *rows,
+                            float *losses, int32_t *counts, void *stream);
+/* dscores (NL,B,K,M), dboxes (NL,B,K,9): the gradients of sum_l g_cls[l] losses[0][l] + g_box[l] losses[1][l] (g_cls, g_box (NL) on the
+ * device, NULL: ones); counts as ptx_gl_loss_fwd left it.  Exactly 0 on a masked token, from column T on, and in the box of an unmatched
+ * query.  One launch. */
+PTX_API int ptx_gl_loss_bwd(const float *scores, const float *boxes, int NL, int B, int K, int M, const uint8_t *text_mask, int T,
+                            const float *gt_boxes, const float *positive_maps, const int32_t *gt_offset, int SG, const int32_t *assign,
+                            float alpha, float gamma, const float *decouple_weights, float cls_scale, float box_weight, const float *g_cls,
+                            const float *g_box, const int32_t *counts, float *dscores, float *dboxes, void *stream);
+/* out (n) = max_t sigmoid(scores[r,t]) over all M columns of scores (n,M): a -inf column gives 0, a NaN gives NaN.  One launch. */
+PTX_API int ptx_gl_predict(const float *scores, long n, int M, float *out, void *stream);
+
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/
  * sparse_featfusion_grounder_preshape.py:428-444 (nearest, zeros padding, align_corners=True, valid_flag=True; bilinear != 0:

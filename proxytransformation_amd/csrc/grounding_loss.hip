@@ -17,16 +17,24 @@
 namespace ptx {
 
 constexpr int kGlPoly = 12;                                 // a quad clipped by six planes has at most ten vertices
-constexpr float kGlCoplanar = 1e-5f;                        // grounding_loss_host.COPLANAR_TOL
+constexpr double kGlCoplanar = 1e-5;                        // grounding_loss_host.COPLANAR_TOL
 constexpr float kGlEps = 1e-12f;                            // FocalLossCost's eps
 
-struct GlBox { float c[3], h[3], ax[3][3]; };               // centre, half sizes, ax[m] = column m of R
+// THE IoU RUNS IN DOUBLE, IN THE PLANE OF THE FACE IT CLIPS.  Two boxes that nearly coincide (a converged prediction and its target) have
+// pairs of faces tilted by theta ~ 1e-2 .. 1e-5 against each other; the line such a pair meets in lies where two distances of the order
+// theta x size cancel, so any error e in a vertex, an axis or a distance moves it by e / theta, each of the two faces' lanes moves it on
+// its own, and the strip between the two lines is counted twice or not at all: an IoU error of about 0.3 eps / theta -- 4.5e-4 at
+// theta = 1e-4 in fp32 (measured; the float64 specification moves by 1e-6 under an ulp there).  So the boxes' axes come from double
+// sines and cosines (orthonormal to 1e-16), a face's polygon is kept in the face's own two coordinates (u, v) (exactly planar), a clip
+// plane is the affine function D0 + u Du + v Dv of them, and the areas are 2D cross products.
+struct GlBox { double c[3], h[3], ax[3][3]; };              // centre, half sizes, ax[m] = column m of R
 
 // Rz Rx Ry from the cosines / sines (c, s) and the "ones" u of the three factors: u = 1 everywhere gives R; the derivative by angle k
 // takes (c_k, s_k, u_k) = (-sin, cos, 0)
-__device__ __forceinline__ void gl_rot(const float c[3], const float s[3], const float u[3], float R[3][3])
+template <typename F>
+__device__ __forceinline__ void gl_rot(const F c[3], const F s[3], const F u[3], F R[3][3])
 {
-    const float M[3][3] = {{c[0] * u[1], -s[0] * c[1], s[0] * s[1]}, {s[0] * u[1], c[0] * c[1], -c[0] * s[1]}, {0.0f, u[0] * s[1], u[0] * c[1]}};
+    const F M[3][3] = {{c[0] * u[1], -s[0] * c[1], s[0] * s[1]}, {s[0] * u[1], c[0] * c[1], -c[0] * s[1]}, {F(0), u[0] * s[1], u[0] * c[1]}};
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         R[r][0] = M[r][0] * c[2] - M[r][2] * s[2];
@@ -44,14 +52,15 @@ __device__ __forceinline__ void gl_angles(const float *a, float c[3], float s[3]
 __device__ __forceinline__ GlBox gl_box(const float *b, float cx, float cy, float cz)
 {
     GlBox o;
-    float c[3], s[3], R[3][3];
-    const float u[3] = {1.0f, 1.0f, 1.0f};
-    gl_angles(b + 6, c, s);
+    double c[3], s[3], R[3][3];
+    const double u[3] = {1.0, 1.0, 1.0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { c[k] = cos((double)b[6 + k]); s[k] = sin((double)b[6 + k]); }
     gl_rot(c, s, u, R);
-    o.c[0] = b[0] - cx; o.c[1] = b[1] - cy; o.c[2] = b[2] - cz;
+    o.c[0] = (double)b[0] - (double)cx; o.c[1] = (double)b[1] - (double)cy; o.c[2] = (double)b[2] - (double)cz;
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
-        o.h[m] = b[3 + m] * 0.5f;
+        o.h[m] = (double)b[3 + m] * 0.5;
 #pragma unroll
         for (int r = 0; r < 3; ++r) o.ax[m][r] = R[r][m];
     }
@@ -59,7 +68,7 @@ __device__ __forceinline__ GlBox gl_box(const float *b, float cx, float cy, floa
 }
 
 // axis m of the box by a runtime index, without indexing the struct's arrays dynamically
-__device__ __forceinline__ void gl_axis(const GlBox &X, int m, float a[3], float &h)
+__device__ __forceinline__ void gl_axis(const GlBox &X, int m, double a[3], double &h)
 {
 #pragma unroll
     for (int r = 0; r < 3; ++r) a[r] = m == 0 ? X.ax[0][r] : (m == 1 ? X.ax[1][r] : X.ax[2][r]);
@@ -67,21 +76,28 @@ __device__ __forceinline__ void gl_axis(const GlBox &X, int m, float a[3], float
 }
 
 // the signed distance of p to the plane of face f = 2 m + (sigma < 0), positive outside
-__device__ __forceinline__ float gl_dist(const GlBox &X, int f, const float p[3])
+__device__ __forceinline__ double gl_dist(const GlBox &X, int f, const double p[3])
 {
-    float a[3], h;
+    double a[3], h;
     gl_axis(X, f >> 1, a, h);
-    const float sg = (f & 1) ? -1.0f : 1.0f;
+    const double sg = (f & 1) ? -1.0 : 1.0;
     return sg * (a[0] * (p[0] - X.c[0]) + a[1] * (p[1] - X.c[1]) + a[2] * (p[2] - X.c[2])) - h;
 }
 
-// vertex k of face f: c + sigma h_m a_m + su h_u a_u + sv h_v a_v with (su, sv) = (+,+), (-,+), (-,-), (+,-)
-__device__ __forceinline__ void gl_quad(const GlBox &X, int f, int k, float p[3])
+// the in-plane axes of face f: u = m + 1, v = m + 2 (mod 3)
+__device__ __forceinline__ void gl_face_axes(int f, int &m, int &iu, int &iv)
 {
-    const int m = f >> 1, iu = m == 2 ? 0 : m + 1, iv = iu == 2 ? 0 : iu + 1;
-    float am[3], au[3], av[3], hm, hu, hv;
+    m = f >> 1; iu = m == 2 ? 0 : m + 1; iv = iu == 2 ? 0 : iu + 1;
+}
+
+// vertex k of face f: c + sigma h_m a_m + su h_u a_u + sv h_v a_v with (su, sv) = (+,+), (-,+), (-,-), (+,-)
+__device__ __forceinline__ void gl_quad(const GlBox &X, int f, int k, double p[3])
+{
+    int m, iu, iv;
+    gl_face_axes(f, m, iu, iv);
+    double am[3], au[3], av[3], hm, hu, hv;
     gl_axis(X, m, am, hm); gl_axis(X, iu, au, hu); gl_axis(X, iv, av, hv);
-    const float sg = (f & 1) ? -1.0f : 1.0f, su = (k == 0 || k == 3) ? 1.0f : -1.0f, sv = k < 2 ? 1.0f : -1.0f;
+    const double sg = (f & 1) ? -1.0 : 1.0, su = (k == 0 || k == 3) ? 1.0 : -1.0, sv = k < 2 ? 1.0 : -1.0;
 #pragma unroll
     for (int r = 0; r < 3; ++r) p[r] = X.c[r] + sg * hm * am[r] + su * hu * au[r] + sv * hv * av[r];
 }
@@ -89,24 +105,24 @@ __device__ __forceinline__ void gl_quad(const GlBox &X, int f, int k, float p[3]
 // THE COPLANARITY RULE (grounding_loss_host.py): face i of the first box and face j of the second are coplanar when all four vertices of
 // each lie within tol of the other's plane.  0: not; +1: coplanar, facing the same way; -1: coplanar, facing each other.  Always called
 // as (A, i, B, j), whichever face the lane is clipping: the same arithmetic gives the same decision in both directions.
-__device__ __forceinline__ int gl_coplanar(const GlBox &A, int i, const GlBox &B, int j, float tol)
+__device__ __forceinline__ int gl_coplanar(const GlBox &A, int i, const GlBox &B, int j, double tol)
 {
-    float d = 0.0f, p[3];
+    double d = 0.0, p[3];
     bool nan = false;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         gl_quad(A, i, k, p);
-        const float da = fabsf(gl_dist(B, j, p));
+        const double da = fabs(gl_dist(B, j, p));
         gl_quad(B, j, k, p);
-        const float db = fabsf(gl_dist(A, i, p));
+        const double db = fabs(gl_dist(A, i, p));
         nan = nan || !(da == da) || !(db == db);
-        d = fmaxf(d, fmaxf(da, db));
+        d = fmax(d, fmax(da, db));
     }
     if (nan || !(d <= tol)) return 0;
-    float na[3], nb[3], h;
+    double na[3], nb[3], h;
     gl_axis(A, i >> 1, na, h); gl_axis(B, j >> 1, nb, h);
-    const float dot = (na[0] * nb[0] + na[1] * nb[1] + na[2] * nb[2]) * (((i ^ j) & 1) ? -1.0f : 1.0f);
-    return dot > 0.0f ? 1 : -1;
+    const double dot = (na[0] * nb[0] + na[1] * nb[1] + na[2] * nb[2]) * (((i ^ j) & 1) ? -1.0 : 1.0);
+    return dot > 0.0 ? 1 : -1;
 }
 
 // IoU of boxes b1, b2 (9 values each) by the 16 lanes of a group (lane = 0 .. 15): every lane returns the same value.  NaN for a box
@@ -123,70 +139,80 @@ __device__ float gl_pair_iou(const float *b1, const float *b2, int lane)
 #pragma unroll
     for (int i = 3; i < 6; ++i) ok = ok && v1[i] > 0.0f && v2[i] > 0.0f;
     if (!ok) return NAN;                                    // the whole group takes this branch
-    const float va = v1[3] * v1[4] * v1[5], vb = v2[3] * v2[4] * v2[5];
+    const double va = (double)v1[3] * v1[4] * v1[5], vb = (double)v2[3] * v2[4] * v2[5];
     const GlBox A = gl_box(v1, v1[0], v1[1], v1[2]), B = gl_box(v2, v1[0], v1[1], v1[2]);
-    const float ra = sqrtf(A.h[0] * A.h[0] + A.h[1] * A.h[1] + A.h[2] * A.h[2]);
-    const float rb = sqrtf(B.h[0] * B.h[0] + B.h[1] * B.h[1] + B.h[2] * B.h[2]);
-    float vi = 0.0f;
+    const double ra = sqrt(A.h[0] * A.h[0] + A.h[1] * A.h[1] + A.h[2] * A.h[2]);
+    const double rb = sqrt(B.h[0] * B.h[0] + B.h[1] * B.h[1] + B.h[2] * B.h[2]);
+    double vi = 0.0;
     if (B.c[0] * B.c[0] + B.c[1] * B.c[1] + B.c[2] * B.c[2] <= (ra + rb) * (ra + rb)) {      // else: too far apart to meet
-        float contrib = 0.0f;
+        double contrib = 0.0;
         if (lane < 12) {
             const bool first = lane < 6;
             const int fx = first ? lane : lane - 6;
             const GlBox X = first ? A : B, Y = first ? B : A;
-            const float tol = kGlCoplanar * fmaxf(fmaxf(fmaxf(v1[3], v1[4]), v1[5]), fmaxf(fmaxf(v2[3], v2[4]), v2[5]));
-            float poly[kGlPoly][3], next[kGlPoly][3], d[kGlPoly];
-            int n = 4;
+            const double tol = kGlCoplanar * (double)fmaxf(fmaxf(fmaxf(v1[3], v1[4]), v1[5]), fmaxf(fmaxf(v2[3], v2[4]), v2[5]));
+            // the face: its point o = c + sigma h_m a_m, its axes a_u, a_v, and the quad (+-h_u, +-h_v) in them
+            int fm, iu, iv;
+            gl_face_axes(fx, fm, iu, iv);
+            double am[3], au[3], av[3], hm, hu, hv, o[3];
+            gl_axis(X, fm, am, hm); gl_axis(X, iu, au, hu); gl_axis(X, iv, av, hv);
+            const double sg = (fx & 1) ? -1.0 : 1.0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) gl_quad(X, fx, k, poly[k]);
+            for (int r = 0; r < 3; ++r) o[r] = X.c[r] + sg * hm * am[r] - Y.c[r];
+            double poly[kGlPoly][2], next[kGlPoly][2], d[kGlPoly];
+            int n = 4;
+            poly[0][0] = hu; poly[0][1] = hv; poly[1][0] = -hu; poly[1][1] = hv;
+            poly[2][0] = -hu; poly[2][1] = -hv; poly[3][0] = hu; poly[3][1] = -hv;
             for (int j = 0; j < 6 && n >= 3; ++j) {
                 const int flag = first ? gl_coplanar(A, fx, B, j, tol) : gl_coplanar(A, j, B, fx, tol);
                 if (flag == 1 && first) continue;           // the shared surface: the first box's face stands for it
                 if (flag != 0) { n = 0; break; }
+                // plane j of Y on this face: d(u, v) = D0 + u Du + v Dv, positive outside
+                double an[3], hy;
+                gl_axis(Y, j >> 1, an, hy);
+                const double sj = (j & 1) ? -1.0 : 1.0;
+                const double D0 = sj * (an[0] * o[0] + an[1] * o[1] + an[2] * o[2]) - hy;
+                const double Du = sj * (an[0] * au[0] + an[1] * au[1] + an[2] * au[2]);
+                const double Dv = sj * (an[0] * av[0] + an[1] * av[1] + an[2] * av[2]);
                 for (int k = 0; k < kGlPoly; ++k)
-                    if (k < n) d[k] = gl_dist(Y, j, poly[k]);
+                    if (k < n) d[k] = D0 + (poly[k][0] * Du + poly[k][1] * Dv);
                 int m = 0;
                 for (int k = 0; k < kGlPoly; ++k) {
                     if (k >= n) continue;
                     const int k2 = k + 1 == n ? 0 : k + 1;
-                    const bool in1 = d[k] <= 0.0f, in2 = d[k2] <= 0.0f;
+                    const bool in1 = d[k] <= 0.0, in2 = d[k2] <= 0.0;
                     if (in1 && m < kGlPoly) {
-                        next[m][0] = poly[k][0]; next[m][1] = poly[k][1]; next[m][2] = poly[k][2];
+                        next[m][0] = poly[k][0]; next[m][1] = poly[k][1];
                         ++m;
                     }
-                    if (in1 != in2 && m < kGlPoly) {        // the new vertex from the inside end: the same bits in both faces of an edge
+                    if (in1 != in2 && m < kGlPoly) {        // the new vertex from the inside end, whichever way the edge is walked
                         const int ki = in1 ? k : k2, ko = in1 ? k2 : k;
-                        const float t = d[ki] / (d[ki] - d[ko]);
+                        const double t = d[ki] / (d[ki] - d[ko]);
                         next[m][0] = poly[ki][0] + t * (poly[ko][0] - poly[ki][0]);
                         next[m][1] = poly[ki][1] + t * (poly[ko][1] - poly[ki][1]);
-                        next[m][2] = poly[ki][2] + t * (poly[ko][2] - poly[ki][2]);
                         ++m;
                     }
                 }
                 n = m;
                 for (int k = 0; k < kGlPoly; ++k)
-                    if (k < n) { poly[k][0] = next[k][0]; poly[k][1] = next[k][1]; poly[k][2] = next[k][2]; }
+                    if (k < n) { poly[k][0] = next[k][0]; poly[k][1] = next[k][1]; }
             }
             if (n >= 3) {
-                float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+                double twice = 0.0;
                 for (int k = 1; k < kGlPoly - 1; ++k) {
                     if (k + 1 >= n) continue;
-                    const float a0 = poly[k][0] - poly[0][0], a1 = poly[k][1] - poly[0][1], a2 = poly[k][2] - poly[0][2];
-                    const float c0 = poly[k + 1][0] - poly[0][0], c1 = poly[k + 1][1] - poly[0][1], c2 = poly[k + 1][2] - poly[0][2];
-                    sx += a1 * c2 - a2 * c1; sy += a2 * c0 - a0 * c2; sz += a0 * c1 - a1 * c0;
+                    const double a0 = poly[k][0] - poly[0][0], a1 = poly[k][1] - poly[0][1];
+                    const double c0 = poly[k + 1][0] - poly[0][0], c1 = poly[k + 1][1] - poly[0][1];
+                    twice += a0 * c1 - a1 * c0;
                 }
-                float a[3], h;
-                gl_axis(X, fx >> 1, a, h);
-                const float sg = (fx & 1) ? -1.0f : 1.0f;
-                const float area = 0.5f * fabsf(a[0] * sx + a[1] * sy + a[2] * sz);
-                const float height = h + sg * (a[0] * X.c[0] + a[1] * X.c[1] + a[2] * X.c[2]);
-                contrib = height * area / 3.0f;
+                const double height = hm + sg * (am[0] * X.c[0] + am[1] * X.c[1] + am[2] * X.c[2]);
+                contrib = height * (0.5 * fabs(twice)) / 3.0;
             }
         }
         for (int f = 0; f < 12; ++f) vi += __shfl(contrib, f, 16);      // the first box's faces, then the second's
-        vi = fminf(fmaxf(vi, 0.0f), fminf(va, vb));
+        vi = fmin(fmax(vi, 0.0), fmin(va, vb));
     }
-    return vi / (va + vb - vi);
+    return (float)(vi / (va + vb - vi));
 }
 
 __global__ __launch_bounds__(256) void k_gl_iou(const float *b1, const float *b2, long pairs, int M, float *out)
@@ -258,7 +284,8 @@ __global__ __launch_bounds__(256) void k_gl_predict(const float *scores, long n,
 #pragma unroll
     for (int s = 8; s >= 1; s >>= 1) {
         m = fmaxf(m, __shfl_xor(m, s, 16));
-        nan = nan || __shfl_xor((int)nan, s, 16);
+        const int other = __shfl_xor((int)nan, s, 16);      // (not behind "nan ||": a lane that skips the shuffle hands its partner nothing)
+        nan = nan || other;
     }
     if (lane == 0) out[row] = nan ? NAN : 1.0f / (1.0f + expf(-m));
 }

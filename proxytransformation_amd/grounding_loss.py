@@ -6,7 +6,8 @@
 Five calls into ``csrc/grounding_loss.hip`` on the current stream, each restated in numpy by ``grounding_loss_host.py``, which is their
 specification: ``box_iou3d`` (the IoU of two 9-DoF boxes; the reference takes it from pytorch3d's CUDA extension, which has no ROCm
 build), ``match_costs`` (every layer, scene, query and ground-truth box in ONE launch), the loss forward (two launches), its backward
-(one) and ``predict_scores``.  fp32; no float atomics and fixed summation orders, so two calls give the same bits.
+(one) and ``predict_scores``.  fp32 operands and results (the IoU's geometry between them runs in double: DESIGN.md 5.15); no float
+atomics and fixed summation orders, so two calls give the same bits.
 
 THE ONE SYNCHRONISE of the stage is in ``assign``: the cost matrices of all layers and scenes travel to the host in one copy through
 pinned memory, the stream is waited for once, ``scipy.optimize.linear_sum_assignment`` runs per (layer, scene) on
@@ -196,7 +197,10 @@ def grounding_loss(scores: torch.Tensor, boxes: torch.Tensor, text_token_mask: t
     ``avg_factor + float32 eps`` (default: ``max(sum_b min(K, G_b), 1)``), ``losses[1][l]`` the four Chamfer terms of its matched pairs,
     weighted by ``decouple_weights``, as a mean over ``8 P`` corners -- one autograd node with gradients to ``scores`` and ``boxes``
     (``grounding_loss_host.loss_host``; ``ptx_gl_loss_fwd`` / ``ptx_gl_loss_bwd``).  ``assign (NL,B,K) int32`` as ``hungarian_assign``
-    returns it.  Raises ``ValueError`` before any launch when no scene has a ground-truth box."""
+    returns it; an entry ``>= G_b`` or ``< -1`` is an unmatched query.  Raises ``ValueError`` before any launch when no scene has a
+    ground-truth box.  A layer whose ``assign`` holds no pair, in a batch that has ground truth, gets NaN as its ``losses[1][l]`` (the mean
+    of nothing, which is what the reference returns); its ``dboxes`` are exactly 0, its classification loss and every other layer are
+    untouched."""
     NL, B, K, M, T, mask = _operands("grounding_loss", scores, boxes, text_token_mask)
     dev = scores.device
     alpha, gamma = _focal_args("grounding_loss", alpha, gamma)

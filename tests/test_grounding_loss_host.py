@@ -276,3 +276,97 @@ def test_argument_checks_answer_einval_before_touching_a_device():
                                None, None) == EINVAL and b"B=65" in err()
     assert lib.ptx_gl_predict(None, 0, 16, None, None) == EINVAL and b"n=0" in err()
     assert lib.ptx_gl_predict(None, 4, 300, None, None) == EINVAL and b"M=300" in err()
+
+
+# ------------------------------------------------------------------------------------------------------------------ preconditions of the edge tests
+# (tests/test_gpu_grounding_loss_edges.py): what its inputs must be for its assertions to mean something, held on the specification alone
+def _diag_iou(A, B):
+    return np.array([gh.box_iou3d_host(a[None], b[None])[0, 0] for a, b in zip(A, B)])
+
+
+@pytest.mark.parametrize("regime", gu.IOU_REGIMES)
+def test_iou_regimes_overlap_and_are_well_conditioned(regime):
+    """A regime cannot pass on empty intersections (more than half of the 576 pairs overlap, 30 % of the thin ones), and two correct
+    fp32 evaluations cannot lie further apart than a quarter of the parity bound: the specification moves by at most ``PARITY / 4``
+    when every input moves one fp32 ulp (72 pairs, 4 draws)."""
+    A, B = gu.iou_regime(regime)
+    assert A.shape == B.shape == (gu.IOU_N, 9) and np.array_equal(A, gu.f32(A)) and np.array_equal(B, gu.f32(B))
+    ref = gh.box_iou3d_host(A, B)
+    share = float((ref > 1e-3).mean())
+    pairs = [(i, j % gu.IOU_N) for i in range(gu.IOU_N) for j in (i, i + 1, i + 7)]
+    moved = gu.ulp_sensitivity(gh.box_iou3d_host, A, B, pairs)
+    print(f"{regime}: {share:.0%} of 576 pairs overlap by more than 1e-3; ulp sensitivity {moved:.2e}")
+    assert share > gu.OVERLAP_SHARE.get(regime, 0.5) and moved <= gu.PARITY / 4
+    if regime == "thin":
+        assert ((A[:, 3:6].min(-1) <= 0.05) & (B[:, 3:6].min(-1) >= 0.02)).all()
+    if regime == "far":
+        assert np.abs(A[:, :3]).max() > 40 and np.abs(B[:, 1]).min() > 20
+    if regime == "angles":
+        assert np.abs(A[:, 6:]).max() > 10 * math.pi
+    if regime == "inside":                                   # the partner is met everywhere, and where it is inside by its half diagonal
+        inside = gu.contained(A, B)                          # the IoU is the ratio of the volumes
+        assert (np.diag(ref) > 1e-3).all() and inside.sum() >= 4 and np.abs(np.diag(ref)[inside] - 0.4 ** 3).max() <= 1e-6
+
+
+@pytest.mark.parametrize("kind", ["cubes", "thin"])
+def test_near_duplicates_converge_and_stay_within_the_rule_in_both_orders(kind):
+    """The diagonal IoU rises to 1 with ``delta``; where the coplanarity rule starts to fire the specification's two argument orders
+    differ, by less than the rule admits on the pair."""
+    floors = {"cubes": {1e-1: 0.24, 1e-2: 0.86, 1e-3: 0.98, 1e-4: 0.998}, "thin": {1e-2: 0.18}}[kind]
+    for delta in gu.DELTAS:
+        A, B = gu.near_duplicates(kind, delta)
+        fwd, bwd = _diag_iou(A, B), _diag_iou(B, A)
+        print(f"{kind} delta {delta:g}: smallest IoU {fwd.min():.4f}, order asymmetry {np.abs(fwd - bwd).max():.2e}")
+        assert fwd.min() >= floors.get(delta, 0.0) and (np.abs(fwd - bwd) <= gu.coplanar_admit(A, B)).all()
+        if delta <= 1e-5:
+            assert fwd.min() >= 0.99
+    thin = gu.near_duplicates("thin", 1e-5)
+    assert ((thin[0][:, 3:6].min(-1) <= 0.05)).all() and float(gu.coplanar_bound(*thin).max()) <= 3.1e-3      # not loose by orders
+
+
+def test_one_box_by_two_names_is_one_box_to_the_specification():
+    for name, A, B in gu.same_box_names():
+        assert len(A) == 64 and (name == "itself") == np.array_equal(A, B)
+        R = lambda X: gh.euler_matrix(X[:, 6:])              # noqa: E731
+        if "cube" in name:                                   # the same set of face normals, another order: coplanar pairs with i != j
+            assert np.abs(np.abs(np.einsum("nij,nik->njk", R(A), R(B))).max(-1) - 1).max() <= 1e-6
+            assert np.abs(np.einsum("nij,nij->nj", R(A), R(B)) - 1).max() > 0.5
+        else:
+            assert np.abs(R(A) - R(B)).max() <= 1e-6
+        for x, y in ((A, B), (B, A)):
+            assert (np.abs(_diag_iou(x, y) - 1.0) <= gu.coplanar_admit(x, y)).all(), name
+
+
+def test_the_specification_does_not_stick_at_a_saturated_score():
+    """at ``x > 17`` an fp32 ``1 - p`` is 0 and the cost would stick at ``-log(1e-12)`` x its weight; float64 follows
+    ``x``.  One token, target 0, the IoU handed in as 0."""
+    one = lambda x: float(gh.cost_host(np.full((1, 1, 1, 1), x), np.zeros((1, 1, 1, 9)), np.ones((1, 1), bool), [np.zeros((1, 9))],      # noqa: E731
+                                       [np.zeros((1, 1))], weights=(1.0, 0.0, 0.0), iou=np.zeros((1, 1, 1)))[0][0][0, 0])
+    stuck = -math.log(1e-12) * 0.75
+    assert abs(one(30.0) - stuck) > 0.05 and abs(one(30.0) - 0.75 * -math.log(math.exp(-30.0) + 1e-12)) <= 1e-3
+    assert abs(one(20.0) - 0.75 * 20.0) <= 1e-2 and one(17.5) < one(20.0) < one(30.0) < stuck + 1e-9
+
+
+def test_edge_batches_are_what_their_tests_say():
+    c = gu.explicit_batch(NL=2, B=3, K=300, M=16, T=7, tokens=(7, 3, 1), G=(48, 48, 48), seed=41)
+    assert c["assign"].shape == (2, 3, 300) and ((c["assign"] >= 0).sum(-1) == 48).all()
+    rows = np.nonzero((c["assign"].reshape(2, -1) >= 0))[1]
+    assert (rows >= 512).any() and (rows < 256).any()        # matched rows in every stride of the layer reduction
+    for b in range(3):
+        for l in range(2):
+            g = c["assign"][l, b][c["assign"][l, b] >= 0]
+            assert len(set(g.tolist())) == len(g) and g.max() < 48
+        assert ((c["pms"][b] > 0) & (c["pms"][b] < 1)).any() and not c["pms"][b][:, 7:].any() and not c["pms"][b][:, :7][:, ~c["mask"][b]].any()
+    sat = gu.saturate(c["scores"], c["mask"], 88.0, 100.0, 1)
+    live = np.broadcast_to(c["mask"][None, :, None, :], sat[..., :7].shape)
+    assert (np.abs(sat[..., :7][live]) >= 88).all() and (sat[..., :7][live] > 0).any() and (sat[..., :7][live] < 0).any()
+    assert np.isneginf(sat[..., :7][~live]).all() and np.isneginf(sat[..., 7:]).all()
+    part = gu.explicit_batch(NL=2, B=2, K=6, M=16, T=7, tokens=(7, 3), G=(4, 3), seed=42, pairs=((1, 0), (2, 2)))
+    assert ((part["assign"] >= 0).sum((1, 2)) == (1, 4)).all()
+    pred, gt = gu.dyadic_ties()
+    S, T = gh.corners_host(pred), gh.corners_host(gt)
+    dist = np.abs(S[:, :, None] - T[:, None]).sum(-1)
+    ties = (dist == dist.min(-1, keepdims=True)).sum(-1)
+    assert sorted(set(ties.ravel().tolist())) == [1, 2, 4, 8] or sorted(set(ties.ravel().tolist())) == [2, 4, 8], ties
+    assert np.array_equal(S, S.astype(np.float32)) and ((S[:, :, None] - T[:, None]) == 0).any()
+    assert (17, 48) in gu.TOKEN_EDGES and (1, 1) in gu.TOKEN_EDGES and len(gu.TOKEN_EDGES) == 15

@@ -138,6 +138,7 @@ PrepLayout prep_layout(const PtxShape &s)
     P.w3 = take((size_t)3 * s.C * s.in_dim); P.b3 = take((size_t)3 * s.C);
     P.t1 = take((size_t)s.heads * P.KT1 * P.hd);
     P.t2 = take((size_t)s.heads * P.hd * P.KT2p);
+    P.t2m = take((size_t)s.heads * P.hd * P.KT2p);
     P.ppg_w = take((size_t)s.C * s.C); P.ppg_c = take(s.C);
     for (int i = 0; i < 2; ++i) {
         P.fc1g_w[i] = take((size_t)s.hidden * s.C); P.fc1g_c[i] = take(s.hidden);
@@ -494,10 +495,16 @@ static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *pr
     // (from ~4000 images per call on -- 32 scenes of 196 views -- the two products as launches of their own, the first on the
     //  64 x 64 split-operand kernel, are faster than the latency-regime chained form: 80 + 72 vs 185 us)
     const bool chained = hd == 32 && nimg < 4096;
+    // The 16-bit pool takes the mean token as one more pixel whose feature vector is mean(f): token 0 is linear in it, so
+    //   s_h(0) = scale q_h . k0_h = sum_c w_h(c) mean(c) + e_h(0)                 (column in_dim of T1; k_img_pool's tile-0 unit)
+    //   a_h(0) v0_h + sum_p a_h(p) v_h(p) = [g_h + a_h(0) mean | a_h(0), a_h(1..hw)] T2m_h^T     (column in_dim of T2m; o-projection)
+    // and the qkv0 launch produces q alone: the first C rows of W3 / b3, a third of its tiles.  The k0 | v0 columns of `qkv0` (row
+    // stride 3 C as before) are not written on this path.
+    const bool tok0 = pooled && !pooled32;
     {   // [q | k0 | v0] of token 0 = W3 mean(f) + b3
         GemmBatch g{}; g.n = 1;
         g.p[0] = GemmProb{fm, prep + P.w3, qkv0, prep + P.b3, nullptr, nullptr, nullptr,
-                          nimg, 3 * C, s.in_dim, s.in_dim, s.in_dim, 3 * C, 0, 0, 0, EPI_NONE};
+                          nimg, tok0 ? C : 3 * C, s.in_dim, s.in_dim, s.in_dim, 3 * C, 0, 0, 0, EPI_NONE};
         if (chained) {
             g.p[0].w2 = prep + P.t1; g.p[0].c2 = we; g.p[0].n2 = P.KT1; g.p[0].ldc2 = s.heads * P.KT1;
             g.p[0].chain_tiles = s.heads; g.p[0].w2_stride = (long)P.KT1 * hd; g.p[0].c2_stride = P.KT1;
@@ -519,8 +526,7 @@ static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *pr
         PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool32(static_cast<const float *>(img), we, qkv0, nimg, s.in_dim, s.hw, C, P.KT1, EW,
                                                         attn_scale(hd), Gs, E, ML, st));
     } else if (pooled) {
-        PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool(img, dt, we, qkv0, nimg, s.in_dim, s.hw, C, P.KT1,
-                                                      EW, attn_scale(hd), Gs, E, ML, st));
+        PTX_TIMED_EXT(KID_IMG_SCORES, st, launch_img_pool(img, dt, we, fm, nimg, s.in_dim, s.hw, P.KT1, EW, Gs, E, ML, st));
     } else {
         PTX_TIMED(KID_IMG_SCORES, st, launch_img_scores(img, dt, we, qkv0, nimg, s.in_dim, s.hw, s.heads, C, P.KT1,
                                                         P.KT2p, attn_scale(hd), gbuf, st));
@@ -540,6 +546,11 @@ static int run_img_proxy(const PtxShape &s, const PtxWeights &w, const float *pr
                 gp.pe = E + (size_t)h * EW; gp.lde = s.heads * EW;
                 gp.pml = ML + (size_t)h * 5; gp.ldml = s.heads * 5;
                 gp.kg = s.in_dim;
+            }
+            if (tok0) {         // ... and from the image mean: no a_h(0) v0_h addend, the table carries the mean token
+                gp.W = prep + P.t2m + (size_t)h * hd * P.KT2p;
+                gp.ad = nullptr; gp.ldad = 0;
+                gp.fm = fm; gp.ldfm = s.in_dim;
             }
         }
         PTX_TIMED(KID_IMG_O, st, launch_gemm(g, st));
@@ -1331,8 +1342,12 @@ int ptx_forward_ex(PtxContext *ctx, const PtxShape *s, const PtxWeights *w, cons
     // over six interleaved pairs, +0.3 ... +1.2 % in three sessions; 6 scenes -0.6 %, 2 and 8 neutral (profiles/r04_tags_gated_rule_ab.txt).
     const bool tags_gated = gated && side->lo_ok && (lf.v[3] >= 0 ? lf.v[3] != 0 : est_image < 1.6 * est_cluster);
     const bool tags_tail = !cluster_on_caller && !tags_gated;
+    // k_select's own completion event is what enqueue_tags() waits for on the tags stream -- unless the tags are gated (released by
+    // the device word that k_slot_net's first thread stores) or run behind it on this stream: then nobody waits for it, and a
+    // completion signal nobody waits for is not requested
+    const bool select_event = ext_event && !tags_tail && !tags_gated;
     PTX_TIMED(KID_SELECT, cs, launch_select_order(S, centers, pad_count, order_override, order, picks, keep, kcenter,
-                                                  ksrc, bbox_in ? nullptr : mm_ws, cs, cluster_on_caller, ext_event && !tags_tail ? side->aux : nullptr,
+                                                  ksrc, bbox_in ? nullptr : mm_ws, cs, cluster_on_caller, select_event ? side->aux : nullptr,
                                                   cg_join_select ? &cjoin : nullptr));
     int32_t *tile_counts = at<int32_t>(ws, L.tile_counts);
     // The slot tags / survivor counts: only k_affine and the host need them.  When the clustering chain is the long one

@@ -225,7 +225,8 @@ struct PrepLayout {
     size_t posb_t, posb_i;          // (Mk,C) per-slot bias tables (PRE:212-215)
     size_t w3, b3;                  // (3C,in_dim), (3C): [q | k0 | v0] of token 0 from the image mean
     size_t t1;                      // (heads, KT1, hd): scale * [WkWc | K-proj of (bc+pos_i)]
-    size_t t2;                      // (heads, hd, KT2p): [WvWc | V-proj of (bc+pos_i)] (transposed)
+    size_t t2;                      // (heads, hd, KT2p): [WvWc | V-proj of (bc+pos_i)] (transposed); column in_dim (i = 0) is 0
+    size_t t2m;                     // the same with column in_dim filled: the mean token as one more pixel (16-bit pool)
     // LayerNorm folds (GemmProb::lnp_in): norm_img -> proxy_proj of the image block; norm2 -> fc1 of both blocks
     size_t ppg_w, ppg_c;            // (C,C), (C)
     size_t fc1g_w[2], fc1g_c[2];    // (hidden,C), (hidden) for the text / image block
@@ -277,6 +278,9 @@ struct GemmProb {
     // with the split-softmax factors of row r computed from ML[r] = (m0, l0, m1, l1, s(0)); the row scalar
     // `rs` is then a_h(0) = ct (gemm.hip, k_gemm32<SK, 1>)
     const float *pg, *pe, *pml; int ldg, gslab, lde, ldml, kg;
+    // fm != null (k_gemm32<SK, 2>): the mean token is merged as one more pixel whose feature vector is fm[r] (R, kg), ld = ldfm:
+    // column k < kg gets  + a_h(0) fm[r][k],  column kg holds a_h(0) against W's column kg, and there is no `rs` / `ad` addend
+    const float *fm; int ldfm;
     // LayerNorm folded across a GEMM -> GEMM seam (no LayerNorm launch, no normalised copy of the rows):
     //   producer (lnp_out != null): besides C, every 32-column tile writes the partial (sum, M2 = sum of squared distances from
     //     the tile's own mean) of its rows' FINAL values over its columns inside N to lnp_out[(row * ceil(N/32) + tile) * 2 + {0,1}];
@@ -426,8 +430,8 @@ int launch_img_gather(const void *img, int dt, int nimg, int in_dim, int hw, int
 bool img_pool_supported(int dt, int in_dim, int hw, int heads);
 size_t img_pool_bytes(int nimg, int in_dim, int EW);
 void img_pool_layout(float *scratch, int nimg, int in_dim, int EW, float **Gs, float **E, float **ML);
-int launch_img_pool(const void *img, int dt, const float *we, const float *qkv0, int nimg, int in_dim, int hw, int C,
-                    int KT1, int EW, float scale, float *Gs, float *E, float *ML, hipStream_t st);
+int launch_img_pool(const void *img, int dt, const float *we, const float *fm, int nimg, int in_dim, int hw,
+                    int KT1, int EW, float *Gs, float *E, float *ML, hipStream_t st);
 
 // imgpool32.hip (r05): the same single pass for fp32 features -- a unit = (image, 128 pixels) = a PAIR of the 16-bit kernel's units,
 // results in the same (Gs, E, ML) layout

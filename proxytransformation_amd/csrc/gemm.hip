@@ -569,8 +569,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm128x(GemmBatch gb, int nrep)
 // basic block and hipcc interleaves the next tile's global loads with the MFMAs.
 // blockIdx.x = row tile: work-groups that share an A row-panel land on the same XCD (b % 8)
 // whenever the row-tile count is a multiple of 8.
-template <int SK, int AMODE, bool CHAIN = false, bool LN = false>   // AMODE 1: A merged on the fly from the k_img_pool tiles; CHAIN: see
-                                                                    // GemmProb::w2; LN: as in k_gemm64
+template <int SK, int AMODE, bool CHAIN = false, bool LN = false>   // AMODE 1: A merged on the fly from the k_img_pool tiles, 2: and
+                                                                    // from the image mean (GemmProb::fm); CHAIN: see GemmProb::w2;
+                                                                    // LN: as in k_gemm64
 __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
 {
     const GemmProb pr = gb.p[blockIdx.z];
@@ -592,31 +593,36 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 aA0, aA1, aA2, aA3, wA0, wA1, wA2, wA3, aB0, aB1, aB2, aB3, wB0, wB1, wB2, wB3;
     float4 gA0 = z4, gA1 = z4, gA2 = z4, gA3 = z4, gB0 = z4, gB1 = z4, gB2 = z4, gB3 = z4;      // AMODE 1: second tile's sums
+    float4 fA0 = z4, fA1 = z4, fA2 = z4, fA3 = z4, fB0 = z4, fB1 = z4, fB2 = z4, fB3 = z4;      // AMODE 2: the mean token's features
     int kA = 0, kB = 0;
     (void)kA; (void)kB;
     // AMODE 1: rows of the pooled partials and the split-softmax factors of this lane's four staging rows
-    size_t g0 = 0, g1 = 0, g2 = 0, g3 = 0, e0 = 0, e1 = 0, e2 = 0, e3 = 0;
+    size_t g0 = 0, g1 = 0, g2 = 0, g3 = 0, e0 = 0, e1 = 0, e2 = 0, e3 = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0;
     float fc0[4] = {0.f, 0.f, 0.f, 0.f}, fc1[4] = {0.f, 0.f, 0.f, 0.f}, fct[4] = {0.f, 0.f, 0.f, 0.f};
     float *cts = lds + (size_t)SK * (4 * 32 * LDT);         // [32] a_h(0) of the tile's rows (AMODE 1)
     float *lnst = cts + 32 + wv * 64;                       // [32][2] mean, rstd of the tile's rows (LayerNorm consumer), per wave
     const bool ln = LN && pr.lnp_in != nullptr;             // work-group uniform
     float mu4[4] = {0.0f, 0.0f, 0.0f, 0.0f};                // means of this lane's four staging rows (0: nothing to centre)
-    if (AMODE == 1) {
+    if (AMODE >= 1) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = min(row0 + r0 + 8 * i, pr.R - 1);
             const float *ml = pr.pml + (size_t)row * pr.ldml;
-            const float m0 = ml[0], l0 = ml[1], m1 = ml[2], l1 = ml[3], s0 = ml[4];
-            const float m = fmaxf(fmaxf(m0, m1), s0);
-            const float x0 = __expf(m0 - m), x1 = __expf(m1 - m), xt = __expf(s0 - m);
+            const float mt0 = ml[0], l0 = ml[1], mt1 = ml[2], l1 = ml[3], s0 = ml[4];
+            const float m = fmaxf(fmaxf(mt0, mt1), s0);
+            const float x0 = __expf(mt0 - m), x1 = __expf(mt1 - m), xt = __expf(s0 - m);
             const float inv = 1.0f / ((l0 * x0 + l1 * x1) + xt);
             fc0[i] = x0 * inv; fc1[i] = x1 * inv; fct[i] = xt * inv;
-            if (wv == 0 && (lane & 7) == 0) cts[r0 + 8 * i] = fct[i];
+            if (AMODE == 1 && wv == 0 && (lane & 7) == 0) cts[r0 + 8 * i] = fct[i];
         }
         g0 = (size_t)min(row0 + r0, pr.R - 1) * pr.ldg; g1 = (size_t)min(row0 + r0 + 8, pr.R - 1) * pr.ldg;
         g2 = (size_t)min(row0 + r0 + 16, pr.R - 1) * pr.ldg; g3 = (size_t)min(row0 + r0 + 24, pr.R - 1) * pr.ldg;
         e0 = (size_t)min(row0 + r0, pr.R - 1) * pr.lde; e1 = (size_t)min(row0 + r0 + 8, pr.R - 1) * pr.lde;
         e2 = (size_t)min(row0 + r0 + 16, pr.R - 1) * pr.lde; e3 = (size_t)min(row0 + r0 + 24, pr.R - 1) * pr.lde;
+        if (AMODE == 2) {
+            m0 = (size_t)min(row0 + r0, pr.R - 1) * pr.ldfm; m1 = (size_t)min(row0 + r0 + 8, pr.R - 1) * pr.ldfm;
+            m2 = (size_t)min(row0 + r0 + 16, pr.R - 1) * pr.ldfm; m3 = (size_t)min(row0 + r0 + 24, pr.R - 1) * pr.ldfm;
+        }
     }
 #define PTX_FETCH(S, j_)                                                                  \
     do {                                                                                  \
@@ -638,6 +644,12 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
             g##S##1 = *reinterpret_cast<const float4 *>(pr.pg + g1 + pr.gslab + kc_);     \
             g##S##2 = *reinterpret_cast<const float4 *>(pr.pg + g2 + pr.gslab + kc_);     \
             g##S##3 = *reinterpret_cast<const float4 *>(pr.pg + g3 + pr.gslab + kc_);     \
+            if (AMODE == 2) {                                                             \
+                f##S##0 = *reinterpret_cast<const float4 *>(pr.fm + m0 + kc_);            \
+                f##S##1 = *reinterpret_cast<const float4 *>(pr.fm + m1 + kc_);            \
+                f##S##2 = *reinterpret_cast<const float4 *>(pr.fm + m2 + kc_);            \
+                f##S##3 = *reinterpret_cast<const float4 *>(pr.fm + m3 + kc_);            \
+            }                                                                             \
         } else {                                                                          \
             a##S##0 = *reinterpret_cast<const float4 *>(pr.pe + e0 + (kc_ - pr.kg));      \
             a##S##1 = *reinterpret_cast<const float4 *>(pr.pe + e1 + (kc_ - pr.kg));      \
@@ -656,6 +668,9 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
         if (k##S < pr.kg) {                                                               \
             a##S##i_ = make_float4(a##S##i_.x * fc0[i_] + g##S##i_.x * fc1[i_], a##S##i_.y * fc0[i_] + g##S##i_.y * fc1[i_], \
                                    a##S##i_.z * fc0[i_] + g##S##i_.z * fc1[i_], a##S##i_.w * fc0[i_] + g##S##i_.w * fc1[i_]); \
+            if (AMODE == 2)           /* + a_h(0) mean(f): fp32 FMAs, nothing narrower */ \
+                a##S##i_ = make_float4(fmaf(fct[i_], f##S##i_.x, a##S##i_.x), fmaf(fct[i_], f##S##i_.y, a##S##i_.y), \
+                                       fmaf(fct[i_], f##S##i_.z, a##S##i_.z), fmaf(fct[i_], f##S##i_.w, a##S##i_.w)); \
         } else {                                                                          \
             const int t_ = k##S - pr.kg;      /* token: 0 = mean token, 1..128 tile 0, 129.. tile 1 */ \
             a##S##i_.x *= t_ == 0 ? fct[i_] : (t_ <= 128 ? fc0[i_] : fc1[i_]);           \
@@ -667,7 +682,7 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
 #define PTX_STASH(S, buf_)                                                                \
     do {                                                                                  \
         float *A_s = base + (buf_) * (2 * 32 * LDT) + r0 * LDT + kq, *W_s = A_s + 32 * LDT; \
-        if (AMODE == 1) { PTX_MERGE(S, 0); PTX_MERGE(S, 1); PTX_MERGE(S, 2); PTX_MERGE(S, 3); } \
+        if (AMODE >= 1) { PTX_MERGE(S, 0); PTX_MERGE(S, 1); PTX_MERGE(S, 2); PTX_MERGE(S, 3); } \
         if (LN) { sub4(a##S##0, mu4[0]); sub4(a##S##1, mu4[1]); sub4(a##S##2, mu4[2]); sub4(a##S##3, mu4[3]); } \
         *reinterpret_cast<float4 *>(A_s) = a##S##0;                                       \
         *reinterpret_cast<float4 *>(A_s + 8 * LDT) = a##S##1;                             \
@@ -697,7 +712,7 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
     float bias = 0.0f, lnc = 0.0f, resv[16], adv[16], rsv[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { resv[r] = 0.0f; adv[r] = 0.0f; rsv[r] = 0.0f; }
-    const bool has_ad = AMODE == 1 || pr.rs != nullptr;      // work-group uniform
+    const bool has_ad = AMODE == 1 || (AMODE == 0 && pr.rs != nullptr);      // work-group uniform
     if (wv == 0) {
         const int nc = min(n, pr.N - 1);
         if (pr.bias) bias = pr.bias[nc];
@@ -782,7 +797,7 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
             const bool ok = ncol && row < pr.R;
             if (ok) {
                 if (AMODE == 1) v = fmaf(cts[rl], adv[r], v);
-                else if (pr.rs) v = fmaf(rsv[r], adv[r], v);
+                else if (AMODE == 0 && pr.rs) v = fmaf(rsv[r], adv[r], v);
                 if (pr.res) v += resv[r];
                 pr.C[(size_t)row * pr.ldc + n] = v;
             }
@@ -815,7 +830,10 @@ __global__ __launch_bounds__(SK * 64) void k_gemm32(GemmBatch gb)
         //  tile order rotated per row tile so that the 25 work-groups of a head do not read the same W2 lines at once; ONE staging
         //  buffer per wave instead of two (a wave's LDS operations execute in order, the area is wave-private) and the chained
         //  variant under 170 VGPRs, so that all 600 work-groups are resident at once: correct, 24.2 us.  What bounds the launch
-        //  is neither latency nor residency: the 200 chain work-groups write the 19 MB of `we` in ~9 us -- 2 TB/s of stores.)
+        //  is neither latency nor residency: the 200 chain work-groups write the 19 MB of `we` in ~9 us -- 2 TB/s of stores.
+        //  Since then the 16-bit pooled path launches the q columns alone -- the 400 plain work-groups produced k0 | v0, which the
+        //  tables carry now (api.hip, `tok0`): 200 work-groups in one round, 23.3 -> 18.9 us in the kernel trace, median of 40
+        //  steps, profiles/img_token0_timeline.txt.)
         auto load_w2 = [&](int t, float4 (&wb)[4]) {
             const float *wr = W2 + (size_t)min(t * 32 + li, pr.n2 - 1) * 32 + hh * 4;
 #pragma unroll
@@ -879,9 +897,13 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
         const GemmProb &p = gb.p[g];
         PTX_REQUIRE((p.A || p.pg) && p.W && p.C, "gemm: null operand in group %d", g);
         PTX_REQUIRE((p.pg != nullptr) == (gb.p[0].pg != nullptr), "gemm: mixed A modes in one batch");
-        PTX_REQUIRE(p.pg == nullptr || (p.pe && p.pml && p.ad && p.kg % BK == 0 && p.kg <= p.K && p.ldg % 4 == 0 &&
-                                        p.gslab % 4 == 0 && p.lde % 4 == 0),
+        PTX_REQUIRE(p.pg == nullptr || (p.pe && p.pml && (p.ad != nullptr) != (p.fm != nullptr) && p.kg % BK == 0 && p.kg <= p.K &&
+                                        p.ldg % 4 == 0 && p.gslab % 4 == 0 && p.lde % 4 == 0),
                     "gemm: bad pooled-A description in group %d", g);
+        PTX_REQUIRE(p.fm == nullptr || (p.pg != nullptr && p.rs == nullptr && p.ldfm % 4 == 0 && p.ldfm >= p.kg &&
+                                        (reinterpret_cast<uintptr_t>(p.fm) & 15) == 0),
+                    "gemm: bad mean-token description in group %d", g);
+        PTX_REQUIRE((p.fm != nullptr) == (gb.p[0].fm != nullptr), "gemm: mixed A modes in one batch");
         PTX_REQUIRE(p.R >= 1 && p.N >= 1 && p.K >= 4, "gemm: empty problem in group %d", g);
         PTX_REQUIRE(p.K % 4 == 0 && p.lda % 4 == 0 && p.ldw % 4 == 0,
                     "gemm: K=%d lda=%d ldw=%d must be multiples of 4", p.K, p.lda, p.ldw);
@@ -953,7 +975,8 @@ int launch_gemm(const GemmBatch &gb_in, hipStream_t st, int compute_dtype)
     }
     if (gb.p[0].pg != nullptr) {
         // A merged on the fly from the pooling tiles: always the latency-regime kernel, K split four ways
-        PTX_TRY((launch_gemm32<4, 1>(gb, rmax, nmax, st)));
+        if (gb.p[0].fm != nullptr) PTX_TRY((launch_gemm32<4, 2>(gb, rmax, nmax, st)));
+        else PTX_TRY((launch_gemm32<4, 1>(gb, rmax, nmax, st)));
     } else if (tiles32 >= g64_min) {
         // enough tiles to fill the chip: 64x64 tiles re-use each staged operand twice as often
         const dim3 grid(cdiv(rmax, 64), cdiv(nmax, 64), gb.n);

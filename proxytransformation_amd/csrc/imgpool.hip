@@ -37,6 +37,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int kPoolHeads = 8;
 constexpr int kPoolNtImages = 4096;      // images per launch (~21 scenes of 196 views) from which the partials are stored as streaming lines (see the write-out)
 constexpr int kPoolWPad = 544;          // LDS row stride (elements) of the split weights: rows 16 words apart mod 64
+static_assert(kPoolWPad >= 512 + 16 + 16, "a weight row: 512 channels, then (4 B per wave) the fp16 scales and the mean token's score partials");
 constexpr int kPoolPPad = 136;          // LDS row stride (elements) of the split numerators (128 pixels + 8)
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -101,11 +102,11 @@ __device__ __forceinline__ u32x4 shr_elems(const u32x4 &v, int k)
 }
 
 struct PoolArgs {
-    const unsigned short *img; const float *we, *qkv0;
-    int nimg, in_dim, hw, C, KT1, EW; float scale;
+    const unsigned short *img; const float *we, *fm;     // fm [nimg][in_dim]: the image means (k_img_mean)
+    int nimg, in_dim, hw, KT1, EW;
     float *Gs;          // [nimg][2][heads][in_dim]  sum_p e_h(p) f(c,p) of the tile
     float *E;           // [nimg][heads][EW]         token 0: 1, token 1 + p: e_h(p) = exp(s_h(p) - m_tile), 0 beyond hw
-    float *ML;          // [nimg][heads][5]          m_0, l_0, m_1, l_1, s_h(0) = scale * q_h . k0_h (mean token)
+    float *ML;          // [nimg][heads][5]          m_0, l_0, m_1, l_1, s_h(0) = sum_c w_h(c) mean(c) + e_h(0) (mean token)
 };
 // These three are the A operand of the o-projection GEMM, which merges the two tiles and the mean token on the
 // fly (split softmax, gemm.hip k_gemm32<4, 1>): m = max(m_0, m_1, s(0)), l = l_0 e^(m_0-m) + l_1 e^(m_1-m) + e^(s(0)-m),
@@ -146,6 +147,8 @@ __global__ __launch_bounds__(512) void k_img_pool(PoolArgs a)
     float wv[heads];
 #pragma unroll
     for (int h = 0; h < heads; ++h) wv[h] = wim[(size_t)h * a.KT1 + tid];
+    // ... and, in the tile-0 unit, this thread's channel of the image mean: the mean token is one more pixel (below)
+    const float fmv = T == 0 ? a.fm[(size_t)im * in_dim + tid] : 0.0f;
     u32x4 L[2][8];
     const bool tensor_end = im == a.nimg - 1 && cw + 64 == in_dim;    // wave-uniform
 #pragma unroll
@@ -171,15 +174,11 @@ __global__ __launch_bounds__(512) void k_img_pool(PoolArgs a)
         const int p = 128 * T + lane + 64 * u;
         ev[u] = p < hw ? wim[(size_t)wid * a.KT1 + in_dim + 1 + p] : 0.0f;
     }
-    // score of the mean token, s_h(0) = scale * q_h . k0_h (wave = head; published by the tile-0 unit)
-    // (only the loads here: reducing right away would wait for them -- and, in order, for all the feature loads
-    // above -- before the weight loads below are even issued)
-    float sq = 0.0f, sk = 0.0f;
-    if (T == 0) {
-        const int hd = a.C / heads;
-        const float *qv = a.qkv0 + (size_t)im * 3 * a.C + wid * hd;
-        if (lane < hd) { sq = qv[lane]; sk = qv[a.C + lane]; }
-    }
+    // score of the mean token (wave = head; published by the tile-0 unit): token 0 is linear in the image mean, so it is the
+    // score of a pixel whose feature vector is mean(f),  s_h(0) = sum_c w_h(c) mean(c) + e_h(0),  e_h(0) = column in_dim of
+    // [w_h | e_h] (prep.hip, k_prep_t1) -- the qkv0 launch no longer produces k0.  Here only the load of e_h(0); the sum over the
+    // channels is taken below from the weights this thread holds anyway (fp32 products, fixed order).
+    const float e0 = T == 0 ? wim[(size_t)wid * a.KT1 + in_dim] : 0.0f;
     // head weights of this image -> three 16-bit parts in LDS.  Thread = channel, so wave w splits exactly the 64
     // channels it contracts in stage 1 (in_dim = 512 = one channel per thread) and, for fp16, scales them by a
     // power of two of its own: no other wave needs to know it (all loads first).
@@ -189,6 +188,11 @@ __global__ __launch_bounds__(512) void k_img_pool(PoolArgs a)
         const int c = tid;                                      // in_dim == 512 == threads (img_pool_supported)
 #pragma unroll
         for (int h = 0; h < heads; ++h) {
+            if (T == 0) {       // (block-uniform) this wave's 64 channels of s_h(0): parked in the padding of the weight rows
+                                // (behind the fp16 scales), summed over the waves by wave h behind the first barrier
+                const float ps = wave_sum(wv[h] * fmv);
+                if (lane == 0) *reinterpret_cast<float *>(wpart + (size_t)h * kPoolWPad + in_dim + 16 + 2 * wid) = ps;
+            }
             if (DT == 2) {
                 const int k = pow2_scale_exp(wave_max(fabsf(wv[h])));
                 wv[h] *= pow2f(k);
@@ -259,7 +263,11 @@ __global__ __launch_bounds__(512) void k_img_pool(PoolArgs a)
         for (int u = 0; u < 2; ++u) e[u] = 128 * T + lane + 64 * u < hw ? expf(sv[u] - m) : 0.0f;
         const float l = wave_sum(e[0] + e[1]);
         float *erow = a.E + ((size_t)im * heads + h) * a.EW;
-        const float s0 = T == 0 ? wave_sum(sq * sk) * a.scale : 0.0f;
+        float s0 = e0;          // wave-uniform; the eight channel slices in wave order
+        if (T == 0) {
+#pragma unroll
+            for (int w = 0; w < 8; ++w) s0 += *reinterpret_cast<const float *>(wpart + (size_t)h * kPoolWPad + in_dim + 16 + 2 * w);
+        }
         if (lane == 0) {
             float *ml = a.ML + ((size_t)im * heads + h) * 5;
             ml[2 * T] = m;
@@ -384,11 +392,11 @@ void img_pool_layout(float *scratch, int nimg, int in_dim, int EW, float **Gs, f
 }
 
 // Gs / E / ML: the three result arrays of img_pool_layout(), already offset to the first image of this launch
-int launch_img_pool(const void *img, int dt, const float *we, const float *qkv0, int nimg, int in_dim, int hw, int C,
-                    int KT1, int EW, float scale, float *Gs, float *E, float *ML, hipStream_t st)
+int launch_img_pool(const void *img, int dt, const float *we, const float *fm, int nimg, int in_dim, int hw,
+                    int KT1, int EW, float *Gs, float *E, float *ML, hipStream_t st)
 {
     PTX_REQUIRE(EW % 4 == 0 && EW >= hw + 1 && hw > 128 && hw <= 255, "img pool: hw=%d EW=%d", hw, EW);
-    PoolArgs pa{static_cast<const unsigned short *>(img), we, qkv0, nimg, in_dim, hw, C, KT1, EW, scale, Gs, E, ML};
+    PoolArgs pa{static_cast<const unsigned short *>(img), we, fm, nimg, in_dim, hw, KT1, EW, Gs, E, ML};
     const size_t lds = sizeof(float) * 8 * kPoolHeads * 128 + sizeof(unsigned short) * 24 * (kPoolWPad + kPoolPPad);
     PTX_REQUIRE(lds <= 64 * 1024, "img pool: %zu B of LDS", lds);
     static const int nt_env = getenv("PTX_POOL_NT") ? atoi(getenv("PTX_POOL_NT")) : -1;      // A/B runs: 0 / 1 force it

@@ -61,7 +61,8 @@ __global__ void k_prep_w3(const float *qw, const float *kw, const float *vw, con
 }
 
 // T1[h][t][d], t < in_dim : scale * sum_j Wk[h*hd+d][j] * Wc[j][t]
-//              t = in_dim+i: scale * sum_j Wk[h*hd+d][j] * (bc[j] + pos[i][j])   (i = 0 unused: 0)
+//              t = in_dim+i: scale * sum_j Wk[h*hd+d][j] * (bc[j] + pos[i][j])   (i = 0: the mean token, whose "feature vector"
+//              is mean(f) -- s_h(0) = sum_c w_h(c) mean(c) + e_h(0), imgpool.hip; no other reader of [w_h | e_h] touches e_h(0))
 __global__ void k_prep_t1(const float *kw, const float *cw, const float *cb, const float *pos, int C,
                           int in_dim, int hw, int heads, float scale, float *t1)
 {
@@ -73,7 +74,7 @@ __global__ void k_prep_t1(const float *kw, const float *cw, const float *cb, con
     float s = 0.0f;
     if (t < in_dim) {
         for (int j = 0; j < C; ++j) s = fmaf(wk[j], cw[(size_t)j * in_dim + t], s);
-    } else if (t > in_dim) {
+    } else {
         const float *pi = pos + (size_t)(t - in_dim) * C;
         for (int j = 0; j < C; ++j) s = fmaf(wk[j], cb[j] + pi[j], s);
     }
@@ -81,9 +82,11 @@ __global__ void k_prep_t1(const float *kw, const float *cw, const float *cb, con
 }
 
 // T2[h][d][t], t < in_dim : sum_j Wv[h*hd+d][j] * Wc[j][t]
-//              t = in_dim+i: sum_j Wv[h*hd+d][j] * (bc[j] + pos[i][j]) for 1 <= i <= hw, else 0
+//              t = in_dim+i: sum_j Wv[h*hd+d][j] * (bc[j] + pos[i][j]) for i0 <= i <= hw, else 0
+// i0 = 1: the mean token's value row comes from the qkv0 GEMM (a_h(0) v0_h in the o-projection's epilogue: the fp32 pool and the
+// three-launch path, whose A operand carries a_h(0) in column in_dim);  i0 = 0: the table carries it (the 16-bit pool, api.hip)
 __global__ void k_prep_t2(const float *vw, const float *cw, const float *cb, const float *pos, int C,
-                          int in_dim, int hw, int heads, int KT2p, float *t2)
+                          int in_dim, int hw, int heads, int KT2p, int i0, float *t2)
 {
     const int hd = C / heads;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,7 +96,7 @@ __global__ void k_prep_t2(const float *vw, const float *cw, const float *cb, con
     float s = 0.0f;
     if (t < in_dim) {
         for (int j = 0; j < C; ++j) s = fmaf(wv[j], cw[(size_t)j * in_dim + t], s);
-    } else if (t > in_dim && t <= in_dim + hw) {
+    } else if (t >= in_dim + i0 && t <= in_dim + hw) {
         const float *pi = pos + (size_t)(t - in_dim) * C;
         for (int j = 0; j < C; ++j) s = fmaf(wv[j], cb[j] + pi[j], s);
     }
@@ -154,7 +157,9 @@ int run_prepare(const PtxShape &s, const PtxWeights &w, float *prep, hipStream_t
                        w.cm_b, w.pos, C, s.in_dim, s.hw, s.heads, scale, prep + P.t1);
     PTX_LAUNCHED("k_prep_t1");
     hipLaunchKernelGGL(k_prep_t2, dim3(cdiv(s.heads * P.hd * P.KT2p, T)), dim3(T), 0, st, w.v_w, w.cm_w,
-                       w.cm_b, w.pos, C, s.in_dim, s.hw, s.heads, P.KT2p, prep + P.t2);
+                       w.cm_b, w.pos, C, s.in_dim, s.hw, s.heads, P.KT2p, 1, prep + P.t2);
+    hipLaunchKernelGGL(k_prep_t2, dim3(cdiv(s.heads * P.hd * P.KT2p, T)), dim3(T), 0, st, w.v_w, w.cm_w,
+                       w.cm_b, w.pos, C, s.in_dim, s.hw, s.heads, P.KT2p, 0, prep + P.t2m);
     PTX_LAUNCHED("k_prep_t2");
     PTX_TRY(launch_prep_lnfold(w.img.pp_w, w.norm_img_w, w.norm_img_b, w.img.pp_b, C, C, prep + P.ppg_w, prep + P.ppg_c, st));
     const PtxBlock *blk[2] = {&w.text, &w.img};

@@ -714,6 +714,32 @@ PTX_API int ptx_dec_boxes(const float *h, const float *weight, const float *bias
 PTX_API int ptx_dec_scores(const float *hidden, int NL, int B, int K, int C, const float *text, const uint8_t *text_mask, int T,
                            int max_text_len, int scaled, const float *bias, float *out, void *stream);
 
+/* ------------------------------------------------------------------ the decoder's operators under autograd (ABI 13, by addition)
+ * The backward of ptx_dec_attention and ptx_dec_ln (csrc/decoder_bwd.hip); the Linear's backward is ptx_op_gemm / ptx_op_colsum /
+ * ptx_op_eltwise, assembled in Python (proxytransformation_amd/decoder.py), restated in numpy (decoder_grad_host.py).  The same rules:
+ * fp32, no float atomics, fixed summation orders, everything on `stream`, no host wait, host checks before anything is enqueued.
+ *
+ * ptx_dec_attention with one more result: stats (B,H,Kq,2) = the final maximum and sum (m, l) of every (scene, head, query); l == 0 marks
+ * a query without a key (m = -inf).  The same kernel and the same bits in `out` as ptx_dec_attention. */
+PTX_API int ptx_dec_attention_stats(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask, int B,
+                                    int Kq, int L, int H, int hd, float *out, float *stats, void *stream);
+/* The gradients of ptx_dec_attention: with P = expf((q / sqrtf(hd)) k^T - m) / l recomputed from stats, D = rowsum(dout * out),
+ * dP = dout v^T, dS = P (dP - D): dv = P^T dout, dq = dS k / sqrtf(hd), dk = dS^T q / sqrtf(hd).  out, dout, dq (B,Kq,H hd) and dk, dv
+ * (B,L,H hd) are dense; q, k, v and their strides as in the forward.  Every element of dq, dk, dv is written exactly once (no memset by
+ * the caller): zeros for a masked key (never read, here either), for every key of a scene whose queries have no key and for the dq of a
+ * query without a key.  rowdot: (B,H,Kq) floats of workspace (D).  Two launches: queries x key tiles ascending for dq, keys x query tiles
+ * ascending for dk / dv. */
+PTX_API int ptx_dec_attention_bwd(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask, int B,
+                                  int Kq, int L, int H, int hd, const float *out, const float *stats, const float *dout, float *dq,
+                                  float *dk, float *dv, float *rowdot, void *stream);
+/* The gradients of ptx_dec_ln at x (n,C): mean and rstd are recomputed as the forward computes them.  One norm (weight2 NULL): dy (n,C)
+ * is the gradient of out; dx = LN^T(dy), xdy = xhat * dy; dweight = colsum(xdy), dbias = colsum(dy) (ptx_op_colsum).  Two norms
+ * (weight2 given, with bias, g1 and xdy2): dy and dy2 are the gradients of out and out2, either may be NULL (zeros), not both;
+ * g1 = dy + LN2^T(dy2), dx = LN^T(g1), xdy = xhat * g1, xdy2 = xhat2 * dy2; dweight = colsum(xdy), dbias = colsum(g1),
+ * dweight2 = colsum(xdy2), dbias2 = colsum(dy2).  C: a multiple of 64 up to 512.  One launch. */
+PTX_API int ptx_dec_ln_bwd(const float *x, long n, int C, const float *weight, const float *bias, float eps, const float *weight2,
+                           const float *dy, const float *dy2, float *dx, float *xdy, float *g1, float *xdy2, void *stream);
+
 /* ------------------------------------------------------------------ the grounding loss behind the decoder (ABI 13, by addition)
  * GroundingHead.loss as the shipped configuration runs it (dense_heads/grounding_head.py:606-824): the matching costs of
  * HungarianAssigner3D, the sigmoid focal loss over the unmasked text tokens and the decoupled corner (Chamfer) loss of the matched boxes,

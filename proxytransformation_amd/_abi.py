@@ -217,6 +217,9 @@ SIGNATURES.update({
     "ptx_dec_ln": (_I, [_P, _L, _I, _P, _P, _F, _P, _P, _P, _P, _P]),
     "ptx_dec_boxes": (_I, [_P, _P, _P, _I, _P, _L, _P, _P]),
     "ptx_dec_scores": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "ptx_dec_attention_stats": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "ptx_dec_attention_bwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ptx_dec_ln_bwd": (_I, [_P, _L, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ptx_gl_iou": (_I, [_P, _I, _P, _I, _P, _P]),
     "ptx_gl_cost": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _P, _P]),
     "ptx_gl_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _F, _F, _P, _F, _F, _P, _P, _P, _P]),

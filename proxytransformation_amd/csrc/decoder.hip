@@ -10,6 +10,8 @@
 //   ptx_dec_attention  one flash-style kernel: work-group = (64 queries, head, scene), key tiles of 64 in ascending order, the running
 //       maximum and sum per query, heads merged in the output.  Both products run on the exact-fp32 matrix instruction.  A masked key is
 //       never read (predicated loads), a key tile that is masked throughout is skipped, a query without a key gets zeros.
+//       ptx_dec_attention_stats: the same kernel, which then also stores the final (m, l) of every query for the backward
+//       (decoder_bwd.hip); the store is null-checked, the arithmetic and the bits of `out` are the same.
 //   ptx_dec_ln         LayerNorm over rows of width C: the mean first, then the centred sum of squares; optionally a second LayerNorm of
 //       the first one's result (the decoder's `norm` behind `norms[3]`), both written.
 //   ptx_dec_boxes      the last Linear (C -> 9) of a regression branch and the baseline box decode against the query coordinates:
@@ -123,6 +125,7 @@ struct DecAttnArgs {
     const float *q, *k, *v;                                 // (B,Kq,.) / (B,L,.) with row strides ldq / ldk / ldv; head h at column h HD
     const uint8_t *mask;                                    // (B,L), 1 = ignore the key; null: no key is masked
     float *out;                                             // (B,Kq,H HD)
+    float *stats;                                           // (B,H,Kq,2) or null: the final maximum and sum (m, l); l == 0: no key
     int B, Kq, L, H;
     long ldq, ldk, ldv;
     float scale;
@@ -261,6 +264,10 @@ __global__ __launch_bounds__(256) void k_dec_attn(DecAttnArgs a)
         __syncthreads();
     }
     if (qd == 0) s_l[srow] = l_run;
+    if (a.stats != nullptr && qd == 0 && q0 + srow < a.Kq) {   // what the backward recomputes P from
+        float *st = a.stats + (((size_t)b * a.H + head) * a.Kq + q0 + srow) * 2;
+        st[0] = m_run; st[1] = l_run;
+    }
     if (HD == 32 && wc == 1) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) Ps[0][tile_row(r, wr, hh)][li] = o[r];
@@ -381,10 +388,9 @@ int ptx_dec_linear(const float *x, const float *add, int add_cols, long n, const
     return PTX_OK;
 }
 
-int ptx_dec_attention(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask, int B, int Kq, int L,
-                      int H, int hd, float *out, void *stream)
+static int dec_attention(const char *who, const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask,
+                         int B, int Kq, int L, int H, int hd, float *out, float *stats, bool want_stats, void *stream)
 {
-    const char *who = "ptx_dec_attention";
     PTX_REQUIRE(B >= 1 && B <= kHeadMaxScenes && Kq >= 1 && Kq <= kHeadMaxK && L >= 1 && L <= (1 << 24),
                 "%s: B=%d Kq=%d L=%d (B: 1 to 64; Kq: 1 to 1024; L: 1 to 2^24)", who, B, Kq, L);
     PTX_REQUIRE((hd == 32 || hd == 64) && H >= 1 && H * hd <= 512, "%s: H=%d hd=%d (hd: 32 or 64; H hd up to 512)", who, H, hd);
@@ -392,16 +398,28 @@ int ptx_dec_attention(const float *q, long ldq, const float *k, long ldk, const 
     PTX_REQUIRE(ldq >= C && ldk >= C && ldv >= C && ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ldq <= (1 << 20) && ldk <= (1 << 20) &&
                     ldv <= (1 << 20),
                 "%s: ldq=%ld ldk=%ld ldv=%ld (row strides: multiples of 4 from H hd=%ld to 2^20)", who, ldq, ldk, ldv, C);
-    PTX_REQUIRE(q && k && v && out, "%s: null argument", who);
+    PTX_REQUIRE(q && k && v && out && (stats || !want_stats), "%s: null argument", who);
     PTX_REQUIRE(sp_aligned16({q, k, v}), "%s: q, k and v must be 16-byte aligned", who);
     DecAttnArgs a{};
-    a.q = q; a.k = k; a.v = v; a.mask = mask; a.out = out; a.B = B; a.Kq = Kq; a.L = L; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
+    a.q = q; a.k = k; a.v = v; a.mask = mask; a.out = out; a.stats = stats; a.B = B; a.Kq = Kq; a.L = L; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
     a.scale = 1.0f / sqrtf((float)hd);
     const dim3 grid(cdiv(Kq, 64), H, B);
     if (hd == 64) hipLaunchKernelGGL((k_dec_attn<64>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL((k_dec_attn<32>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
     PTX_LAUNCHED("k_dec_attn");
     return PTX_OK;
+}
+
+int ptx_dec_attention(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask, int B, int Kq, int L,
+                      int H, int hd, float *out, void *stream)
+{
+    return dec_attention("ptx_dec_attention", q, ldq, k, ldk, v, ldv, mask, B, Kq, L, H, hd, out, nullptr, false, stream);
+}
+
+int ptx_dec_attention_stats(const float *q, long ldq, const float *k, long ldk, const float *v, long ldv, const uint8_t *mask, int B, int Kq,
+                            int L, int H, int hd, float *out, float *stats, void *stream)
+{
+    return dec_attention("ptx_dec_attention_stats", q, ldq, k, ldk, v, ldv, mask, B, Kq, L, H, hd, out, stats, true, stream);
 }
 
 int ptx_dec_ln(const float *x, long n, int C, const float *weight, const float *bias, float eps, float *out, const float *weight2,

@@ -17,8 +17,14 @@ Parity-unpinned against ``nn.MultiheadAttention``: a masked key is never read (a
 by a zero weight).  A query whose every key is masked gets zeros from the attention, so the layer adds ``out_proj.bias`` only: what torch
 2.10 gives in both grad modes; older releases give NaN.
 
-Out of scope: training and backward, attention masks, bf16, ``num_reg=12`` and the FCAF coder, the loss and ``predict_by_feat``.  There
-is no CPU path: tensors must be on the GPU and the library must be built."""
+Under autograd: ``attention``, ``linear``, ``layer_norm`` and ``linear_add_ln`` take ``differentiable=True`` and are then one
+``torch.autograd.Function`` node each (``linear_add_ln``: two), with the same forward bits, gradients specified by
+``decoder_grad_host.py``, no synchronise and no atomics: the body of a decoder layer trains.  Without the keyword they detach their
+operands as before.
+
+Out of scope: ``GroundingDecoder(differentiable=True)`` (its ``forward`` stays under ``no_grad``), the backward of ``posembed`` (a
+training-mode BatchNorm), of ``boxes`` and of ``contrastive_scores``, double backward, dropout, attention masks, bf16, ``num_reg=12`` and
+the FCAF coder, the loss and ``predict_by_feat``.  There is no CPU path: tensors must be on the GPU and the library must be built."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -26,10 +32,12 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _abi, decoder_host, query_select
+from . import train as _train_ops
 from .query_select import QuerySelect
-from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _gpu, _mask_bytes, _np, _ptr, _stream, _width
+from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _gpu, _mask_bytes, _np, _ptr, _stream, _wants_grad, _width
 
 __all__ = ["GroundingDecoder", "attention", "boxes", "contrastive_scores", "layer_norm", "linear", "linear_add_ln", "posembed"]
 
@@ -83,10 +91,18 @@ def posembed(x: torch.Tensor, module) -> torch.Tensor:
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor] = None, relu: bool = False,
-           add_cols: Optional[int] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+           add_cols: Optional[int] = None, residual: Optional[torch.Tensor] = None, differentiable: bool = False) -> torch.Tensor:
     """``(...,Cout) fp32 = act((x + add) @ weight.T + bias) (+ residual)`` on ``x (...,Cin)``: the add is fused into the operand load and
     reaches the output columns below ``add_cols`` only (a multiple of 64; default: all).  ``Cin``: a multiple of 64 up to 2048;
-    ``Cout``: a multiple of 64 up to 4096.  The ReLU keeps a NaN (``decoder_host.linear_host``; ``ptx_dec_linear``, one launch)."""
+    ``Cout``: a multiple of 64 up to 4096.  The ReLU keeps a NaN (``decoder_host.linear_host``; ``ptx_dec_linear``, one launch).
+    ``differentiable=True``: one autograd node with gradients to ``x``, ``add``, ``weight``, ``bias``, ``residual``, the same forward
+    bits (``decoder_grad_host.linear_bwd_host``); ``relu`` together with ``residual`` is refused there."""
+    if differentiable:
+        if relu and residual is not None:
+            raise NotImplementedError("linear: differentiable=True with relu and a residual is not implemented (the decoder never uses it; "
+                                      "the ReLU's mask would need a second saved tensor)")
+        if _wants_grad(x, weight, bias, add, residual):
+            return _LinearFn.apply(x, weight, bias, add, residual, bool(relu), add_cols)
     _gpu("linear", x, weight, bias, add, residual)
     dev = x.device
     x, weight, bias = _f32(x, "linear", dev), _f32(weight, "linear", dev), _f32(bias, "linear", dev)
@@ -113,6 +129,90 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     return out
 
 
+def _dweight_rows(g: torch.Tensor, lo: int, hi: int, xs: torch.Tensor, dw: torch.Tensor) -> None:
+    """``dw[lo:hi] = g[:, lo:hi].T @ xs`` with ``g (n,Cout)``, ``xs (n,Cin)``: ``ptx_op_gemm`` on the strided column range through
+    ``train.mm_rows``, which cuts a long contraction into few tiles into slices over the rows (``ksplit``) that ``ptx_op_colsum`` adds
+    in double -- the one rule ``train.mm`` follows too."""
+    n, cout = g.shape
+    cin = int(xs.shape[1])
+    _train_ops.mm_rows(g, xs, dw, hi - lo, cin, n, a=(1, cout), b=(cin, 1), a_off=lo, c_off=lo * cin)
+
+
+class _LinearFn(torch.autograd.Function):
+    """``linear`` as one node.  Saved: ``x``, ``add``, ``weight`` and, behind a ReLU, the result (its sign is the mask).  The backward is
+    the training operators' kernels: ``dpre = dy * (out > 0)`` (``ptx_op_eltwise`` 5), ``dx = dpre W`` and
+    ``dadd = dpre[:, :add_cols] W[:add_cols]`` (``ptx_op_gemm``), ``dW[:add_cols] = dpre[:, :add_cols]^T (x + add)`` on the materialised
+    sum (rounded as the forward's operand load rounds it) and ``dW[add_cols:] = dpre[:, add_cols:]^T x`` -- every row of ``dW`` written
+    once, no accumulate call -- ``dbias = colsum(dpre)`` in double (``ptx_op_colsum``), ``dresidual = dy``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, add, residual, relu, add_cols):
+        out = linear(x, weight, bias, add, relu, add_cols, residual)
+        dev = out.device
+        cout = int(weight.shape[0])
+        ctx.relu, ctx.cols = relu, (0 if add is None else cout if add_cols is None else int(add_cols))
+        ctx.have = (add is not None, relu)
+        ctx.meta = [(None, None) if t is None else (tuple(t.shape), t.dtype) for t in (x, weight, bias, add, residual)]
+        keep = [_f32(x, "linear", dev), _f32(weight, "linear", dev)]
+        if add is not None:
+            keep.append(_f32(add, "linear", dev))
+        if relu:
+            keep.append(out)
+        ctx.save_for_backward(*keep)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        saved = list(ctx.saved_tensors)
+        x, w = saved[0], saved[1]
+        add = saved[2] if ctx.have[0] else None
+        out = saved[-1] if ctx.have[1] else None
+        dev = dy.device
+        cout, cin = int(w.shape[0]), int(w.shape[1])
+        n, cols = x.numel() // cin, ctx.cols
+        need_x, need_w, need_b, need_add, need_res = ctx.needs_input_grad[:5]
+        dy = _f32(dy, "linear", dev)
+        grads = [None] * 5
+        if need_res:
+            grads[4] = dy
+        if n == 0:
+            for i, (shape, dt) in enumerate(ctx.meta[:4]):
+                if shape is not None and ctx.needs_input_grad[i]:
+                    grads[i] = torch.zeros(shape, dtype=dt, device=dev)
+        else:
+            with torch.cuda.device(dev):
+                g = dy.view(n, cout)
+                if ctx.relu:
+                    g = _train_ops.eltwise(5, out.view(n, cout), g)
+                x2 = x.view(n, cin)
+                if need_x or (need_add and cols == cout):
+                    grads[0] = _train_ops.mm(g, w).view(x.shape)
+                if need_add:
+                    if cols == cout:
+                        grads[3] = grads[0]
+                    elif cols == 0:
+                        grads[3] = torch.zeros_like(x)
+                    else:
+                        grads[3] = torch.empty_like(x)
+                        _train_ops.gemm(g, w, grads[3], n, cin, cols, a=(cout, 1), b=(cin, 1), c=(cin, 1))
+                if not need_x:
+                    grads[0] = None
+                if need_w:
+                    dw = torch.empty_like(w)
+                    if cols:
+                        _dweight_rows(g, 0, cols, x2 if add is None else _train_ops.eltwise(0, x2, add.view(n, cin)), dw)
+                    if cols < cout:
+                        _dweight_rows(g, cols, cout, x2, dw)
+                    grads[1] = dw
+                if need_b:
+                    grads[2] = _train_ops.colsum(g)
+        for i, (shape, dt) in enumerate(ctx.meta):
+            if grads[i] is not None:
+                grads[i] = grads[i].reshape(shape).to(dt)
+        return tuple(grads) + (None, None)
+
+
 def _rows_view(what: str, t: torch.Tensor, dev) -> Tuple[torch.Tensor, int]:
     """``t (B,n,C)`` as the attention takes it: fp32, unit stride along C, scene b a whole number of rows behind scene b - 1."""
     if t.device != dev or t.dim() != 3:
@@ -125,14 +225,25 @@ def _rows_view(what: str, t: torch.Tensor, dev) -> Tuple[torch.Tensor, int]:
     return t, int(t.stride(1))
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], num_heads: int) -> torch.Tensor:
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], num_heads: int,
+              differentiable: bool = False) -> torch.Tensor:
     """``(B,Kq,C) fp32``: multi-head attention of ``q (B,Kq,C)`` over ``k``, ``v (B,L,C)`` with the key padding mask ``mask (B,L)`` bool,
     True = ignore (``None``: no key is masked); ``q`` is scaled by ``1/sqrt(hd)``, heads are merged in the output.  The operands may be column ranges of a wider
     projection output (strided views).  Head dimension 32 or 64.  One flash-style launch: key tiles of 64 in ascending order, an online
     maximum and sum; a tile that is masked throughout is skipped.  A masked key is never read -- a NaN under it leaves no trace
     (parity-unpinned: ``nn.MultiheadAttention`` multiplies it by a zero weight).  A query whose every key is masked gets zeros (torch 2.10;
     older torch gives NaN).  A NaN in an unmasked key or value of a head reaches the outputs of that scene and head
-    (``decoder_host.attention_host``; ``ptx_dec_attention``)."""
+    (``decoder_host.attention_host``; ``ptx_dec_attention``).  ``differentiable=True``: one autograd node with gradients to ``q``, ``k``,
+    ``v`` (contiguous ``(B,n,C)``; the slice backward of a strided operand places them), the same forward bits
+    (``decoder_grad_host.attention_bwd_host``; ``ptx_dec_attention_stats`` / ``ptx_dec_attention_bwd``)."""
+    if differentiable and _wants_grad(q, k, v):
+        return _AttentionFn.apply(q, k, v, mask, int(num_heads))
+    return _attention(q, k, v, mask, num_heads, False)[0]
+
+
+def _attention(q, k, v, mask, num_heads, want_stats: bool):
+    """``attention``'s checks and launch: ``(out, (q, k, v, mask, stats) as the launch took them)``; ``stats (B,H,Kq,2)`` -- the final
+    maximum and sum of every query -- only with ``want_stats``, None when nothing was launched."""
     _gpu("attention", q, k, v, mask)
     dev = q.device
     if q.dim() != 3 or k.dim() != 3 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
@@ -147,13 +258,56 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[
         mask = _mask_bytes("attention", "the mask", mask, (B, L))
     out = torch.empty((B, Kq, C), dtype=torch.float32, device=dev)
     if Kq == 0:
-        return out
+        return out, None
     if L == 0:
-        return out.zero_()
+        return out.zero_(), None
     (q, ldq), (k, ldk), (v, ldv) = _rows_view("attention", q, dev), _rows_view("attention", k, dev), _rows_view("attention", v, dev)
+    if want_stats:
+        stats = torch.empty((B, H, Kq, 2), dtype=torch.float32, device=dev)
+        _abi.check(_abi.lib().ptx_dec_attention_stats(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, _ptr(mask), B, Kq, L, H, C // H,
+                                                      out.data_ptr(), stats.data_ptr(), _stream(dev)), "ptx_dec_attention_stats")
+        return out, (q, k, v, mask, stats)
     _abi.check(_abi.lib().ptx_dec_attention(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, _ptr(mask), B, Kq, L, H, C // H,
                                             out.data_ptr(), _stream(dev)), "ptx_dec_attention")
-    return out
+    return out, None
+
+
+class _AttentionFn(torch.autograd.Function):
+    """``attention`` as one node: saves the operands as the launch took them, the result and ``(m, l)`` per query; the backward
+    recomputes the probabilities (``ptx_dec_attention_bwd``: two launches, every gradient element written once)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, mask, H):
+        out, saved = _attention(q, k, v, mask, H, True)
+        ctx.H, ctx.shapes, ctx.dtypes = H, (tuple(q.shape), tuple(k.shape)), (q.dtype, k.dtype, v.dtype)
+        ctx.launched = saved is not None
+        if ctx.launched:
+            ctx.has_mask = saved[3] is not None
+            ctx.save_for_backward(*(t for t in saved if t is not None), out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        (B, Kq, C), (_, L, _) = ctx.shapes
+        dev, H = dout.device, ctx.H
+        if not ctx.launched:                                 # no query or no key: nothing flowed
+            zeros = lambda n, dt: torch.zeros((B, n, C), dtype=dt, device=dev)      # noqa: E731
+            return zeros(Kq, ctx.dtypes[0]), zeros(L, ctx.dtypes[1]), zeros(L, ctx.dtypes[2]), None, None
+        saved = list(ctx.saved_tensors)
+        out = saved.pop()
+        q, k, v = saved[:3]
+        mask, stats = (saved[3] if ctx.has_mask else None), saved[-1]
+        dout = _f32(dout, "attention", dev)
+        dq = torch.empty((B, Kq, C), dtype=torch.float32, device=dev)
+        dk, dv = torch.empty((B, L, C), dtype=torch.float32, device=dev), torch.empty((B, L, C), dtype=torch.float32, device=dev)
+        rowdot = torch.empty((B, H, Kq), dtype=torch.float32, device=dev)
+        _abi.check(_abi.lib().ptx_dec_attention_bwd(q.data_ptr(), int(q.stride(1)), k.data_ptr(), int(k.stride(1)), v.data_ptr(),
+                                                    int(v.stride(1)), _ptr(mask), B, Kq, L, H, C // H, out.data_ptr(), stats.data_ptr(),
+                                                    dout.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), rowdot.data_ptr(),
+                                                    _stream(dev)), "ptx_dec_attention_bwd")
+        need = ctx.needs_input_grad
+        return tuple(g.to(dt) if n else None for g, dt, n in zip((dq, dk, dv), ctx.dtypes, need[:3])) + (None, None)
 
 
 def _ln_pair(ln) -> Tuple[torch.Tensor, torch.Tensor, float]:
@@ -162,11 +316,23 @@ def _ln_pair(ln) -> Tuple[torch.Tensor, torch.Tensor, float]:
     return ln[0], ln[1], float(ln[2]) if len(ln) > 2 else LN_EPS
 
 
-def layer_norm(x: torch.Tensor, ln, ln2=None, out2: Optional[torch.Tensor] = None):
+def layer_norm(x: torch.Tensor, ln, ln2=None, out2: Optional[torch.Tensor] = None, differentiable: bool = False):
     """``LayerNorm(x)`` over the last axis of ``x (...,C)``; with ``ln2`` also ``LayerNorm2`` of that result: ``(out, out2)``.  ``ln``:
     an ``nn.LayerNorm`` or ``(weight, bias[, eps])``.  The row mean first, then the centred sum of squares
     (``decoder_host.layer_norm_host``; ``ptx_dec_ln``, one launch).  ``out2``: a contiguous fp32 tensor of x's shape that receives the
-    second result (a layer's slot of ``hidden_states``)."""
+    second result (a layer's slot of ``hidden_states``).  ``differentiable=True``: one autograd node with gradients to ``x`` and both
+    norms' weight and bias, the same forward bits; either result may go unused (``decoder_grad_host.layer_norm_bwd_host``;
+    ``ptx_dec_ln_bwd``); ``out2`` is refused there."""
+    if differentiable:
+        if out2 is not None:
+            raise ValueError("layer_norm: out2 cannot be given with differentiable=True (an in-place slot cannot be a graph output)")
+        w, b, eps = _ln_pair(ln)
+        w2, b2, eps2 = _ln_pair(ln2) if ln2 is not None else (None, None, eps)
+        if _wants_grad(x, w, b, w2, b2):
+            if eps2 != eps:
+                raise ValueError(f"layer_norm: both norms must share eps, got {eps} and {eps2}")
+            res = _LayerNormFn.apply(x, w, b, w2, b2, eps)
+            return res[0] if ln2 is None else res
     _gpu("layer_norm", x)
     dev = x.device
     x = _f32(x, "layer_norm", dev)
@@ -195,12 +361,69 @@ def layer_norm(x: torch.Tensor, ln, ln2=None, out2: Optional[torch.Tensor] = Non
     return out if ln2 is None else (out, out2)
 
 
+class _LayerNormFn(torch.autograd.Function):
+    """``layer_norm`` as one node with one or two results.  Saved: ``x`` and the parameters; the statistics (and, with the second norm,
+    the first result) are recomputed by ``ptx_dec_ln_bwd``, which writes ``dx = LN1^T(dy + LN2^T(dy2))`` and the per-row terms whose
+    column sums in double (``ptx_op_colsum``) are the parameters' gradients.  A result nobody used arrives as None and is not read."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, w2, b2, eps):
+        two = w2 is not None
+        res = layer_norm(x, (w, b, eps), (w2, b2, eps) if two else None)
+        dev = x.device
+        ctx.eps, ctx.two = eps, two
+        ctx.meta = [(None, None) if t is None else (tuple(t.shape), t.dtype) for t in (x, w, b, w2, b2)]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*(_f32(t, "layer_norm", dev) for t in ((x, w, b, w2) if two else (x, w))))
+        return res if two else (res,)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dys):
+        saved = ctx.saved_tensors
+        x, w = saved[0], saved[1]
+        b, w2 = (saved[2], saved[3]) if ctx.two else (None, None)
+        dev = x.device
+        C = int(x.shape[-1])
+        n = x.numel() // C
+        dy = _f32(dys[0], "layer_norm", dev)
+        dy2 = _f32(dys[1], "layer_norm", dev) if ctx.two else None
+        grads = [None] * 5
+        if dy is None and dy2 is None:
+            return tuple(grads) + (None,)
+        if n == 0:
+            grads = [None if shape is None else torch.zeros(shape, dtype=dt, device=dev) for shape, dt in ctx.meta]
+            return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad)) + (None,)
+        dx, xdy = torch.empty_like(x), torch.empty_like(x)
+        g1, xdy2 = (torch.empty_like(x), torch.empty_like(x)) if ctx.two else (None, None)
+        _abi.check(_abi.lib().ptx_dec_ln_bwd(x.data_ptr(), n, C, w.data_ptr(), _ptr(b), ctx.eps, _ptr(w2), _ptr(dy), _ptr(dy2), dx.data_ptr(),
+                                             xdy.data_ptr(), _ptr(g1), _ptr(xdy2), _stream(dev)), "ptx_dec_ln_bwd")
+        need = ctx.needs_input_grad
+        with torch.cuda.device(dev):
+            grads[0] = dx
+            if need[1]:
+                grads[1] = _train_ops.colsum(xdy.view(n, C))
+            if need[2]:
+                grads[2] = _train_ops.colsum((g1 if ctx.two else dy).view(n, C))
+            if ctx.two and need[3]:
+                grads[3] = _train_ops.colsum(xdy2.view(n, C))
+            if ctx.two and need[4]:
+                grads[4] = _train_ops.colsum(dy2.view(n, C)) if dy2 is not None else torch.zeros((C,), dtype=torch.float32, device=dev)
+        out = []
+        for g, (shape, dt), wanted in zip(grads, ctx.meta, need):
+            out.append(g.reshape(shape).to(dt) if (g is not None and wanted) else None)
+        return tuple(out) + (None,)
+
+
 def linear_add_ln(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], residual: torch.Tensor, ln, ln2=None,
-                  out2: Optional[torch.Tensor] = None):
+                  out2: Optional[torch.Tensor] = None, differentiable: bool = False):
     """``LayerNorm(x @ weight.T + bias + residual)``: an attention's out-projection or the FFN's second layer, the identity and the
     norm behind it; with ``ln2`` also the decoder's ``norm`` of that result, ``(out, out2)``.  Two launches: the residual is added in the
-    GEMM's epilogue, the norm needs whole rows (``decoder_host.linear_add_ln_host``)."""
-    return layer_norm(linear(x, weight, bias, residual=residual), ln, ln2, out2)
+    GEMM's epilogue, the norm needs whole rows (``decoder_host.linear_add_ln_host``).  ``differentiable=True``: the composition of
+    ``linear`` and ``layer_norm`` under autograd, two nodes; ``out2`` is refused there."""
+    if differentiable and out2 is not None:
+        raise ValueError("linear_add_ln: out2 cannot be given with differentiable=True (an in-place slot cannot be a graph output)")
+    return layer_norm(linear(x, weight, bias, residual=residual, differentiable=differentiable), ln, ln2, out2, differentiable)
 
 
 def boxes(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], coords: torch.Tensor,

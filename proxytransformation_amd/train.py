@@ -102,6 +102,23 @@ def gemm(A, B, C, M, N, K, a=(0, 1), b=(0, 1), c=(0, 1), batch=1, inner=1, a_bs=
                                1 if accumulate else 0, ksplit, c_sk, _st()), "ptx_op_gemm")
 
 
+def mm_rows(A, B, C, M, N, K, a, b, a_off=0, b_off=0, c_off=0, alpha=1.0, accumulate=False):
+    """The M dense rows of N floats that start ``c_off`` elements into the contiguous ``C`` (+)= alpha op(A) op(B), the operands given by
+    their (row stride, col stride) ``a`` / ``b`` and element offsets (a column range of a wider matrix, a transpose).  Decides the
+    k-split for ``mm`` and for every other caller."""
+    kw = dict(a=a, b=b, c=(N, 1), a_off=a_off, b_off=b_off, alpha=alpha)
+    tiles = ((M + 63) // 64) * ((N + 63) // 64)
+    if K >= 1024 and tiles < 512 and not accumulate:
+        # a long contraction into a small result (weight gradients): slices of K across the chip, summed in order.  A
+        # work-group's walk over K is a chain of dependent round trips, so the slices are short (>= 256 k = 8 steps) and many
+        ks = int(min(256, max(2, 2048 // tiles), max(2, K // 256)))
+        part = torch.empty((ks, M * N), dtype=_F32, device=A.device)
+        gemm(A, B, part, M, N, K, ksplit=ks, c_sk=M * N, **kw)
+        colsum(part, out=C.view(-1)[c_off:c_off + M * N])
+        return
+    gemm(A, B, C, M, N, K, c_off=c_off, accumulate=accumulate, **kw)
+
+
 def mm(a2, b2, ta=False, tb=False, out=None, alpha=1.0, accumulate=False):
     """Dense 2-D product of contiguous matrices: op(a2) @ op(b2)."""
     ar, ac = a2.shape
@@ -111,17 +128,7 @@ def mm(a2, b2, ta=False, tb=False, out=None, alpha=1.0, accumulate=False):
     assert K == K2, (a2.shape, b2.shape, ta, tb)
     if out is None:
         out = torch.empty((M, N), dtype=_F32, device=a2.device)
-    kw = dict(a=(1, ac) if ta else (ac, 1), b=(1, bc) if tb else (bc, 1), c=(N, 1), alpha=alpha)
-    tiles = ((M + 63) // 64) * ((N + 63) // 64)
-    if K >= 1024 and tiles < 512 and not accumulate:
-        # a long contraction into a small result (weight gradients): slices of K across the chip, summed in order.  A
-        # work-group's walk over K is a chain of dependent round trips, so the slices are short (>= 256 k = 8 steps) and many
-        ks = int(min(256, max(2, 2048 // tiles), max(2, K // 256)))
-        part = torch.empty((ks, M * N), dtype=_F32, device=a2.device)
-        gemm(a2, b2, part, M, N, K, ksplit=ks, c_sk=M * N, **kw)
-        colsum(part, out=out.view(-1))
-        return out
-    gemm(a2, b2, out, M, N, K, accumulate=accumulate, **kw)
+    mm_rows(a2, b2, out, M, N, K, a=(1, ac) if ta else (ac, 1), b=(1, bc) if tb else (bc, 1), alpha=alpha, accumulate=accumulate)
     return out
 
 

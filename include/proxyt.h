@@ -740,6 +740,44 @@ PTX_API int ptx_dec_attention_bwd(const float *q, long ldq, const float *k, long
 PTX_API int ptx_dec_ln_bwd(const float *x, long n, int C, const float *weight, const float *bias, float eps, const float *weight2,
                            const float *dy, const float *dy2, float *dx, float *xdy, float *g1, float *xdy2, void *stream);
 
+/* ------------------------------------------------------------------ training through the whole decoder (ABI 13, by addition)
+ * What ptx_dec_attention_bwd / ptx_dec_ln_bwd leave open (csrc/decoder_train.hip): PositionEmbeddingLearned with a training-mode
+ * BatchNorm, the backward of ptx_dec_boxes and of ptx_dec_scores; restated in numpy by decoder_grad_host.py.  The same rules: fp32, no
+ * float atomics, fixed summation orders, everything on `stream`, no host wait, host checks before anything is enqueued.  Sums over rows
+ * run in double over slabs of rows that are added in ascending order; their workspace is
+ * ptx_dec_train_workspace_bytes(n, C, nv) bytes (8-byte aligned) for nv values per channel: 0 where n (1 to 2^24), C (a multiple of 64
+ * up to 512) or nv (1 to 10) is out of range. */
+PTX_API size_t ptx_dec_train_workspace_bytes(long n, int C, int nv);
+/* The batch statistics of z = x w1^T + b1 over the n >= 2 rows of x (n,cin), 1 <= cin <= 9, w1 (C,cin): mean and centred sum of squares
+ * per channel (row slabs merged with Chan's formula in double), then, per channel in double and rounded once: rstd = 1 / sqrt(M2 / n +
+ * eps), w1f = w1 gamma rstd, b1f = (b1 - mean) gamma rstd + beta -- the operands ptx_dec_posembed then takes -- and stats (2,C) =
+ * (mean | rstd).  run_mean / run_var (both or neither): `repeat` sequential fp32 updates r = (1 - momentum) r + momentum v with the batch
+ * mean and the unbiased variance M2 / (n - 1).  Workspace: nv = 2.  Two launches. */
+PTX_API int ptx_dec_posembed_stats(const float *x, long n, int cin, const float *w1, const float *b1, const float *gamma, const float *beta,
+                                   int C, double eps, float momentum, int repeat, float *run_mean, float *run_var, float *w1f, float *b1f,
+                                   float *stats, void *workspace, size_t ws_bytes, void *stream);
+/* h (n,C) = relu(x w1f^T + b1f): the hidden tensor of ptx_dec_posembed, its bits (the ReLU keeps a NaN).  One launch. */
+PTX_API int ptx_dec_posembed_hidden(const float *x, long n, int cin, const float *w1f, const float *b1f, int C, float *h, void *stream);
+/* The first layer's and the BatchNorm's gradients from dh (n,C), the gradient of the hidden tensor: dpre = dh where the recomputed hidden
+ * value is > 0 (a NaN passes nothing), zhat = (z - mean) rstd; dgb (2,C) = (dbeta = sum dpre | dgamma = sum dpre zhat);
+ * dz = gamma rstd (dpre - dbeta / n - zhat dgamma / n); dw1 (C,cin) = dz^T x, db1 (C) = sum dz.  Workspace: nv = max(cin + 1, 2).  Four
+ * launches. */
+PTX_API int ptx_dec_posembed_bwd(const float *x, long n, int cin, const float *w1, const float *b1, const float *gamma, const float *stats,
+                                 const float *w1f, const float *b1f, const float *dh, int C, float *dgb, float *dw1, float *db1,
+                                 void *workspace, size_t ws_bytes, void *stream);
+/* The gradients of ptx_dec_boxes under dboxes (n,9): p = h weight^T + bias recomputed as the forward forms it; dp (n,9) = dboxes on the
+ * centre and the angles, (expf(p) >= 0.02 ? dboxes : 0) * expf(p) on the sizes (torch's exp().clamp(min=0.02): NaN where p is NaN);
+ * dh (n,C) = dp weight, dweight (9,C) = dp^T h.  dbias = the column sums of dp (ptx_op_colsum).  Workspace: nv = 9.  Three launches. */
+PTX_API int ptx_dec_boxes_bwd(const float *h, const float *weight, const float *bias, int C, long n, const float *dboxes, float *dh, float *dp,
+                              float *dweight, void *workspace, size_t ws_bytes, void *stream);
+/* The gradients of ptx_dec_scores under dscores (NL,B,K,max_text_len), read only at the tokens t < T with text_mask[b,t] (a NaN elsewhere
+ * leaves no trace): dhidden (NL,B,K,C) = dscores text (/ sqrtf(C) when scaled), dtext (B,T,C) = sum over (layer, query) ascending of
+ * dscores^T hidden (/ sqrtf(C)), zeros on a masked token; dbias (1), optional = sum of dscores, per (layer, scene) in double and then
+ * ascending, with NL B doubles of workspace.  Two launches, four with dbias. */
+PTX_API int ptx_dec_scores_bwd(const float *dscores, const float *hidden, int NL, int B, int K, int C, const float *text,
+                               const uint8_t *text_mask, int T, int max_text_len, int scaled, float *dhidden, float *dtext, float *dbias,
+                               void *workspace, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------ the grounding loss behind the decoder (ABI 13, by addition)
  * GroundingHead.loss as the shipped configuration runs it (dense_heads/grounding_head.py:606-824): the matching costs of
  * HungarianAssigner3D, the sigmoid focal loss over the unmasked text tokens and the decoupled corner (Chamfer) loss of the matched boxes,

@@ -220,6 +220,12 @@ SIGNATURES.update({
     "ptx_dec_attention_stats": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "ptx_dec_attention_bwd": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ptx_dec_ln_bwd": (_I, [_P, _L, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ptx_dec_train_workspace_bytes": (_Z, [_L, _I, _I]),
+    "ptx_dec_posembed_stats": (_I, [_P, _L, _I, _P, _P, _P, _P, _I, C.c_double, _F, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_dec_posembed_hidden": (_I, [_P, _L, _I, _P, _P, _I, _P, _P]),
+    "ptx_dec_posembed_bwd": (_I, [_P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "ptx_dec_boxes_bwd": (_I, [_P, _P, _P, _I, _L, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_dec_scores_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ptx_gl_iou": (_I, [_P, _I, _P, _I, _P, _P]),
     "ptx_gl_cost": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _P, _P]),
     "ptx_gl_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _F, _F, _P, _F, _F, _P, _P, _P, _P]),

@@ -17,13 +17,14 @@ Parity-unpinned against ``nn.MultiheadAttention``: a masked key is never read (a
 by a zero weight).  A query whose every key is masked gets zeros from the attention, so the layer adds ``out_proj.bias`` only: what torch
 2.10 gives in both grad modes; older releases give NaN.
 
-Under autograd: ``attention``, ``linear``, ``layer_norm`` and ``linear_add_ln`` take ``differentiable=True`` and are then one
-``torch.autograd.Function`` node each (``linear_add_ln``: two), with the same forward bits, gradients specified by
-``decoder_grad_host.py``, no synchronise and no atomics: the body of a decoder layer trains.  Without the keyword they detach their
-operands as before.
+Under autograd: ``attention``, ``linear``, ``layer_norm``, ``linear_add_ln``, ``posembed`` (with its BatchNorm in training mode: batch
+statistics), ``boxes`` and ``contrastive_scores`` take ``differentiable=True`` and are then one ``torch.autograd.Function`` node each
+(``linear_add_ln``: two), with the same forward bits, gradients specified by ``decoder_grad_host.py``, no synchronise and no atomics.
+``GroundingDecoder(..., differentiable=True)`` in ``.train()`` runs the chain built from them: a loss on the hidden states and boxes
+reaches ``query``, ``key``, ``text_feats``, every parameter the reference trains and the regression branches.  Without the keyword
+they detach their operands as before and the module is the eval forward.
 
-Out of scope: ``GroundingDecoder(differentiable=True)`` (its ``forward`` stays under ``no_grad``), the backward of ``posembed`` (a
-training-mode BatchNorm), of ``boxes`` and of ``contrastive_scores``, double backward, dropout, attention masks, bf16, ``num_reg=12`` and
+Out of scope: training through frozen BatchNorms, double backward, dropout, attention masks, bf16, ``num_reg=12`` and
 the FCAF coder, the loss and ``predict_by_feat``.  There is no CPU path: tensors must be on the GPU and the library must be built."""
 from __future__ import annotations
 
@@ -37,9 +38,9 @@ from torch.autograd.function import once_differentiable
 from . import _abi, decoder_host, query_select
 from . import train as _train_ops
 from .query_select import QuerySelect
-from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _gpu, _mask_bytes, _np, _ptr, _stream, _wants_grad, _width
+from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _mask_bytes, _np, _ptr, _stream, _wants_grad, _width
 
-__all__ = ["GroundingDecoder", "attention", "boxes", "contrastive_scores", "layer_norm", "linear", "linear_add_ln", "posembed"]
+__all__ = ["GroundingDecoder", "attention", "boxes", "contrastive_scores", "layer_norm", "linear", "linear_add_ln", "posembed", "posembed_folded"]
 
 MAX_CIN, MAX_COUT, MAX_FFN = 2048, 4096, 2048
 LN_EPS = 1e-5
@@ -71,10 +72,29 @@ def _fold(module, dev) -> _Folded:
     return _Folded(head, dev)
 
 
-def posembed(x: torch.Tensor, module) -> torch.Tensor:
+def _posembed_head(module) -> nn.Sequential:
+    return module.position_embedding_head if hasattr(module, "position_embedding_head") else module
+
+
+def posembed(x: torch.Tensor, module, differentiable: bool = False, repeat: int = 1) -> torch.Tensor:
     """``(B,N,C) fp32``: ``PositionEmbeddingLearned`` in eval on ``x (B,N,cin)``, ``cin`` 1 to 9 -- Conv1d, the BatchNorm folded into it,
     ReLU (a NaN kept), Conv1d (``decoder_host.posembed_host``; ``ptx_dec_posembed``, one launch).  ``module``: the reference's module
-    (or its ``position_embedding_head``)."""
+    (or its ``position_embedding_head``).  ``differentiable=True`` with the BatchNorm in training mode: batch statistics over all ``B N``
+    rows (``decoder_grad_host.posembed_train_host``; ``ptx_dec_posembed_stats`` folds them on the device, then the same launch), the
+    running statistics moved ``repeat`` times and ``num_batches_tracked`` advanced by ``repeat``; one autograd node with gradients to the
+    six parameters, none to ``x`` (an ``x`` that requires grad is refused).  In eval with a parameter that requires grad it raises: a
+    frozen BatchNorm is not trained through."""
+    if differentiable and not isinstance(module, _Folded):
+        head = _posembed_head(module)
+        conv1, bn, conv2 = head[0], head[1], head[3]
+        if bn.training:
+            if _wants_grad(x):
+                raise NotImplementedError("posembed: x requires grad; the position embedding passes no gradient to its coordinates (the "
+                                          "reference detaches them): detach x")
+            return _posembed_train(x, conv1, bn, conv2, int(repeat))
+        if _wants_grad(conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias):
+            raise NotImplementedError("posembed: differentiable=True with the BatchNorm in eval mode and a parameter that requires grad: "
+                                      "training through a frozen BatchNorm is not implemented; call .train() or freeze the parameters")
     _gpu("posembed", x)
     dev = x.device
     x = _f32(x, "posembed", dev)
@@ -88,6 +108,139 @@ def posembed(x: torch.Tensor, module) -> torch.Tensor:
         _abi.check(_abi.lib().ptx_dec_posembed(x.data_ptr(), B * N, f.cin, f.w1.data_ptr(), f.b1.data_ptr(), f.w2.data_ptr(),
                                                f.b2.data_ptr(), f.C, out.data_ptr(), _stream(dev)), "ptx_dec_posembed")
     return out
+
+
+def _slab_workspace(n: int, C: int, nv: int, dev) -> torch.Tensor:
+    """The doubles the row-slab reductions of ``csrc/decoder_train.hip`` take for ``nv`` values per channel."""
+    nbytes = int(_abi.lib().ptx_dec_train_workspace_bytes(n, C, nv))
+    if nbytes == 0:
+        raise ValueError(f"decoder: {n} rows of width {C} are outside the training operators' range (1 to 2^24 rows)")
+    return torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+
+
+def _posembed_train(x, conv1, bn, conv2, repeat: int) -> torch.Tensor:
+    """``posembed``'s checks on the training path, all before the first launch."""
+    _gpu("posembed", x, conv1.weight)
+    dev = x.device
+    cin, C = int(conv1.in_channels), _width("posembed", conv1.out_channels)
+    if x.dim() != 3 or x.shape[2] != cin or not 1 <= cin <= 9:
+        raise ValueError(f"posembed: x (B,N,{cin}) with cin from 1 to 9 expected, got {tuple(x.shape)}")
+    n = int(x.shape[0]) * int(x.shape[1])
+    if n == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {[1, C, 1]}")
+    if not 1 <= repeat <= 64:
+        raise ValueError(f"posembed: repeat must be 1 to 64, got {repeat}")
+    if bn.momentum is None or not bn.affine:
+        raise NotImplementedError("posembed: a BatchNorm with momentum=None (cumulative average) or without affine parameters is not "
+                                  "implemented")
+    if bn.track_running_stats:
+        for t in (bn.running_mean, bn.running_var):
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"posembed: the running statistics must be contiguous fp32 on {dev}")
+    if n == 0:
+        return torch.empty((int(x.shape[0]), int(x.shape[1]), C), dtype=torch.float32, device=dev)
+    return _PosembedTrainFn.apply(x, conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias, bn, repeat)
+
+
+def _fold_batch(x, n: int, w1, b1, gamma, beta, bn, repeat: int):
+    """``ptx_dec_posembed_stats`` on fp32 operands: ``(w1' (C,cin), b1' (C), stats (2,C) = (mean | rstd))`` of the ``n`` rows of ``x``;
+    with ``repeat > 0`` the BatchNorm's running statistics move ``repeat`` times and ``num_batches_tracked`` advances by ``repeat``."""
+    dev = x.device
+    C, cin = int(w1.shape[0]), int(w1.shape[1])
+    w1f, b1f = torch.empty((C, cin), dtype=torch.float32, device=dev), torch.empty((C,), dtype=torch.float32, device=dev)
+    stats = torch.empty((2, C), dtype=torch.float32, device=dev)
+    ws = _slab_workspace(n, C, 2, dev)
+    track = bool(bn.track_running_stats) and repeat > 0
+    _abi.check(_abi.lib().ptx_dec_posembed_stats(x.data_ptr(), n, cin, w1.data_ptr(), b1.data_ptr(), gamma.data_ptr(), beta.data_ptr(), C,
+                                                 float(bn.eps), float(bn.momentum), repeat, _ptr(bn.running_mean if track else None),
+                                                 _ptr(bn.running_var if track else None), w1f.data_ptr(), b1f.data_ptr(), stats.data_ptr(),
+                                                 ws.data_ptr(), ws.numel() * 8, _stream(dev)), "ptx_dec_posembed_stats")
+    if track:
+        torch.autograd.graph.increment_version(bn.running_mean)      # the kernel wrote them: the prepared eval operands are keyed on this
+        torch.autograd.graph.increment_version(bn.running_var)
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(repeat)
+    return w1f, b1f, stats
+
+
+def posembed_folded(x: torch.Tensor, module) -> _Folded:
+    """The operands ``posembed``'s training forward hands to its ``ptx_dec_posembed`` launch: the BatchNorm's batch statistics over the
+    rows of ``x`` and its affine folded into the first Conv1d on the device.  Moves no running statistics.  ``posembed(x, <this>)`` is
+    the training forward's result bit for bit."""
+    _gpu("posembed", x)
+    dev = x.device
+    head = _posembed_head(module)
+    conv1, bn, conv2 = head[0], head[1], head[3]
+    x = _f32(x, "posembed", dev)
+    n = x.numel() // int(conv1.in_channels)
+    if n < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got {n} rows")
+    f = _Folded.__new__(_Folded)
+    f.cin, f.C = int(conv1.in_channels), _width("posembed", conv1.out_channels)
+    put = lambda t: _f32(t, "posembed", dev)      # noqa: E731
+    f.w1, f.b1, _ = _fold_batch(x, n, put(conv1.weight), put(conv1.bias), put(bn.weight), put(bn.bias), bn, 0)
+    f.w2, f.b2 = put(conv2.weight).reshape(f.C, f.C), put(conv2.bias)
+    return f
+
+
+class _PosembedTrainFn(torch.autograd.Function):
+    """``posembed`` with batch statistics as one node.  Forward: ``ptx_dec_posembed_stats`` (the moments of ``z = x W1^T + b1`` over
+    row slabs, merged by Chan's formula in double; the fold; the running statistics) and ``ptx_dec_posembed`` on the folded first
+    layer -- the hidden tensor never exists.  Saved: ``x``, the parameters, ``(mean, rstd)`` and the folded ``(w1', b1')`` (``C (cin +
+    1)`` floats, so that the backward's ReLU mask is the forward's).  Backward: the hidden tensor recomputed
+    (``ptx_dec_posembed_hidden``), ``dW2 = dout^T h`` and ``dh = dout W2`` (``ptx_op_gemm``), ``db2`` (``ptx_op_colsum``), the rest in
+    ``ptx_dec_posembed_bwd``."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, gamma, beta, w2, b2, bn, repeat):
+        dev = x.device
+        C, cin = int(w1.shape[0]), int(w1.shape[1])
+        B, N = int(x.shape[0]), int(x.shape[1])
+        n = B * N
+        ctx.meta = [(tuple(t.shape), t.dtype) for t in (w1, b1, gamma, beta, w2, b2)]
+        x = _f32(x, "posembed", dev)
+        w1, b1, gamma, beta = (_f32(t, "posembed", dev) for t in (w1, b1, gamma, beta))
+        w2, b2 = _f32(w2, "posembed", dev), _f32(b2, "posembed", dev)
+        w1f, b1f, stats = _fold_batch(x, n, w1, b1, gamma, beta, bn, repeat)
+        out = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+        _abi.check(_abi.lib().ptx_dec_posembed(x.data_ptr(), n, cin, w1f.data_ptr(), b1f.data_ptr(), w2.data_ptr(), b2.data_ptr(), C,
+                                               out.data_ptr(), _stream(dev)), "ptx_dec_posembed")
+        ctx.save_for_backward(x, w1, b1, gamma, w2, stats, w1f, b1f)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        x, w1, b1, gamma, w2, stats, w1f, b1f = ctx.saved_tensors
+        dev = x.device
+        C, cin = int(w1.shape[0]), int(w1.shape[1])
+        n = x.numel() // cin
+        lib = _abi.lib()
+        g = _f32(dout, "posembed", dev).view(n, C)
+        need = ctx.needs_input_grad[1:7]
+        grads = [None] * 6
+        with torch.cuda.device(dev):
+            w2m = w2.view(C, C)
+            if need[4]:
+                h = torch.empty((n, C), dtype=torch.float32, device=dev)
+                _abi.check(lib.ptx_dec_posembed_hidden(x.data_ptr(), n, cin, w1f.data_ptr(), b1f.data_ptr(), C, h.data_ptr(), _stream(dev)),
+                           "ptx_dec_posembed_hidden")
+                dw2 = torch.empty((C, C), dtype=torch.float32, device=dev)
+                _dweight_rows(g, 0, C, h, dw2)
+                grads[4] = dw2
+            if need[5]:
+                grads[5] = _train_ops.colsum(g)
+            if any(need[:4]):
+                dh = _train_ops.mm(g, w2m)
+                dgb = torch.empty((2, C), dtype=torch.float32, device=dev)
+                dw1, db1 = torch.empty((C, cin), dtype=torch.float32, device=dev), torch.empty((C,), dtype=torch.float32, device=dev)
+                ws = _slab_workspace(n, C, max(cin + 1, 2), dev)
+                _abi.check(lib.ptx_dec_posembed_bwd(x.data_ptr(), n, cin, w1.data_ptr(), b1.data_ptr(), gamma.data_ptr(), stats.data_ptr(),
+                                                    w1f.data_ptr(), b1f.data_ptr(), dh.data_ptr(), C, dgb.data_ptr(), dw1.data_ptr(),
+                                                    db1.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(dev)), "ptx_dec_posembed_bwd")
+                grads[0], grads[1], grads[2], grads[3] = dw1, db1, dgb[1], dgb[0]
+        out = [g_.reshape(shape).to(dt) if (g_ is not None and wanted) else None for g_, (shape, dt), wanted in zip(grads, ctx.meta, need)]
+        return (None,) + tuple(out) + (None, None)
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], add: Optional[torch.Tensor] = None, relu: bool = False,
@@ -427,10 +580,17 @@ def linear_add_ln(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Te
 
 
 def boxes(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], coords: torch.Tensor,
-          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+          out: Optional[torch.Tensor] = None, differentiable: bool = False) -> torch.Tensor:
     """``(B,K,9)``: the last Linear ``weight (9,C)`` of a regression branch on ``h (B,K,C)`` and the baseline decode against
     ``coords (B,K,3)`` -- ``center = p[0:3] + coords``, ``size = max(expf(p[3:6]), 0.02)`` with a NaN kept, ``euler = p[6:9]``
-    (``query_select_host.boxes_host``; ``ptx_dec_boxes``, one launch)."""
+    (``query_select_host.boxes_host``; ``ptx_dec_boxes``, one launch).  ``differentiable=True``: one autograd node with gradients to
+    ``h``, ``weight`` and ``bias`` (none to ``coords``), the same forward bits (``decoder_grad_host.boxes_bwd_host``;
+    ``ptx_dec_boxes_bwd``); ``out`` is refused there."""
+    if differentiable:
+        if out is not None:
+            raise ValueError("boxes: out cannot be given with differentiable=True (an in-place slot cannot be a graph output)")
+        if _wants_grad(h, weight, bias):
+            return _BoxesFn.apply(h, weight, bias, coords)
     _gpu("boxes", h, weight, bias, coords)
     dev = h.device
     h, weight, bias, coords = _f32(h, "boxes", dev), _f32(weight, "boxes", dev), _f32(bias, "boxes", dev), _f32(coords, "boxes", dev)
@@ -449,11 +609,57 @@ def boxes(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], c
     return out
 
 
+class _BoxesFn(torch.autograd.Function):
+    """``boxes`` as one node.  Saved: ``h``, ``weight``, ``bias``; the log-sizes are recomputed (a saved size of 0.02 does not say on which
+    side of the clamp it was).  ``ptx_dec_boxes_bwd`` writes ``dp``, ``dh = dp W`` and ``dW = dp^T h`` (row slabs in double, ascending);
+    ``dbias = colsum(dp)`` in double (``ptx_op_colsum``)."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, coords):
+        res = boxes(h, weight, bias, coords)
+        dev = res.device
+        ctx.meta = [(None, None) if t is None else (tuple(t.shape), t.dtype) for t in (h, weight, bias)]
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(*(_f32(t, "boxes", dev) for t in ((h, weight, bias) if ctx.has_bias else (h, weight))))
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dboxes):
+        saved = ctx.saved_tensors
+        h, w = saved[0], saved[1]
+        bias = saved[2] if ctx.has_bias else None
+        dev = h.device
+        C = int(h.shape[-1])
+        n = h.numel() // C
+        need = ctx.needs_input_grad[:3]
+        if n == 0:
+            grads = [None if shape is None else torch.zeros(shape, dtype=dt, device=dev) for shape, dt in ctx.meta]
+            return tuple(g if wanted else None for g, wanted in zip(grads, need)) + (None,)
+        d = _f32(dboxes, "boxes", dev)
+        dh, dp = torch.empty_like(h), torch.empty((n, 9), dtype=torch.float32, device=dev)
+        dw = torch.empty((9, C), dtype=torch.float32, device=dev)
+        ws = _slab_workspace(n, C, 9, dev)
+        _abi.check(_abi.lib().ptx_dec_boxes_bwd(h.data_ptr(), w.data_ptr(), _ptr(bias), C, n, d.data_ptr(), dh.data_ptr(), dp.data_ptr(),
+                                                dw.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream(dev)), "ptx_dec_boxes_bwd")
+        grads = [dh, dw, None]
+        if ctx.has_bias and need[2]:
+            with torch.cuda.device(dev):
+                grads[2] = _train_ops.colsum(dp)
+        out = [g.reshape(shape).to(dt) if (g is not None and wanted) else None for g, (shape, dt), wanted in zip(grads, ctx.meta, need)]
+        return tuple(out) + (None,)
+
+
 def contrastive_scores(hidden_states: torch.Tensor, text_feats: torch.Tensor, text_token_mask: torch.Tensor,
-                       bias: Optional[torch.Tensor] = None, scaled: bool = True, max_text_len: int = 256) -> torch.Tensor:
+                       bias: Optional[torch.Tensor] = None, scaled: bool = True, max_text_len: int = 256,
+                       differentiable: bool = False) -> torch.Tensor:
     """``(NL,B,K,max_text_len) fp32``: ``ContrastiveEmbed`` in full on every layer's ``hidden_states (NL,B,K,C)`` --
     ``hidden . text[b,t] (/ sqrtf(C)) (+ bias)`` on the tokens with ``text_token_mask[b,t]``, ``-inf`` on masked tokens and on the columns
-    from ``T`` on (``decoder_host.contrastive_scores_host``; ``ptx_dec_scores``, one launch)."""
+    from ``T`` on (``decoder_host.contrastive_scores_host``; ``ptx_dec_scores``, one launch).  ``differentiable=True``: one autograd node
+    with gradients to ``hidden_states``, ``text_feats`` and the scalar ``bias``, the same forward bits; the incoming gradient under a
+    masked token or from column ``T`` on is never read (``decoder_grad_host.scores_bwd_host``; ``ptx_dec_scores_bwd``)."""
+    if differentiable and _wants_grad(hidden_states, text_feats, bias):
+        return _ScoresFn.apply(hidden_states, text_feats, text_token_mask, bias, bool(scaled), int(max_text_len))
     _gpu("contrastive_scores", hidden_states, text_feats, text_token_mask, bias)
     dev = hidden_states.device
     hs, text, bias = _f32(hidden_states, "contrastive_scores", dev), _f32(text_feats, "contrastive_scores", dev), \
@@ -473,6 +679,47 @@ def contrastive_scores(hidden_states: torch.Tensor, text_feats: torch.Tensor, te
         _abi.check(_abi.lib().ptx_dec_scores(hs.data_ptr(), NL, B, K, C, text.data_ptr(), mask.data_ptr(), T, M, int(bool(scaled)), _ptr(bias),
                                              out.data_ptr(), _stream(dev)), "ptx_dec_scores")
     return out
+
+
+class _ScoresFn(torch.autograd.Function):
+    """``contrastive_scores`` as one node.  Saved: ``hidden_states``, ``text_feats`` and the mask.  ``ptx_dec_scores_bwd``: two launches on
+    the exact-fp32 matrix instruction (``dhidden`` over the tokens, ``dtext`` over ``layer * K + query`` ascending) and, with a bias, its
+    sum per (layer, scene) in double, then ascending."""
+
+    @staticmethod
+    def forward(ctx, hidden_states, text_feats, text_token_mask, bias, scaled, max_text_len):
+        out = contrastive_scores(hidden_states, text_feats, text_token_mask, bias, scaled, max_text_len)
+        dev = out.device
+        ctx.scaled, ctx.M, ctx.has_bias = scaled, max_text_len, bias is not None
+        ctx.meta = [(None, None) if t is None else (tuple(t.shape), t.dtype) for t in (hidden_states, text_feats, bias)]
+        B, T = int(text_feats.shape[0]), int(text_feats.shape[1])
+        ctx.save_for_backward(_f32(hidden_states, "contrastive_scores", dev), _f32(text_feats, "contrastive_scores", dev),
+                              _mask_bytes("contrastive_scores", "the mask", text_token_mask, (B, T)))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dscores):
+        hs, text, mask = ctx.saved_tensors
+        dev = hs.device
+        NL, B, K, C = (int(s) for s in hs.shape)
+        T = int(text.shape[1])
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3])
+        if NL * K == 0:
+            grads = [None if shape is None else torch.zeros(shape, dtype=dt, device=dev) for shape, dt in ctx.meta]
+            g = tuple(x if wanted else None for x, wanted in zip(grads, need))
+            return g[0], g[1], None, g[2], None, None
+        ds = _f32(dscores, "contrastive_scores", dev)
+        dh, dt_ = torch.empty_like(hs), torch.empty_like(text)
+        want_bias = ctx.has_bias and need[2]
+        db = torch.empty((1,), dtype=torch.float32, device=dev) if want_bias else None
+        ws = torch.empty((NL * B,), dtype=torch.float64, device=dev) if want_bias else None
+        _abi.check(_abi.lib().ptx_dec_scores_bwd(ds.data_ptr(), hs.data_ptr(), NL, B, K, C, text.data_ptr(), mask.data_ptr(), T, ctx.M,
+                                                 int(ctx.scaled), dh.data_ptr(), dt_.data_ptr(), _ptr(db), _ptr(ws),
+                                                 0 if ws is None else ws.numel() * 8, _stream(dev)), "ptx_dec_scores_bwd")
+        out = [g.reshape(shape).to(dt) if (g is not None and wanted) else None
+               for g, (shape, dt), wanted in zip((dh, dt_, db), ctx.meta, need)]
+        return out[0], out[1], None, out[2], None, None
 
 
 # ------------------------------------------------------------------------------------------------------------------ the module
@@ -548,15 +795,23 @@ class GroundingDecoder(nn.Module):
     Accepted: ``embed_dims`` a multiple of 64 from 64 to 512, head dimension 32 or 64, ``feedforward_channels`` a multiple of 64 up to
     2048, ``1 <= B <= 64``, ``0 <= K <= 1024``, ``1 <= T <= 256``; ``K = 0`` or ``Lmax = 0`` returns correctly shaped empties and launches
     nothing.  Refused: ``post_norm_cfg`` (ValueError, as in the reference), attention masks and ``value is not key``
-    (NotImplementedError), training mode or an input that requires grad with grad mode on (NotImplementedError), ``bbox_head=None``
-    (ValueError; the reference fails on an undefined name there).
+    (NotImplementedError), training mode or an input that requires grad with grad mode on (NotImplementedError; both are accepted with
+    ``differentiable=True``, below), ``bbox_head=None`` (ValueError; the reference fails on an undefined name there).
+
+    ``differentiable=True`` (stored as ``self.differentiable``): in ``.train()`` the forward is the training path (``_run_train``) --
+    batch statistics in both position embeddings, ``cross_posembed`` once with ``repeat=num_layers``, the boxes detached between layers,
+    no gradient to ``key_coords``, ``query_coords`` or ``pred_bboxes``; the hidden Linears of a regression branch run through
+    ``linear(relu=True)``, whose summation order differs from the eval path's ``query_select.linear``, so this path is held to float64
+    and not to the eval bits.  In ``.eval()`` it is the eval forward, and raises when an input requires grad (frozen BatchNorms).
 
     The operands the launches take (concatenated projections, folded position embeddings) are prepared once and rebuilt when a parameter
     or buffer is replaced or its ``_version`` changes (``load_state_dict``, in-place updates).  A write through ``.data`` bumps no
     version and is not seen: move the module (``.to``) or write in place under ``no_grad`` instead."""
 
-    def __init__(self, num_layers: int, layer_cfg: dict, post_norm_cfg=None, return_intermediate: bool = True, init_cfg=None, with_cp=None):
+    def __init__(self, num_layers: int, layer_cfg: dict, post_norm_cfg=None, return_intermediate: bool = True, init_cfg=None, with_cp=None,
+                 differentiable: bool = False):
         super().__init__()
+        self.differentiable = bool(differentiable)
         self.layer_cfg, self.num_layers = layer_cfg, int(num_layers)
         self.post_norm_cfg, self.return_intermediate, self.with_cp = post_norm_cfg, bool(return_intermediate), with_cp
         if not 1 <= self.num_layers <= 64:
@@ -644,10 +899,17 @@ class GroundingDecoder(nn.Module):
         tensors = [query, key, key_padding_mask, query_coords, key_coords, pred_bboxes, text_feats, text_attention_mask]
         if not all(isinstance(t, torch.Tensor) for t in tensors):
             raise TypeError("GroundingDecoder: the operands must be tensors")
-        if self.training:
-            raise NotImplementedError("GroundingDecoder: the eval forward only; call .eval() (training through the decoder is not implemented)")
-        if torch.is_grad_enabled() and any(t.is_floating_point() and t.requires_grad for t in tensors):
-            raise NotImplementedError("GroundingDecoder is inference-only: an input requires grad; call it under torch.no_grad() or detach")
+        wanted = torch.is_grad_enabled() and any(t.is_floating_point() and t.requires_grad for t in tensors)
+        if not self.differentiable:
+            if self.training:
+                raise NotImplementedError("GroundingDecoder: the eval forward only; call .eval() (training through the decoder is not "
+                                          "implemented)")
+            if wanted:
+                raise NotImplementedError("GroundingDecoder is inference-only: an input requires grad; call it under torch.no_grad() or detach")
+        elif not self.training and wanted:
+            raise NotImplementedError("GroundingDecoder(differentiable=True) in eval mode: an input requires grad, and training through the "
+                                      "frozen BatchNorms of the position embeddings is not implemented; call .train(), or call it under "
+                                      "torch.no_grad() / detach the inputs for the eval forward")
         C = self.embed_dims
         if query.dim() != 3 or query.shape[2] != C:
             raise ValueError(f"GroundingDecoder: query (B,K,{C}) expected, got {tuple(query.shape)}")
@@ -679,6 +941,10 @@ class GroundingDecoder(nn.Module):
             if self.return_intermediate:
                 return (torch.zeros((NL, B, K, C), dtype=torch.float32, device=dev), torch.zeros((NL, B, K, 9), dtype=torch.float32, device=dev))
             return torch.zeros((B, K, C), dtype=torch.float32, device=dev), torch.zeros((B, K, 9), dtype=torch.float32, device=dev)
+        if self.differentiable and self.training:
+            return self._run_train(branches, _f32_grad(query), _f32_grad(key), key_padding_mask, _f32(query_coords, "GroundingDecoder", dev),
+                                   _f32(key_coords, "GroundingDecoder", dev), _f32(pred_bboxes, "GroundingDecoder", dev),
+                                   _f32_grad(text_feats), text_attention_mask)
         with torch.no_grad():
             return self._run(branches, _f32(query, "GroundingDecoder", dev), _f32(key, "GroundingDecoder", dev), key_padding_mask,
                              _f32(query_coords, "GroundingDecoder", dev), _f32(key_coords, "GroundingDecoder", dev),
@@ -738,11 +1004,84 @@ class GroundingDecoder(nn.Module):
             return hidden, all_boxes
         return query, bboxes
 
-    def head_scores(self, hidden_states: torch.Tensor, head_inputs_dict: dict, query_select: QuerySelect) -> torch.Tensor:
-        """``GroundingHead.forward``'s ``all_layers_cls_scores (NL,B,K,max_text_len)`` with the ``QuerySelect``'s ``cls_branch``."""
+    def _run_train(self, branches, query, key, pad, qcoords, kcoords, bboxes, text, tmask):
+        """The training path: the chain of ``_run`` built only from the differentiable operators, with the live parameters as the
+        autograd leaves (``_prepare``'s cache, keyed on versions that every optimiser step bumps, is not used).  The position embeddings
+        take batch statistics; ``cross_posembed`` runs once with ``repeat=NL`` (the reference calls it per layer on the same rows).  The
+        hoisted key/value projection stays one launch per group of layers on a ``torch.cat`` of the live weight slices (autograd's slice
+        backward hands each layer its rows).  The hidden Linears of a regression branch are ``linear(relu=True)`` -- straight
+        accumulation, where the eval path's ``query_select.linear`` adds per 64-wide block: this path is held to float64, not to the
+        eval bits.  The boxes carry a gradient to the regression branch and ``query``; they are detached before they become the next
+        layer's ``pred_bboxes``, as are the coordinates."""
+        dev, C, NL = query.device, self.embed_dims, self.num_layers
+        B, K, T = int(query.shape[0]), int(query.shape[1]), int(text.shape[1])
+        pad = _mask_bytes("GroundingDecoder", "the mask", pad, tuple(key.shape[:2]))
+        tmask = _mask_bytes("GroundingDecoder", "the mask", tmask, (B, T))
+        text_keys_take_pos = T == K                          # mmcv: key_pos = query_pos when the shapes agree
+        key_pos = posembed(kcoords, self.cross_posembed, differentiable=True, repeat=NL)
+        group = max(1, MAX_COUT // (2 * C))
+        scene_kv, text_kv = {}, {}
+        for lo in range(0, NL, group):
+            ids = list(range(lo, min(lo + group, NL)))
+            n = len(ids)
+            for name, store in (("cross_attn", scene_kv), ("cross_attn_text", text_kv)):
+                if name == "cross_attn_text" and text_keys_take_pos:
+                    continue
+                ws = [getattr(self.layers[i], name).attn.in_proj_weight for i in ids]
+                bs = [getattr(self.layers[i], name).attn.in_proj_bias for i in ids]
+                w = torch.cat([w_[C:2 * C] for w_ in ws] + [w_[2 * C:] for w_ in ws])
+                b = torch.cat([b_[C:2 * C] for b_ in bs] + [b_[2 * C:] for b_ in bs])
+                if name == "cross_attn":
+                    kv = linear(key, w, b, add=key_pos, add_cols=n * C, differentiable=True)
+                else:
+                    kv = linear(text, w, b, differentiable=True)
+                for j, lid in enumerate(ids):
+                    store[lid] = (kv[:, :, j * C:(j + 1) * C], kv[:, :, (n + j) * C:(n + j + 1) * C])
+        hidden, all_boxes = [], []
+        for lid, layer in enumerate(self.layers):
+            query_pos = posembed(bboxes, self.self_posembed, differentiable=True)
+            a, H = layer.self_attn.attn, layer.self_attn.num_heads
+            qkv = linear(query, a.in_proj_weight, a.in_proj_bias, add=query_pos, add_cols=2 * C, differentiable=True)
+            o = attention(qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:], None, H, differentiable=True)
+            query = linear_add_ln(o, a.out_proj.weight, a.out_proj.bias, query, layer.norms[0], differentiable=True)
+            a, H = layer.cross_attn_text.attn, layer.cross_attn_text.num_heads
+            q = linear(query, a.in_proj_weight[:C], a.in_proj_bias[:C], add=query_pos, differentiable=True)
+            if text_keys_take_pos:
+                kv = linear(text, a.in_proj_weight[C:], a.in_proj_bias[C:], add=query_pos, add_cols=C, differentiable=True)
+                tk, tv = kv[:, :, :C], kv[:, :, C:]
+            else:
+                tk, tv = text_kv[lid]
+            query = linear_add_ln(attention(q, tk, tv, tmask, H, differentiable=True), a.out_proj.weight, a.out_proj.bias, query,
+                                  layer.norms[1], differentiable=True)
+            a, H = layer.cross_attn.attn, layer.cross_attn.num_heads
+            q = linear(query, a.in_proj_weight[:C], a.in_proj_bias[:C], add=query_pos, differentiable=True)
+            query = linear_add_ln(attention(q, *scene_kv[lid], pad, H, differentiable=True), a.out_proj.weight, a.out_proj.bias, query,
+                                  layer.norms[2], differentiable=True)
+            fc1, fc2 = layer.ffn.layers[0][0], layer.ffn.layers[1]
+            h = linear(query, fc1.weight, fc1.bias, relu=True, differentiable=True)
+            if self.return_intermediate:
+                query, hid = linear_add_ln(h, fc2.weight, fc2.bias, query, layer.norms[3], self.norm, differentiable=True)
+                hidden.append(hid)
+            else:
+                query = linear_add_ln(h, fc2.weight, fc2.bias, query, layer.norms[3], differentiable=True)
+            lins = branches[lid]
+            h = query
+            for lin in lins[:-1]:
+                h = linear(h, lin.weight, lin.bias, relu=True, differentiable=True)
+            new_boxes = boxes(h, lins[-1].weight, lins[-1].bias, qcoords, differentiable=True)
+            all_boxes.append(new_boxes)
+            bboxes = new_boxes.detach()
+        if self.return_intermediate:
+            return torch.stack(hidden), torch.stack(all_boxes)
+        return query, new_boxes
+
+    def head_scores(self, hidden_states: torch.Tensor, head_inputs_dict: dict, query_select: QuerySelect,
+                    differentiable: bool = False) -> torch.Tensor:
+        """``GroundingHead.forward``'s ``all_layers_cls_scores (NL,B,K,max_text_len)`` with the ``QuerySelect``'s ``cls_branch``;
+        ``differentiable=True``: ``contrastive_scores`` under autograd."""
         qs = query_select
         return contrastive_scores(hidden_states, head_inputs_dict["text_feats"], head_inputs_dict["text_token_mask"],
-                                  qs.cls_branch.bias if qs.has_bias else None, qs.scaled, qs.max_text_len)
+                                  qs.cls_branch.bias if qs.has_bias else None, qs.scaled, qs.max_text_len, differentiable=differentiable)
 
     def forward_host(self, query, key, key_padding_mask, query_coords, key_coords, pred_bboxes, text_feats, text_attention_mask, bbox_head,
                      dtype=np.float64, **kw):

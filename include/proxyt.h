@@ -815,6 +815,15 @@ PTX_API int ptx_gl_loss_bwd(const float *scores, const float *boxes, int NL, int
                             const float *g_box, const int32_t *counts, float *dscores, float *dboxes, void *stream);
 /* out (n) = max_t sigmoid(scores[r,t]) over all M columns of scores (n,M): a -inf column gives 0, a NaN gives NaN.  One launch. */
 PTX_API int ptx_gl_predict(const float *scores, long n, int M, float *out, void *stream);
+/* assign (NL,B,K) int32 = the minimum-cost matching of every (layer, scene): the index of query k's box within its scene, -1 for an
+ * unmatched query and for every query of a scene without a box.  cost (NL,K,SG) as ptx_gl_cost leaves it (a NaN or +inf entry counts as
+ * 100, -inf as -100); scene b's K x G_b matrix is the columns gt_offset[b] .. gt_offset[b+1] - 1 (gt_offset (B+1) on the device); max_g
+ * = the host's max_b G_b.  The rectangular shortest-augmenting-path method in double, one wave per problem; min(K, G_b) pairs; among
+ * columns of equal smallest path cost the lowest index is taken (grounding_loss_host.sap_assign_host is the specification, bit for bit).
+ * Limits: min(K, max_g) <= 256, max(K, max_g) <= 1024.  A scene whose offsets are not 0 <= lo <= hi <= SG with hi - lo <= max_g reads
+ * nothing and gets -1.  assign is written entirely (no memset needed).  One launch; added without a change of the ABI version. */
+PTX_API int ptx_gl_assign(const float *cost, int NL, int B, int K, const int32_t *gt_offset, int SG, int max_g, int32_t *assign,
+                          void *stream);
 
 /* ------------------------------------------------------------------ image feature -> point sampling
  * batch_point_sample (models/layers/fusion_layers/point_fusion.py:208-313) as called at detectors/

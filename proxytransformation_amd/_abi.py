@@ -231,6 +231,7 @@ SIGNATURES.update({
     "ptx_gl_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _F, _F, _P, _F, _F, _P, _P, _P, _P]),
     "ptx_gl_loss_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _F, _F, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
     "ptx_gl_predict": (_I, [_P, _L, _I, _P, _P]),
+    "ptx_gl_assign": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "ptx_point_sample_workspace_bytes": (_Z, [_I, _I, _I, _I]),
     "ptx_point_sample_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),

@@ -3,16 +3,21 @@
 ``contrastive_scores``' ``(NL,B,K,max_text_len)`` with ``-inf`` on masked tokens and behind ``T``, and ``GroundingDecoder``'s
 ``(NL,B,K,9)`` boxes.
 
-Five calls into ``csrc/grounding_loss.hip`` on the current stream, each restated in numpy by ``grounding_loss_host.py``, which is their
-specification: ``box_iou3d`` (the IoU of two 9-DoF boxes; the reference takes it from pytorch3d's CUDA extension, which has no ROCm
-build), ``match_costs`` (every layer, scene, query and ground-truth box in ONE launch), the loss forward (two launches), its backward
-(one) and ``predict_scores``.  fp32 operands and results (the IoU's geometry between them runs in double: DESIGN.md 5.15); no float
-atomics and fixed summation orders, so two calls give the same bits.
+Six calls into ``csrc/grounding_loss.hip`` and ``csrc/grounding_assign.hip`` on the current stream, each restated in numpy by
+``grounding_loss_host.py``, which is their specification: ``box_iou3d`` (the IoU of two 9-DoF boxes; the reference takes it from
+pytorch3d's CUDA extension, which has no ROCm build), ``match_costs`` (every layer, scene, query and ground-truth box in ONE launch),
+the matching on the device (one), the loss forward (two launches), its backward (one) and ``predict_scores``.  fp32 operands and results
+(the IoU's geometry and the matching's duals between them run in double: DESIGN.md 5.15, 5.18); no float atomics and fixed summation
+orders, so two calls give the same bits.
 
-THE ONE SYNCHRONISE of the stage is in ``assign``: the cost matrices of all layers and scenes travel to the host in one copy through
-pinned memory, the stream is waited for once, ``scipy.optimize.linear_sum_assignment`` runs per (layer, scene) on
-``nan_to_num(cost, 100, 100, -100)``, and the assignment goes back in one copy.  The reference does this once per (layer, scene) -- 36
-round trips at 6 layers and 6 scenes -- and sleeps 20 ms before each (hungarian_assigner.py:120); there is no sleep here.
+THE ONE SYNCHRONISE of the stage is in ``assign`` with ``matcher='host'`` (the default): the cost matrices of all layers and scenes
+travel to the host in one copy through pinned memory, the stream is waited for once, ``scipy.optimize.linear_sum_assignment`` runs per
+(layer, scene) on ``nan_to_num(cost, 100, 100, -100)``, and the assignment goes back in one copy.  The reference does this once per
+(layer, scene) -- 36 round trips at 6 layers and 6 scenes -- and sleeps 20 ms before each (hungarian_assigner.py:120); there is no sleep
+here.  With ``matcher='device'`` the matching is one more launch (``ptx_gl_assign``: the same shortest-augmenting-path method, one wave
+per (layer, scene); ``grounding_loss_host.sap_assign_host`` is its specification, bit for bit) and the stage has NO synchronise: cost,
+matching, loss and backward are enqueued without a host wait.  On a tie between optimal matchings the two matchers may pick different
+pairs.
 
 The loss is one autograd node ``(scores, boxes) -> (2,NL)``; the matching sees detached values.  Deviations from the reference: a batch
 without any ground-truth box raises ``ValueError`` before anything is launched (the reference takes the mean of nothing: NaN); a masked
@@ -20,7 +25,7 @@ token is never read (the reference multiplies by a mask).  Unpinned: mmdet's foc
 not installed), and pytorch3d's IoU on degenerate pairs (coplanar faces, zero sizes) is not reproduced -- ``grounding_loss_host.py``
 states this project's rule.
 
-Out of scope: matching on the device, denoising queries, bf16, double backward, ``norm_decouple_loss``, ``decouple_groups=3``, the
+Out of scope: denoising queries, bf16, double backward, ``norm_decouple_loss``, ``decouple_groups=3``, the
 ``g4`` corner grouping, ``num_reg=12`` and the FCAF coder.  There is no CPU path: tensors must be on the GPU and the library must be
 built."""
 from __future__ import annotations
@@ -33,6 +38,7 @@ import torch
 from torch import nn
 
 from . import _abi
+from .grounding_loss_host import SAP_MAX_COLS, SAP_MAX_ROWS
 from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _mask_bytes, _stream
 
 __all__ = ["GroundingLoss", "box_iou3d", "grounding_loss", "hungarian_assign", "match_costs", "predict_scores"]
@@ -134,18 +140,46 @@ def _solve(cost: np.ndarray, G: Sequence[int], B: int) -> np.ndarray:
     return out
 
 
+MATCHERS = ("host", "device")
+
+
+def _matcher(what: str, matcher: str, scores=None, gt_bboxes: Sequence = ()) -> str:
+    """``matcher`` checked; with the operands: the device solver's limits on every scene, from the shapes alone (before any launch)."""
+    if matcher not in MATCHERS:
+        raise ValueError(f"{what}: matcher must be 'host' or 'device', got {matcher!r}")
+    if matcher == "device" and scores is not None and scores.dim() == 4:
+        K = int(scores.shape[2])
+        for b, g in enumerate(gt_bboxes):
+            G = int((g.tensor if hasattr(g, "tensor") else g).shape[0])
+            if min(K, G) > SAP_MAX_ROWS or max(K, G) > SAP_MAX_COLS:
+                raise ValueError(f"{what}: matcher='device' takes min(K, G_b) <= {SAP_MAX_ROWS} and max(K, G_b) <= {SAP_MAX_COLS}, got K={K}, "
+                                 f"G_b={G} in scene {b}; use matcher='host'")
+    return matcher
+
+
 def hungarian_assign(scores: torch.Tensor, boxes: torch.Tensor, text_token_mask: torch.Tensor, gt_bboxes: Sequence[torch.Tensor],
                      positive_maps: Sequence[torch.Tensor], alpha: float = 0.25, gamma: float = 2.0, weights=(1.0, 2.0, 2.0),
-                     _targets: Optional[_Targets] = None) -> torch.Tensor:
+                     _targets: Optional[_Targets] = None, matcher: str = "host") -> torch.Tensor:
     """``assign (NL,B,K) int32`` on the device: the index of the matched ground-truth box within its scene, -1 for an unmatched query.
-    One launch, one device-to-host copy through pinned memory, ONE synchronise, scipy per (layer, scene), one copy back.  A scene without
-    a box assigns -1 everywhere; ``G_b > K`` matches ``K`` pairs."""
+    ``matcher='host'``: one launch, one device-to-host copy through pinned memory, ONE synchronise, scipy per (layer, scene), one copy
+    back.  ``matcher='device'``: two launches (``ptx_gl_cost``, ``ptx_gl_assign``), no copy and no synchronise; ``min(K, G_b) <= 256`` and
+    ``max(K, G_b) <= 1024`` in every scene, else ``ValueError``; the matching of ``grounding_loss_host.sap_assign_host``, which has
+    scipy's total cost and, off ties, scipy's pairs.  A scene without a box assigns -1 everywhere; ``G_b > K`` matches ``K`` pairs."""
+    _matcher("hungarian_assign", matcher, scores, gt_bboxes)
     with torch.no_grad():
+        if matcher == "device" and _targets is None and scores.dim() == 4:      # (the offsets of the second launch: built once)
+            _gpu("hungarian_assign", scores)
+            _targets = _Targets("hungarian_assign", gt_bboxes, positive_maps, int(scores.shape[1]), int(scores.shape[3]), scores.device)
         cost, G = match_costs(scores, boxes, text_token_mask, gt_bboxes, positive_maps, alpha, gamma, weights, _targets)
         dev, (NL, K, SG) = cost.device, cost.shape
         B = len(G)
         if K == 0 or SG == 0:
             return torch.full((NL, B, K), -1, dtype=torch.int32, device=dev)
+        if matcher == "device":
+            assign = torch.empty((NL, B, K), dtype=torch.int32, device=dev)
+            _abi.check(_abi.lib().ptx_gl_assign(cost.data_ptr(), NL, B, K, _targets.offset_ptr, SG, max(G), assign.data_ptr(), _stream(dev)),
+                       "ptx_gl_assign")
+            return assign
         host = torch.empty(cost.shape, dtype=torch.float32, pin_memory=True)
         host.copy_(cost, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()         # the stage's one synchronise
@@ -256,8 +290,10 @@ class GroundingLoss(nn.Module):
     ``loss(all_layers_cls_scores (NL,B,K,max_text_len), all_layers_pred_bboxes (NL,B,K,9), text_token_mask (B,T), gt_bboxes: list of
     (G_b,9), positive_maps: list of (G_b,max_text_len))`` returns the reference's dict: ``loss_cls``, ``loss_bbox`` (the last layer) and
     ``d{i}.loss_cls``, ``d{i}.loss_bbox`` for the layers ``0 .. NL-2``.  ``assign(...)`` (same arguments) returns the matching alone,
-    ``(NL,B,K) int32``.  ``predict(all_layers_cls_scores, all_layers_pred_bboxes)`` is ``predict_by_feat``: ``(bboxes_3d (B,K,9),
-    scores_3d (B,K))`` of the last layer.
+    ``(NL,B,K) int32``.  ``matcher`` (keyword only): ``'host'`` (the default: scipy behind the stage's one synchronise) or ``'device'``
+    (``ptx_gl_assign``: ``loss`` then enqueues cost, matching and loss and returns without a host wait; ``min(K, G_b) <= 256`` and
+    ``max(K, G_b) <= 1024``, else ``ValueError``).  ``predict(all_layers_cls_scores, all_layers_pred_bboxes)`` is ``predict_by_feat``:
+    ``(bboxes_3d (B,K,9), scores_3d (B,K))`` of the last layer.
 
     With ``sync_cls_avg_factor=True`` and ``torch.distributed`` initialised, the number of matched pairs is averaged over the ranks for
     the classification divisor, as ``reduce_mean`` does.  Raises ``NotImplementedError`` with the argument's name on what is not built:
@@ -268,9 +304,11 @@ class GroundingLoss(nn.Module):
                  box_coder: str = "baseline", sync_cls_avg_factor: bool = True, decouple_bbox_loss: bool = True, decouple_groups: int = 4,
                  decouple_weights: Optional[Sequence[float]] = (0.2, 0.2, 0.2, 0.4), norm_decouple_loss: bool = False,
                  loss_cls: Optional[dict] = None, loss_bbox: Optional[dict] = None, train_cfg: Optional[dict] = None,
-                 contrastive_cfg: Optional[dict] = None, share_pred_layer: bool = True, test_cfg=None, init_cfg=None):
+                 contrastive_cfg: Optional[dict] = None, share_pred_layer: bool = True, test_cfg=None, init_cfg=None, *,
+                 matcher: str = "host"):
         super().__init__()
         who = "GroundingLoss"
+        self.matcher = _matcher(who, matcher)
         if int(num_reg) == 12:
             raise NotImplementedError(f"{who}: num_reg=12 (the 6D rotation) is not implemented; num_reg=9")
         if int(num_reg) != 9:
@@ -337,12 +375,14 @@ class GroundingLoss(nn.Module):
         return _Targets("GroundingLoss", gt_bboxes, positive_maps, B, M, scores.device)
 
     def assign(self, all_layers_cls_scores, all_layers_pred_bboxes, text_token_mask, gt_bboxes, positive_maps, _targets=None) -> torch.Tensor:
+        _matcher("GroundingLoss", self.matcher, all_layers_cls_scores, gt_bboxes)
         tg = _targets or self._targets(all_layers_cls_scores, all_layers_pred_bboxes, text_token_mask, gt_bboxes, positive_maps)
         return hungarian_assign(all_layers_cls_scores, all_layers_pred_bboxes, text_token_mask, gt_bboxes, positive_maps, self.cost_alpha,
-                                self.cost_gamma, self.cost_weights, tg)
+                                self.cost_gamma, self.cost_weights, tg, self.matcher)
 
     def loss(self, all_layers_cls_scores, all_layers_pred_bboxes, text_token_mask, gt_bboxes, positive_maps) -> dict:
         scores, boxes = all_layers_cls_scores, all_layers_pred_bboxes
+        _matcher("GroundingLoss", self.matcher, scores, gt_bboxes)
         tg = self._targets(scores, boxes, text_token_mask, gt_bboxes, positive_maps)
         K = int(scores.shape[2])
         num_pos = sum(min(K, g) for g in tg.G)

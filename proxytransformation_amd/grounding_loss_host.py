@@ -16,7 +16,10 @@ coincident faces "inside" the other independently (two identical rotated boxes: 
 The costs, the loss and its gradients follow the reference's lines: models/losses/match_cost.py:227-237 (``BinaryFocalLossCost``),
 ``BBox3DL1Cost`` (an L1 ``cdist``), models/losses/chamfer_distance.py:58-63, 160-203, dense_heads/grounding_head.py:686-824 as the shipped
 configuration runs it, and mmdet's sigmoid focal loss (``py_sigmoid_focal_loss`` with ``weight_reduce_loss``), restated from the
-published source and not pinned against an installed mmdet."""
+published source and not pinned against an installed mmdet.
+
+Two matchings: ``assign_host`` is the host matcher's (scipy); ``sap_assign_host`` writes the shortest-augmenting-path method out with
+one stated tie rule and is what the device matcher (``ptx_gl_assign``, csrc/grounding_assign.hip) reproduces bit for bit."""
 from __future__ import annotations
 
 import math
@@ -24,7 +27,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-__all__ = ["COPLANAR_TOL", "SIGNS", "assign_host", "box_iou3d_host", "corners_host", "cost_host", "euler_matrix", "loss_dict", "loss_host", "predict_host"]
+__all__ = ["COPLANAR_TOL", "SIGNS", "assign_host", "box_iou3d_host", "corners_host", "cost_host", "euler_matrix", "loss_dict", "loss_host", "predict_host", "sap_assign_host"]
 
 COPLANAR_TOL = 1e-5
 F32_EPS = float(np.finfo(np.float32).eps)
@@ -221,6 +224,91 @@ def assign_host(costs: List[List[np.ndarray]], K: int) -> np.ndarray:
                 continue
             rows, cols = linear_sum_assignment(np.nan_to_num(c, nan=100.0, posinf=100.0, neginf=-100.0))
             out[l, b, rows] = cols
+    return out
+
+
+SAP_MAX_ROWS, SAP_MAX_COLS = 256, 1024                     # the device solver's limits on min(K, G_b) and max(K, G_b)
+
+
+def _sap(C: np.ndarray) -> np.ndarray:
+    """``col4row (n)`` of the ``n x m`` float64 matrix ``C`` (``n <= m``, every entry finite): one augmentation per row in increasing
+    index, every loop bounded as the kernel bounds it."""
+    n, m = C.shape
+    u, v = np.zeros(n), np.zeros(m)
+    col4row, row4col = np.full(n, -1, np.int64), np.full(m, -1, np.int64)
+    for cur in range(n):
+        spc = np.full(m, np.inf)                            # the shortest path cost to every column
+        path = np.full(m, -1, np.int64)
+        remaining = np.ones(m, bool)
+        tree, reached = [], []                              # the matched rows the tree took in, the path cost at which each was reached
+        min_val, i, sink = 0.0, cur, -1
+        for _ in range(n + 1):
+            r = ((min_val + C[i]) - u[i]) - v               # in this order: the kernel forms the same doubles
+            better = remaining & (r < spc)
+            spc[better], path[better] = r[better], i
+            lowest = spc[remaining].min()
+            if not lowest < np.inf:
+                return col4row
+            j = int(np.nonzero(remaining & (spc == lowest))[0][0])          # THE TIE RULE: the lowest column index
+            min_val = lowest
+            remaining[j] = False
+            if row4col[j] < 0:
+                sink = j
+                break
+            i = int(row4col[j])
+            tree.append(i)
+            reached.append(lowest)                          # = spc[col4row[i]]: a scanned column's path cost no longer moves
+        if sink < 0:
+            return col4row
+        u[cur] = u[cur] + min_val
+        for i, d in zip(tree, reached):
+            u[i] = u[i] + (min_val - d)
+        v[~remaining] = v[~remaining] - (min_val - spc[~remaining])
+        j = sink
+        for _ in range(len(tree) + 1):                      # walk back from the sink
+            i = int(path[j])
+            row4col[j] = i
+            col4row[i], j = j, col4row[i]
+            if i == cur:
+                break
+    return col4row
+
+
+def sap_assign_host(cost: np.ndarray, G: Sequence[int], B: int) -> np.ndarray:
+    """``assign (NL,B,K) int32`` of ``cost (NL,K,sum G)`` as ``ptx_gl_cost`` leaves it: the specification of ``ptx_gl_assign``
+    (``hungarian_assign(matcher='device')``), which the device reproduces bit for bit.  No scipy: the rectangular shortest-augmenting-path
+    method (Jonker-Volgenant as Crouse states it, which is what scipy runs) written out, per (layer, scene) on the scene's ``K x G_b``
+    column range.
+
+    * Every entry is mapped as it is read, as ``hungarian_assign``'s host path maps it: NaN -> 100, +inf -> 100, -inf -> -100; fp32
+      values widened to float64.
+    * The smaller side supplies the rows, ``n = min(K, G_b)``, augmented in increasing index; the larger side the columns.
+    * Duals, path costs and every comparison in float64; a path cost is ``((min_val + c) - u[i]) - v[j]``, a dual moves by
+      ``u[i] + (min_val - spc[col4row[i]])`` and ``v[j] - (min_val - spc[j])``: additions and subtractions only, in this order.
+    * THE TIE RULE: among the columns not yet scanned that share the smallest path cost, the one with the LOWEST COLUMN INDEX is
+      scanned next -- whether it is free or matched.  (scipy prefers a free column and otherwise the last of its shrinking list; on a
+      tie both matchings are optimal, the pairs may differ.)
+    * ``n`` augmentations of at most ``n + 1`` tree steps each.  All entries are finite after the mapping, so a step always finds a
+      column; if it ever did not, the problem stops and the rows it has not matched keep -1.
+    A scene without a box, and ``K = 0``, give -1 everywhere."""
+    cost = np.asarray(cost)
+    NL, K, SG = cost.shape
+    if len(G) != B or sum(G) != SG:
+        raise ValueError(f"sap_assign_host: {B} box counts that sum to {SG} expected, got {list(G)}")
+    mapped = np.nan_to_num(cost.astype(np.float64), nan=100.0, posinf=100.0, neginf=-100.0)
+    out = np.full((NL, B, K), -1, np.int32)
+    lo = 0
+    for b in range(B):
+        if G[b] and K:
+            for l in range(NL):
+                C = mapped[l][:, lo:lo + G[b]]
+                if G[b] > K:                                # the rows are the queries
+                    out[l, b] = _sap(C)
+                else:                                       # the rows are the boxes
+                    col4row = _sap(np.ascontiguousarray(C.T))
+                    matched = col4row >= 0
+                    out[l, b, col4row[matched]] = np.nonzero(matched)[0]
+        lo += G[b]
     return out
 
 

@@ -19,6 +19,21 @@ MIN_GAP = 1e-6
 RANDOM_SHAPES = ((256, 1), (256, 4), (256, 17), (256, 64), (64, 65), (8, 20), (1, 5), (63, 63), (1024, 32))
 
 
+# (K, G of every scene) on both sides of the switch of ``ptx_gl_assign`` at min(K, max G) * max(K, max G) <= 32768 between the matrix
+# staged in LDS and the matrix read in place: staged at exactly 128 KiB with the boxes as the rows (written transposed) and with the
+# queries as the rows; the first shapes read in place, by columns and by rows; one large scene that takes the whole launch out of staging
+# while the 3-, 0- and 40-box scenes beside it run on the in-place path.  Random and special matrices are drawn with seed 7 + K
+# (``stage_edge_cost``); the random ones have a unique optimum (gaps 2e-3 to 2e-2, ``require_unique`` guards it).
+STAGE_EDGE_SHAPES = ((256, (128,)), (128, (256,)), (256, (129,)), (129, (256,)), (256, (3, 129, 0, 40)))
+STAGE_EDGE_NL = 2
+STAGE_FLOATS = 32768
+
+
+def staged(K, max_g):
+    """Whether ``ptx_gl_assign`` stages the matrices of a launch in LDS (csrc/grounding_assign.hip, ``kGaStageFloats``)."""
+    return min(K, max_g) * max(K, max_g) <= STAGE_FLOATS
+
+
 def mapped(cost):
     """The matrix the matchers solve: float64 of the fp32 values with ``hungarian_assign``'s mapping of NaN and the infinities."""
     return np.nan_to_num(np.asarray(cost, np.float32).astype(np.float64), nan=100.0, posinf=100.0, neginf=-100.0)
@@ -45,6 +60,21 @@ def product_cost(n):
     """``cost[i,j] = (i+1)(j+1)``: the optimum is the anti-diagonal and the augmenting paths grow long."""
     i = np.arange(1, n + 1, dtype=np.float64)
     return (i[:, None] * i[None, :]).astype(np.float32)[None]
+
+
+def product_cost_rect(K, G):
+    """``cost[k,g] = (k+1)(g+1)`` as a ``K x G`` matrix (every entry exact in fp32 up to 256 x 128): long augmenting paths on a
+    rectangle, either side as the rows.  The expected matching comes from the specification, not from a formula."""
+    return (np.arange(1, K + 1, dtype=np.float64)[:, None] * np.arange(1, G + 1, dtype=np.float64)[None, :]).astype(np.float32)[None]
+
+
+@functools.lru_cache(maxsize=None)
+def stage_edge_cost(kind, K, G):
+    """The ``random`` / ``special`` / ``dyadic`` matrix of a ``STAGE_EDGE_SHAPES`` entry (read-only: drawn once, shared)."""
+    draw = dict(random=random_cost, special=special_cost, dyadic=dyadic_cost)[kind]
+    cost = draw(STAGE_EDGE_NL, K, G, 7 + K)
+    cost.setflags(write=False)
+    return cost
 
 
 def special_cost(NL, K, G, seed):

@@ -34,7 +34,7 @@ static int check(long n, int C, int nv)
 
 int main()
 {
-    const long edges[] = {1, 2, 255, 256, 257, 511, 512, 513, 20820, 1024l * 256 - 1, 1024l * 256, 1024l * 256 + 1, 2048l * 256, 2048l * 256 + 1,
+    const long edges[] = {1, 2, 255, 256, 257, 511, 512, 513, 20820, 1024l * 256 - 1, 1024l * 256, 1024l * 256 + 1, 1024l * 256 + 257, 2048l * 256, 2048l * 256 + 1,
                           (1l << 24) - 1, 1l << 24};
     for (long n : edges)
         for (int C : {64, 256, 512})

@@ -60,7 +60,47 @@ def test_posembed_one_row_is_refused_as_torch_refuses_it():
         tu.pe_module(c)(torch.from_numpy(c["x"][:, :1]).transpose(1, 2))
 
 
-@pytest.mark.parametrize("cin,C,n,shift,padded", tu.PE_CASES + [tu.PE_UNPADDED])
+@pytest.mark.parametrize("cin,C,n,shift,padded", tu.PE_SLAB_CASES + [tu.PE_CHUNK_CASE])
+def test_posembed_specification_is_torch_over_several_slabs(cin, C, n, shift, padded):
+    """The cases of tests/test_gpu_decoder_train_edges.py: the numpy specification is the float64 torch chain at 1e-10 on each.  At
+    262145 rows no leaf goes by ``hold``, so no precondition is asserted there: the fp32 chain's yardsticks and its ``dconv1_b`` against
+    the bound are printed (fp32 torch is no yardstick for that leaf at this size, decoder_train_util says why), and float64's own
+    ``dconv1_b`` is at rounding scale."""
+    c = tu.pe_case(cin, C, n, shift, padded)
+    r32, r64 = tu.pe_refs(cin, C, n, shift, padded)
+    spec = tu.pe_spec(c, np.float64)
+    for k in ("out", "running_mean", "running_var") + tu.PE_GRADS:
+        if k == "dconv1_b":                                  # zero in exact arithmetic: both are roundings, at the scale of dconv1_w's terms
+            assert float(np.abs(spec[k] - r64[k]).max()) <= 1e-10 * max(1.0, float(np.abs(r64["dconv1_w"]).max())), k
+            continue
+        assert close(spec[k], r64[k]), k
+    assert r64["num_batches_tracked"] == 6
+    if (cin, C, n, shift, padded) == tu.PE_CHUNK_CASE:
+        for k in ("out", "running_mean", "running_var") + tuple(g for g in tu.PE_GRADS if g != "dconv1_b"):
+            print(f"posembed {n} rows {k}: fp32 yardstick {su.rel(r32[k], r64[k]):.3e}")
+        bound = tu.conv1_bias_bound(c)
+        print(f"posembed {n} rows dconv1_b: fp32 torch {np.abs(r32['dconv1_b']).max():.3e}  float64 {np.abs(r64['dconv1_b']).max():.3e}  "
+              f"bound {bound.max():.3e}  |dconv1_w| {np.abs(r64['dconv1_w']).max():.3e}")
+        assert np.isfinite(bound).all() and (bound > 0).all()
+        assert float(np.abs(r64["dconv1_b"]).max()) <= 1e-9 * max(1.0, float(np.abs(r64["dconv1_w"]).max()))
+
+
+def test_posembed_first_slab_alone_and_reversed_rows():
+    """The first 256 rows of the 257-row case alone (one slab): ``hold``'s precondition and the bound on that cut, which the GPU module
+    draws; reversing the order of those rows moves nothing in float64 but the order of ``out``."""
+    case = tu.PE_SLAB_CASES[0]
+    c = tu.pe_cut(tu.pe_case(*case), 256)
+    r32, r64 = tu.pe_torch(c, torch.float32), tu.pe_torch(c, torch.float64)
+    back = tu.pe_torch(tu.pe_reversed(c, 256), torch.float64)
+    for k in ("out", "running_mean", "running_var") + tuple(g for g in tu.PE_GRADS if g != "dconv1_b"):
+        assert su.rel(r32[k], r64[k]) < 1e-5, (k, su.rel(r32[k], r64[k]))
+        assert close(back[k][:, ::-1] if k == "out" else back[k], r64[k]), k
+    assert (np.abs(r32["dconv1_b"]) <= tu.conv1_bias_bound(c)).all()
+    whole = tu.pe_reversed(tu.pe_case(*case), 256)
+    assert np.array_equal(whole["x"][:, 256:], tu.pe_case(*case)["x"][:, 256:]) and np.array_equal(whole["x"][:, 255], tu.pe_case(*case)["x"][:, 0])
+
+
+@pytest.mark.parametrize("cin,C,n,shift,padded", tu.PE_CASES + tu.PE_SLAB_CASES + [tu.PE_UNPADDED])
 def test_posembed_yardsticks_and_the_bias_bound(cin, C, n, shift, padded):
     """``hold``'s precondition on every case the GPU module draws (the fp32 CPU torch chain within 1e-5 of float64), and the fp32 torch
     chain's own ``dconv1_b`` inside the bound the device is held to: the bound is not fitted to the device."""
@@ -80,7 +120,7 @@ def test_posembed_yardsticks_and_the_bias_bound(cin, C, n, shift, padded):
 
 # ------------------------------------------------------------------------------------------------------------------ boxes
 def test_boxes_specification_is_torch_on_both_sides_of_the_clamp():
-    for C, n in tu.BOX_CASES:
+    for C, n in tu.BOX_CASES + tu.BOX_SLAB_CASES:
         c = tu.box_case(C, n)
         ref = tu.box_torch(c, torch.float64)
         spec = gh.boxes_bwd_host(tu.f64(c["h"]), tu.f64(c["weight"]), tu.f64(c["bias"]), tu.f64(c["dboxes"]))
@@ -92,6 +132,24 @@ def test_boxes_specification_is_torch_on_both_sides_of_the_clamp():
         r32 = tu.box_torch(c, torch.float32)
         for k in ("dh", "dweight", "dbias"):
             assert su.rel(r32[k], ref[k]) < 1e-5, (C, n, k)
+
+
+def test_boxes_specification_is_torch_without_a_bias():
+    """``bias=None``: the draw's log-sizes still lie on both sides of the clamp (``h`` scaled, decoder_train_util), the specification
+    returns no ``dbias`` and is float64 torch, and ``hold``'s precondition holds for ``dh`` and ``dweight``."""
+    C, n = tu.BOX_NOBIAS_CASE
+    c = tu.box_case(C, n, has_bias=False)
+    assert c["bias"] is None
+    r32, ref = tu.box_refs(C, n, has_bias=False)
+    spec = gh.boxes_bwd_host(tu.f64(c["h"]), tu.f64(c["weight"]), None, tu.f64(c["dboxes"]))
+    p = tu.f64(c["h"]).reshape(n, C) @ tu.f64(c["weight"]).T
+    assert (p[:, 3:6] > tu.LOG_CLAMP + 1e-3).any() and (p[:, 3:6] < tu.LOG_CLAMP - 1e-3).any()
+    assert np.abs(p[:, 3:6] - tu.LOG_CLAMP).min() > 1e-3
+    assert set(spec) == {"dh", "dweight"} and "dbias" not in ref
+    for k in ("dh", "dweight"):
+        assert close(spec[k], ref[k]), k
+        print(f"boxes without a bias {k}: fp32 yardstick {su.rel(r32[k], ref[k]):.3e}")
+        assert su.rel(r32[k], ref[k]) < 1e-5, k
 
 
 def test_boxes_on_the_clamp_nan_and_infinities():
@@ -125,6 +183,35 @@ def test_scores_specification_is_torch(NL, B, K, T, M, scaled, has_bias):
     for k in ref:
         assert close(spec[k], np.asarray(ref[k]).reshape(np.shape(spec[k]))), k
     assert not spec["dtext"][~c["mask"]].any()               # a masked token gets zeros
+
+
+@pytest.mark.parametrize("NL,B,K,T,M,C", tu.SCORE_WIDE_CASES)
+@pytest.mark.parametrize("scaled,has_bias", [(True, True), (False, False)])
+def test_scores_specification_is_torch_at_width(NL, B, K, T, M, C, scaled, has_bias):
+    """The cases of tests/test_gpu_decoder_train_edges.py: the specification is float64 torch, and ``hold``'s precondition."""
+    c = tu.score_case(NL, B, K, T, M, C=C)
+    assert c["hidden"].shape == (NL, B, K, C) and c["text"].shape == (B, T, C)
+    ref, spec = tu.score_torch(c, torch.float64, scaled, has_bias), tu.score_spec(c, np.float64, scaled, has_bias)
+    r32 = tu.score_torch(c, torch.float32, scaled, has_bias)
+    assert set(ref) == set(spec)
+    for k in ref:
+        assert close(spec[k], np.asarray(ref[k]).reshape(np.shape(spec[k]))), k
+    for k in ("dhidden", "dtext"):
+        assert r32[k].dtype == np.float32 and su.rel(r32[k], ref[k]) < 1e-5, (k, su.rel(r32[k], ref[k]))
+    assert not spec["dtext"][~c["mask"]].any()
+
+
+def test_scores_never_read_the_gradient_under_the_mask_at_width():
+    NL, B, K, T, M, C = tu.SCORE_WIDE_CASES[0]
+    c = tu.score_case(NL, B, K, T, M, all_masked_scene=True, C=C)
+    clean = tu.score_spec(c, np.float64)
+    d = c["dscores"].copy()
+    d[..., T:] = np.nan
+    d[..., :T][np.broadcast_to(~c["mask"][None, :, None, :], d[..., :T].shape)] = np.nan
+    dirty = tu.score_spec(dict(c, dscores=d), np.float64)
+    for k in clean:
+        assert np.isfinite(dirty[k]).all() and np.array_equal(clean[k], dirty[k]), k
+    assert not clean["dhidden"][:, -1].any() and not clean["dtext"][-1].any()
 
 
 def test_scores_never_read_the_gradient_under_the_mask():

@@ -95,6 +95,32 @@ def test_long_augmenting_paths_on_the_product_matrix(n):
     assert np.array_equal(got[0, 0], np.arange(n)[::-1])     # the rearrangement inequality: the anti-diagonal, strictly
 
 
+@pytest.mark.parametrize("K,G", au.STAGE_EDGE_SHAPES)
+def test_specification_on_both_sides_of_the_staging_switch(K, G):
+    """The shapes tests/test_gpu_grounding_assign_edges.py launches: on the random matrix (a unique optimum, established here) the
+    specification's pairs are scipy's; on the special one (NaN and infinities mapped to +-100, many ties) a matching of scipy's total."""
+    B = len(G)
+    assert au.staged(K, max(G)) == (max(G) <= 128 or K <= 128)
+    cost = au.stage_edge_cost("random", K, G)
+    gap = au.require_unique(cost, G)
+    print(f"K={K} G={G}: optimality gap {gap:.2e}")
+    got = gh.sap_assign_host(cost, G, B)
+    assert np.array_equal(got, au.check_matching(got, cost, G))
+    cost = au.stage_edge_cost("special", K, G)
+    assert np.isnan(cost).any() and np.isposinf(cost).any() and np.isneginf(cost).any()
+    got = gh.sap_assign_host(cost, G, B)
+    au.check_matching(got, cost, G)
+    for b, g in enumerate(G):
+        assert ((got[:, b] >= 0).sum(-1) == min(K, g)).all()
+
+
+@pytest.mark.parametrize("K,g", [(256, 128), (128, 256)])
+def test_long_augmenting_paths_on_the_product_rectangle(K, g):
+    cost = au.product_cost_rect(K, g)
+    assert cost.shape == (1, K, g) and float(cost.max()) == K * g
+    au.check_matching(gh.sap_assign_host(cost, (g,), 1), cost, (g,))
+
+
 def test_matcher_keyword_refusals_carry_the_numbers():
     for bad in ("gpu", "", None):
         with pytest.raises(ValueError, match="matcher must be 'host' or 'device'"):

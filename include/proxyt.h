@@ -860,6 +860,39 @@ PTX_API int ptx_point_sample_bwd(const float *points, int N, const float *dout, 
                          float ori_w, float pad_h, float pad_w, int bilinear, void *dfeats, int feat_dtype, void *workspace,
                          size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------ level join (ABI 13, by addition)
+ * detectors/sparse_featfusion_grounder_preshape.py:428-479 for ONE backbone level and every scene at once: each row of a sparse
+ * level gets the image features sampled at its position appended,
+ *   out[r] = [ level_feats[r] (Cb) | ptx_point_sample of scene coords[r,0] at (float)coords[r,1:4] * voxel_size (Ci) ],
+ * in one launch.  coords (n,4) int32 rows (scene, x, y, z), the rows of a scene contiguous and the scenes ascending; the point is one
+ * rounded multiply, the bits ptx_voxel_coarsen emits; the sampling is the arithmetic of ptx_point_sample itself (shared device
+ * functions), so out[:, Cb:] equals the per-scene calls bit for bit, nearest (bilinear = 0) and bilinear.  featT: a HOST array of B
+ * device pointers, scene b's channels-last maps as ptx_point_sample_prepare wrote them ((V, H*W, Ci) fp32), read in place.
+ * tables: ptx_level_join_table_floats(B, V) floats, the same content on the host (tables_host: read by the checks) and on the
+ * device (tables_dev: read by the kernels; the caller uploads it, e.g. one pinned staging copy for all levels):
+ *   scene b at tables + 32 b:  [0:12] the (3,4) pre-transform, [12] != 0: apply it, [13] scale_w, [14] scale_h, [15] crop_w,
+ *                              [16] crop_h, [17] != 0: flip, [18] ori_w, [19] pad_h, [20] pad_w, [21:32] unused
+ *   then proj (B, V, 4, 4) row-major at tables + 32 B.
+ * V is the same for every scene.  Cb, Ci: multiples of 64 up to 512; 1 <= B <= 64; n >= 0 (n == 0 launches nothing); a scene
+ * without rows is fine; a row whose scene index is outside [0, B) gets zeros.  level_feats and out: 16-byte aligned.  valid_num (n) int32
+ * or NULL.  All checks are on the
+ * host, before anything is enqueued. */
+PTX_API size_t ptx_level_join_table_floats(int B, int V);
+PTX_API int ptx_level_join(const int32_t *coords, int n, const float *level_feats, int Cb, const float *const *featT,
+                   const float *tables_host, const float *tables_dev, int B, int V, int Ci, int H, int W, float voxel_size,
+                   int bilinear, float *out, int32_t *valid_num, void *stream);
+/* The backward of ptx_level_join in one call.  g (n, Cb + Ci) fp32 contiguous, 16-byte aligned: dlevel_feats (n, Cb) = g[:, :Cb]
+ * (NULL: not wanted); dimg (B, V, Ci, H, W) in storage type feat_dtype (NULL: not wanted) = ptx_point_sample_bwd of every scene on
+ * g[rows of the scene, Cb:], read in place by leading dimension and column offset: the same inverted index, scene by scene on the
+ * one workspace, every element written once (a scene without rows: zeros), no float atomics, bitwise reproducible.  scene_end: a
+ * HOST array, scene b's rows are [scene_end[b-1], scene_end[b]), scene_end[B-1] = n.  valid_num: what the forward wrote.
+ * workspace: ptx_level_join_bwd_workspace_bytes(the largest scene's rows, ...) bytes (0: outside the 32-bit index range; not
+ * needed when dimg is NULL or n == 0). */
+PTX_API size_t ptx_level_join_bwd_workspace_bytes(int max_rows, int V, int H, int W, int bilinear);
+PTX_API int ptx_level_join_bwd(const int32_t *coords, int n, const int32_t *scene_end, const float *g, int Cb, const int32_t *valid_num,
+                       const float *tables_host, const float *tables_dev, int B, int V, int Ci, int H, int W, float voxel_size,
+                       int bilinear, float *dlevel_feats, void *dimg, int feat_dtype, void *workspace, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------ train-mode operators
  * The differentiable half of the path in train mode -- batch-statistics BatchNorm2d / BatchNorm1d (PRE:74, 114,
  * 329-330), Dropout (PRE:189-191, timm Mlp), DropPath (PRE:268) and the gradients of everything between the ball

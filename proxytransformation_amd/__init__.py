@@ -11,6 +11,7 @@ Only what the path needs lives here:
 * ``query_select.QuerySelect``               -- the detector's ``pre_decoder`` behind the neck: pad, text scores, sorted top-k, box decode;
 * ``decoder.GroundingDecoder``               -- the transformer decoder behind it (self, text and scene attention, FFN, box refinement);
 * ``grounding_loss.GroundingLoss``           -- the head's loss behind the decoder: 9-DoF box IoU, Hungarian match costs, focal and corner loss;
+* ``detector.GroundingDetector``             -- all of the above as one module: ``loss`` and ``predict`` of the whole grounder;
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -25,6 +26,7 @@ from .neck import MinkNeck
 from .query_select import QuerySelect
 from .decoder import GroundingDecoder
 from .grounding_loss import GroundingLoss
+from .detector import GroundingDetector
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "GroundingDecoder", "GroundingLoss", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "GroundingDecoder", "GroundingDetector", "GroundingLoss", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
 __version__ = "0.1.0"

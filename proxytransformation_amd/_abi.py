@@ -237,6 +237,10 @@ SIGNATURES.update({
     "ptx_point_sample": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _P, _P, _Z, _P]),
     "ptx_point_sample_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "ptx_point_sample_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _F, _F, _F, _F, _I, _F, _F, _F, _I, _P, _I, _P, _Z, _P]),
+    "ptx_level_join_table_floats": (_Z, [_I, _I]),
+    "ptx_level_join": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "ptx_level_join_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "ptx_level_join_bwd": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _I, _P, _Z, _P]),
     "ptx_op_gemm": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I, _I, _L, _L, _L, _L, _L, _L, _I, _I, _F, _I, _I, _L, _P]),
     "ptx_op_gemm_route": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _L, _I, _I, _L, _L, _L, _L, _L, _L, _I, _I, _F, _I, _I, _L]),
     "ptx_op_transpose": (_I, [_P, _I, _I, _P, _P]),

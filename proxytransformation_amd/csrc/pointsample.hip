@@ -11,6 +11,7 @@
 // hit a pixel), lanes = channels for the gather (256 B contiguous per view and 64 channels).
 #include "common.h"
 #include "imgstore.h"
+#include "pointsample.h"
 
 namespace ptx {
 
@@ -33,122 +34,16 @@ __global__ __launch_bounds__(256) void k_feat_transpose(const void *__restrict__
     }
 }
 
-struct PsArgs {
-    const float *points; int N;
-    const float *featT; int V, C, H, W;
-    const float *proj; const float *pre;
-    float sx, sy, cx, cy; int flip; float ori_w, pad_h, pad_w;
-    float *out; int32_t *valid_num;
-    int bilinear;       // aligned=True: F.grid_sample(mode='bilinear'); 0: 'nearest' (what the detector asks for)
-};
-
-constexpr int kPsMaxQ = 8;      // C <= 512
-
-// the reverse 3D augmentation, composed by the host into one affine (pre == NULL: none)
-__device__ __forceinline__ void ps_pre(const float *A, float &x, float &y, float &z)
-{
-    if (!A) return;
-    const float nx = fmaf(A[2], z, fmaf(A[1], y, A[0] * x)) + A[3];
-    const float ny = fmaf(A[6], z, fmaf(A[5], y, A[4] * x)) + A[7];
-    const float nz = fmaf(A[10], z, fmaf(A[9], y, A[8] * x)) + A[11];
-    x = nx; y = ny; z = nz;
-}
-
-// Where point (x, y, z) lands in view v.  nearest: pix = y * W + x of the sampled pixel; bilinear: (x0, y0) = the north-west
-// neighbour (possibly outside the map) and the weights of the +1 neighbours.  inb: the view contributes a sample; valid: it counts
-// in the divisor.  The forward and the backward's index (k_psb_index) both call this: one statement of the rounded steps.
-struct PsHit { bool inb, valid; int pix, x0, y0; float wx1, wy1; };
-__device__ __forceinline__ PsHit ps_project(const PsArgs &a, float x, float y, float z, int v)
-{
-    PsHit h{false, false, 0, 0, 0, 0.0f, 0.0f};
-    const float *P = a.proj + (size_t)v * 16;
-    // q = [x y z 1] P^T (structures/bbox_3d/utils.py:322-327), one rounding per step, in this order
-    float q[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-        q[r] = __fadd_rn(fmaf(z, P[4 * r + 2], fmaf(y, P[4 * r + 1], __fmul_rn(x, P[4 * r]))), P[4 * r + 3]);
-    const float zc = fmaxf(q[2], 1e-3f);
-    float cx = __fsub_rn(__fmul_rn(__fdiv_rn(q[0], zc), a.sx), a.cx);        // scale -> crop (point_fusion.py:266-267)
-    const float cy = __fsub_rn(__fmul_rn(__fdiv_rn(q[1], zc), a.sy), a.cy);
-    if (a.flip) cx = __fsub_rn(a.ori_w, cx);                                  // horizontal flip (:276)
-    const float nx = __fsub_rn(__fmul_rn(__fdiv_rn(cx, a.pad_w), 2.0f), 1.0f);
-    const float ny = __fsub_rn(__fmul_rn(__fdiv_rn(cy, a.pad_h), 2.0f), 1.0f);
-    // grid_sample, align_corners=True (unnormalise: ((g + 1) / 2) * (size - 1)), zeros padding
-    const float ix = __fmul_rn(__fdiv_rn(__fadd_rn(nx, 1.0f), 2.0f), (float)(a.W - 1));
-    const float iy = __fmul_rn(__fdiv_rn(__fadd_rn(ny, 1.0f), 2.0f), (float)(a.H - 1));
-    if (!a.bilinear) {                                  // nearest: round half to even
-        const float fx = rintf(ix), fy = rintf(iy);
-        h.inb = fx >= 0.0f && fx <= (float)(a.W - 1) && fy >= 0.0f && fy <= (float)(a.H - 1);
-        if (h.inb) h.pix = (int)fy * a.W + (int)fx;
-    } else {                                            // the four neighbours, those outside the map count as 0
-        const float x0 = floorf(ix), y0 = floorf(iy);
-        h.wx1 = __fsub_rn(ix, x0); h.wy1 = __fsub_rn(iy, y0);
-        // a point whose four neighbours are all outside contributes nothing (also covers inf / nan coordinates)
-        h.inb = x0 >= -1.0f && x0 <= (float)(a.W - 1) && y0 >= -1.0f && y0 <= (float)(a.H - 1);
-        if (h.inb) { h.x0 = (int)x0; h.y0 = (int)y0; }
-    }
-    h.valid = cx < a.pad_w && cx > 0.0f && cy < a.pad_h && cy > 0.0f && q[2] > 0.0f;     // :300-301
-    return h;
-}
-
 __global__ __launch_bounds__(256) void k_point_sample(PsArgs a)
 {
     const int n = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (n >= a.N) return;
     const int lane = lane_id();
-    float x = a.points[(size_t)n * 3], y = a.points[(size_t)n * 3 + 1], z = a.points[(size_t)n * 3 + 2];
+    float x, y, z;
+    ps_point(a, n, x, y, z);
     ps_pre(a.pre, x, y, z);
     float acc[kPsMaxQ];
-#pragma unroll
-    for (int q = 0; q < kPsMaxQ; ++q) acc[q] = 0.0f;
-    int nvalid = 0;
-    const int HW = a.H * a.W;
-    for (int v0 = 0; v0 < a.V; v0 += 64) {
-        const int v = v0 + lane;
-        PsHit h{};
-        if (v < a.V) h = ps_project(a, x, y, z, v);
-        const bool inb = h.inb, valid = h.valid;
-        const int pix = h.pix, cx0 = h.x0, cy0 = h.y0;
-        const float wx1 = h.wx1, wy1 = h.wy1;
-        nvalid += __popcll(__ballot(valid));
-        unsigned long long hit = __ballot(inb);
-        while (hit) {                                           // views in ascending order (the reference sums dim 0)
-            const int l = __ffsll((long long)hit) - 1;
-            hit &= hit - 1;
-            if (!a.bilinear) {
-                const int px = __builtin_amdgcn_readlane(pix, l);
-                const float *f = a.featT + ((size_t)(v0 + l) * HW + px) * a.C;
-#pragma unroll
-                for (int q = 0; q < kPsMaxQ; ++q) {
-                    const int c = lane + 64 * q;
-                    if (c < a.C) acc[q] += f[c];
-                }
-            } else {
-                const int x0 = __builtin_amdgcn_readlane(cx0, l), y0 = __builtin_amdgcn_readlane(cy0, l);
-                const float fx = PTX_LANE_F(wx1, l), fy = PTX_LANE_F(wy1, l);
-                const float gx = __fsub_rn(1.0f, fx), gy = __fsub_rn(1.0f, fy);
-                // weights as torch's grid sampler forms them: nw = (x1 - ix)(y1 - iy), ne = (ix - x0)(y1 - iy), ...
-                const float w[4] = {__fmul_rn(gx, gy), __fmul_rn(fx, gy), __fmul_rn(gx, fy), __fmul_rn(fx, fy)};
-                const float *fv = a.featT + (size_t)(v0 + l) * HW * a.C;
-                float s[kPsMaxQ];
-#pragma unroll
-                for (int q = 0; q < kPsMaxQ; ++q) s[q] = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {                   // nw, ne, sw, se
-                    const int xx = x0 + (k & 1), yy = y0 + (k >> 1);
-                    if (xx < 0 || xx >= a.W || yy < 0 || yy >= a.H) continue;      // wave-uniform
-                    const float *f = fv + ((size_t)yy * a.W + xx) * a.C;
-#pragma unroll
-                    for (int q = 0; q < kPsMaxQ; ++q) {
-                        const int c = lane + 64 * q;
-                        if (c < a.C) s[q] = __fadd_rn(s[q], __fmul_rn(f[c], w[k]));
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < kPsMaxQ; ++q) acc[q] += s[q];
-            }
-        }
-    }
+    const int nvalid = ps_accumulate(a, x, y, z, lane, acc);
     const float den = (float)(nvalid > 1 ? nvalid : 1);
 #pragma unroll
     for (int q = 0; q < kPsMaxQ; ++q) {
@@ -190,7 +85,8 @@ __global__ __launch_bounds__(256) void k_psb_index(PsArgs a, PsbIndex ix)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const int n = (int)(i / a.V), v = (int)(i % a.V);
     if (n >= a.N || a.valid_num[n] <= 0) return;
-    float x = a.points[(size_t)n * 3], y = a.points[(size_t)n * 3 + 1], z = a.points[(size_t)n * 3 + 2];
+    float x, y, z;
+    ps_point(a, n, x, y, z);
     ps_pre(a.pre, x, y, z);
     const PsHit h = ps_project(a, x, y, z, v);
     if (!h.inb) return;
@@ -293,6 +189,7 @@ __global__ __launch_bounds__(256) void k_psb_order(PsbIndex ix, int D)
 struct PsbGrad {
     PsbIndex ix; const float *dout; const int32_t *valid_num; void *dfeat;
     int C, HW, ptiles;      // ptiles = ceil(HW / 64)
+    size_t ldo;             // floats between two rows of dout (>= C: a column block of a wider matrix)
 };
 
 template <int DT>
@@ -323,7 +220,7 @@ __global__ __launch_bounds__(256) void k_point_sample_grad(PsbGrad g)
             for (int j = 0; j < cnt; ++j) {
                 const int n = __builtin_amdgcn_readlane(en, j);
                 const float wj = PTX_LANE_F(ew, j), dj = PTX_LANE_F(ed, j);
-                if (c < g.C) acc = __fadd_rn(acc, __fmul_rn(wj, __fdiv_rn(g.dout[(size_t)n * g.C + c], dj)));
+                if (c < g.C) acc = __fadd_rn(acc, __fmul_rn(wj, __fdiv_rn(g.dout[(size_t)n * g.ldo + c], dj)));
             }
         }
         tile[lane][p] = acc;
@@ -352,6 +249,49 @@ static bool psb_layout(int N, int V, int H, int W, int bilinear, PsbLayout &L)
     L.sorted = o; o += align_up((size_t)E * 8, 256);
     L.total = o;
     return true;
+}
+
+size_t psb_bytes(int N, int V, int H, int W, int bilinear)
+{
+    PsbLayout L;
+    if (N < 1 || V < 1 || H < 1 || W < 1 || !psb_layout(N, V, H, W, bilinear, L)) return 0;
+    return L.total;
+}
+
+int psb_run(const char *who, const PsArgs &a, const float *dout, size_t ldo, void *dfeats, int feat_dtype, void *workspace,
+            size_t ws_bytes, hipStream_t st)
+{
+    const int N = a.N, V = a.V, C = a.C, H = a.H, W = a.W;
+    PTX_REQUIRE(N >= 1 && V >= 1 && C >= 1 && C <= 64 * kPsMaxQ && H >= 1 && W >= 1 && feat_dtype >= 0 && feat_dtype <= 2 &&
+                a.pad_h > 0.0f && a.pad_w > 0.0f && ldo >= (size_t)C, "%s: N=%d V=%d C=%d (<= %d) H=%d W=%d dtype=%d pad=(%g, %g)", who, N, V,
+                C, 64 * kPsMaxQ, H, W, feat_dtype, (double)a.pad_h, (double)a.pad_w);
+    PsbLayout L;
+    const int ptiles = cdiv(H * W, 64);
+    PTX_REQUIRE(psb_layout(N, V, H, W, a.bilinear, L) && (long long)V * ptiles <= INT32_MAX,
+                "%s: N=%d V=%d H=%d W=%d: more (point, view) pairs or pixels than 32-bit indices hold", who, N, V, H, W);
+    if (ws_bytes < L.total) { set_error("%s: workspace too small: %zu < %zu bytes", who, ws_bytes, L.total); return PTX_ENOSPACE; }
+    char *ws = static_cast<char *>(workspace);
+    PsbIndex ix{reinterpret_cast<int32_t *>(ws + L.cnt), reinterpret_cast<int32_t *>(ws + L.off), reinterpret_cast<int32_t *>(ws + L.bsum),
+                reinterpret_cast<int2 *>(ws + L.raw), reinterpret_cast<int2 *>(ws + L.sorted)};
+    const int pair_blocks = (int)(((long long)N * V + 255) / 256);
+    PTX_HIP(hipMemsetAsync(ix.cnt, 0, (size_t)(L.D + 1) * 4, st));
+    hipLaunchKernelGGL(k_psb_index<false>, dim3(pair_blocks), dim3(256), 0, st, a, ix);
+    PTX_LAUNCHED("k_psb_index<count>");
+    hipLaunchKernelGGL(k_psb_scan, dim3(L.nb), dim3(256), 0, st, ix.cnt, L.D + 1, ix.off, ix.bsum);
+    PTX_LAUNCHED("k_psb_scan");
+    hipLaunchKernelGGL(k_psb_scan_top, dim3(1), dim3(256), 0, st, ix.bsum, L.nb);
+    PTX_LAUNCHED("k_psb_scan_top");
+    hipLaunchKernelGGL(k_psb_index<true>, dim3(pair_blocks), dim3(256), 0, st, a, ix);
+    PTX_LAUNCHED("k_psb_index<fill>");
+    hipLaunchKernelGGL(k_psb_order, dim3(cdiv(L.D, 256)), dim3(256), 0, st, ix, L.D);
+    PTX_LAUNCHED("k_psb_order");
+    PsbGrad g{ix, dout, a.valid_num, dfeats, C, H * W, ptiles, ldo};
+    const dim3 grid(V * ptiles, cdiv(C, 64));
+    if (feat_dtype == 0) hipLaunchKernelGGL(k_point_sample_grad<0>, grid, dim3(256), 0, st, g);
+    else if (feat_dtype == 1) hipLaunchKernelGGL(k_point_sample_grad<1>, grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(k_point_sample_grad<2>, grid, dim3(256), 0, st, g);
+    PTX_LAUNCHED("k_point_sample_grad");
+    return PTX_OK;
 }
 
 }  // namespace ptx
@@ -407,7 +347,8 @@ int ptx_point_sample(const float *points, int N, const void *feats, int feat_dty
         hipLaunchKernelGGL(k_feat_transpose, dim3(cdiv(H * W, 32), cdiv(C, 32), V), dim3(256), 0, st, feats, feat_dtype, C, H * W, featT);
         PTX_LAUNCHED("k_feat_transpose");
     }
-    PsArgs a{points, N, featT, V, C, H, W, proj, pre, scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w, out, valid_num, bilinear ? 1 : 0};
+    PsArgs a{points, N, featT, V, C, H, W, proj, pre, scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w, out, valid_num, bilinear ? 1 : 0,
+             nullptr, 0.0f};
     hipLaunchKernelGGL(k_point_sample, dim3(cdiv(N, 4)), dim3(256), 0, st, a);
     PTX_LAUNCHED("k_point_sample");
     return PTX_OK;
@@ -416,9 +357,7 @@ int ptx_point_sample(const float *points, int N, const void *feats, int feat_dty
 /* Bytes of ptx_point_sample_bwd's workspace: the (view, pixel) lists sized for every (point, view[, neighbour]) pair. */
 size_t ptx_point_sample_bwd_workspace_bytes(int N, int V, int H, int W, int bilinear)
 {
-    PsbLayout L;
-    if (N < 1 || V < 1 || H < 1 || W < 1 || !psb_layout(N, V, H, W, bilinear, L)) return 0;
-    return L.total;
+    return psb_bytes(N, V, H, W, bilinear);
 }
 
 int ptx_point_sample_bwd(const float *points, int N, const float *dout, const int32_t *valid_num, int V, int C, int H, int W,
@@ -427,39 +366,9 @@ int ptx_point_sample_bwd(const float *points, int N, const float *dout, const in
                          size_t ws_bytes, void *stream)
 {
     PTX_REQUIRE(points && dout && valid_num && proj && dfeats && workspace, "ptx_point_sample_bwd: null argument");
-    PTX_REQUIRE(N >= 1 && V >= 1 && C >= 1 && C <= 64 * kPsMaxQ && H >= 1 && W >= 1 && feat_dtype >= 0 && feat_dtype <= 2 &&
-                pad_h > 0.0f && pad_w > 0.0f, "ptx_point_sample_bwd: N=%d V=%d C=%d (<= %d) H=%d W=%d dtype=%d pad=(%g, %g)", N, V, C,
-                64 * kPsMaxQ, H, W, feat_dtype, (double)pad_h, (double)pad_w);
-    PsbLayout L;
-    const int ptiles = cdiv(H * W, 64);
-    PTX_REQUIRE(psb_layout(N, V, H, W, bilinear, L) && (long long)V * ptiles <= INT32_MAX,
-                "ptx_point_sample_bwd: N=%d V=%d H=%d W=%d: more (point, view) pairs or pixels than 32-bit indices hold", N, V, H, W);
-    if (ws_bytes < L.total) { set_error("ptx_point_sample_bwd: workspace too small: %zu < %zu bytes", ws_bytes, L.total); return PTX_ENOSPACE; }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
-    PsbIndex ix{reinterpret_cast<int32_t *>(ws + L.cnt), reinterpret_cast<int32_t *>(ws + L.off), reinterpret_cast<int32_t *>(ws + L.bsum),
-                reinterpret_cast<int2 *>(ws + L.raw), reinterpret_cast<int2 *>(ws + L.sorted)};
     PsArgs a{points, N, nullptr, V, C, H, W, proj, pre, scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w, nullptr,
-             const_cast<int32_t *>(valid_num), bilinear ? 1 : 0};
-    const int pair_blocks = (int)(((long long)N * V + 255) / 256);
-    PTX_HIP(hipMemsetAsync(ix.cnt, 0, (size_t)(L.D + 1) * 4, st));
-    hipLaunchKernelGGL(k_psb_index<false>, dim3(pair_blocks), dim3(256), 0, st, a, ix);
-    PTX_LAUNCHED("k_psb_index<count>");
-    hipLaunchKernelGGL(k_psb_scan, dim3(L.nb), dim3(256), 0, st, ix.cnt, L.D + 1, ix.off, ix.bsum);
-    PTX_LAUNCHED("k_psb_scan");
-    hipLaunchKernelGGL(k_psb_scan_top, dim3(1), dim3(256), 0, st, ix.bsum, L.nb);
-    PTX_LAUNCHED("k_psb_scan_top");
-    hipLaunchKernelGGL(k_psb_index<true>, dim3(pair_blocks), dim3(256), 0, st, a, ix);
-    PTX_LAUNCHED("k_psb_index<fill>");
-    hipLaunchKernelGGL(k_psb_order, dim3(cdiv(L.D, 256)), dim3(256), 0, st, ix, L.D);
-    PTX_LAUNCHED("k_psb_order");
-    PsbGrad g{ix, dout, valid_num, dfeats, C, H * W, ptiles};
-    const dim3 grid(V * ptiles, cdiv(C, 64));
-    if (feat_dtype == 0) hipLaunchKernelGGL(k_point_sample_grad<0>, grid, dim3(256), 0, st, g);
-    else if (feat_dtype == 1) hipLaunchKernelGGL(k_point_sample_grad<1>, grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(k_point_sample_grad<2>, grid, dim3(256), 0, st, g);
-    PTX_LAUNCHED("k_point_sample_grad");
-    return PTX_OK;
+             const_cast<int32_t *>(valid_num), bilinear ? 1 : 0, nullptr, 0.0f};
+    return psb_run("ptx_point_sample_bwd", a, dout, (size_t)C, dfeats, feat_dtype, workspace, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

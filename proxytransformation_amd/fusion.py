@@ -217,3 +217,207 @@ def prepare_features_many(maps) -> list:
         _abi.check(lib.ptx_point_sample_prepare(m.data_ptr(), _DT[m.dtype], V, C, H, W, ws.data_ptr(), ws.numel(), st),
                    "ptx_point_sample_prepare")
     return views
+
+
+# ---------------------------------------------------------------------------------------------------------------- level join
+_LJ_WORDS = 32          # one scene's table, in floats (include/proxyt.h: ptx_level_join)
+
+
+def image_transform_scalars(img_meta: Optional[dict], img_pad_shape: Sequence[int]) -> tuple:
+    """``(scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w)`` of one sample, as the detector reads them off its ``img_meta``
+    (DET:404-410, 440-441): what ``JoinTables`` takes per scene."""
+    meta = img_meta or {}
+    sw, sh = _pair(meta["scale_factor"][:2], None) if "scale_factor" in meta else (1.0, 1.0)
+    cw, ch = _pair(meta.get("img_crop_offset", 0.0), None)
+    shape = tuple(meta.get("img_shape", img_pad_shape))[:2]
+    return (sw, sh, cw, ch, bool(meta.get("flip", False)), float(shape[1]), float(img_pad_shape[0]), float(img_pad_shape[1]))
+
+
+class JoinTables:
+    """What differs between the scenes of one ``join_level_features`` call -- projection matrices (V,4,4), the reverse 3D
+    augmentation (3,4) or ``None``, the eight image-transform scalars ``(scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h,
+    pad_w)`` -- laid out as ``ptx_level_join`` reads it and brought to the device through ONE pinned staging copy (a ``.to(device)``
+    from pageable memory would block the host behind everything queued on the stream).  The same tables serve every level of a
+    call and its backward.  ``staging``: a dict the caller keeps between calls so that the pinned buffer is allocated once per
+    stream.  ``proj[b]`` / ``pre[b]`` / ``scal[b]`` are the per-scene arguments of ``batch_point_sample``'s own launch (device views
+    of the same upload), for the per-scene route."""
+
+    def __init__(self, projs, pres, scalars, voxel_size: float, device, aligned: bool = False, staging: Optional[dict] = None):
+        import numpy as np
+        B = len(projs)
+        if not (len(pres) == len(scalars) == B):
+            raise ValueError(f"JoinTables: {B} projection stacks, {len(pres)} pre-transforms, {len(scalars)} scalar sets")
+        projs = [np.ascontiguousarray(p, np.float32) for p in projs]
+        V = projs[0].shape[0] if B and projs[0].ndim == 3 else 0
+        for p in projs:
+            if p.shape != (V, 4, 4):
+                raise ValueError(f"JoinTables: every scene needs ({V},4,4) projection matrices (V is uniform per call), got {p.shape}")
+        if not float(voxel_size) > 0.0:
+            raise ValueError(f"JoinTables: voxel_size={voxel_size}")
+        n = _abi.lib().ptx_level_join_table_floats(B, V)
+        if n == 0:
+            raise ValueError(f"JoinTables: B={B} (1..64), V={V} (>= 1)")
+        host = np.zeros((n,), np.float32)                # the library's checks read this copy, in forward and backward
+        for b in range(B):
+            t = host[_LJ_WORDS * b:_LJ_WORDS * (b + 1)]
+            if pres[b] is not None:
+                pre = pres[b].detach().cpu().numpy() if isinstance(pres[b], torch.Tensor) else np.asarray(pres[b])
+                t[0:12] = pre.astype(np.float32).reshape(12)
+                t[12] = 1.0
+            s = scalars[b]
+            if len(s) != 8:
+                raise ValueError("JoinTables: scalars = (scale_w, scale_h, crop_w, crop_h, flip, ori_w, pad_h, pad_w) per scene")
+            t[13:21] = [float(s[0]), float(s[1]), float(s[2]), float(s[3]), 1.0 if s[4] else 0.0, float(s[5]), float(s[6]), float(s[7])]
+            if not (t[19] > 0.0 and t[20] > 0.0):
+                raise ValueError(f"JoinTables: scene {b}: pad_h={s[6]}, pad_w={s[7]}")
+            host[_LJ_WORDS * B + b * V * 16:_LJ_WORDS * B + (b + 1) * V * 16] = projs[b].reshape(-1)
+        device = torch.device(device)
+        st = torch.cuda.current_stream(device)
+        staging = {} if staging is None else staging
+        stg = staging.get(st.cuda_stream)
+        if stg is None or stg["host"].numel() < n:
+            stg = staging[st.cuda_stream] = dict(host=torch.empty((n,), dtype=torch.float32).pin_memory(), done=None)
+            stg["np"] = stg["host"].numpy()
+        if stg["done"] is not None and not stg["done"].query():
+            stg["done"].synchronize()                    # the previous call's copy out of the staging buffer (long done)
+        stg["np"][:n] = host
+        # this call's own device buffer: the join's autograd nodes keep it until their backward
+        self.dev = torch.empty((n,), dtype=torch.float32, device=device)
+        self.dev.copy_(stg["host"][:n], non_blocking=True)
+        stg["done"] = torch.cuda.Event()
+        stg["done"].record(st)
+        self.host, self.B, self.V, self.voxel_size, self.aligned = host, B, V, float(voxel_size), bool(aligned)
+        self.proj = [self.dev[_LJ_WORDS * B + b * V * 16:_LJ_WORDS * B + (b + 1) * V * 16].view(V, 4, 4) for b in range(B)]
+        self.pre = [None if pres[b] is None else self.dev[_LJ_WORDS * b:_LJ_WORDS * b + 12].view(3, 4) for b in range(B)]
+        self.scal = [tuple(float(x) for x in host[_LJ_WORDS * b + 13:_LJ_WORDS * b + 17]) + (int(host[_LJ_WORDS * b + 17] != 0),)
+                     + tuple(float(x) for x in host[_LJ_WORDS * b + 18:_LJ_WORDS * b + 21]) + (1 if aligned else 0,) for b in range(B)]
+
+
+def join_level_features(level, img_features_l: torch.Tensor, tables: JoinTables, prepared: Optional[Sequence[torch.Tensor]] = None
+                        ) -> torch.Tensor:
+    """DET:428-479 for one backbone level and all scenes in ONE launch (``ptx_level_join``, csrc/level_join.hip): every row of
+    ``level`` (a ``SparseLevel``: ``feats (n,Cb)`` fp32, ``coords (n,4)`` int32 with the scene in column 0, ``scene_rows``) gets the
+    image features of ``img_features_l (B,V,Ci,H,W)`` sampled at ``coords[:,1:4] * tables.voxel_size`` appended.  Returns
+    ``(n, Cb+Ci)`` fp32, bit for bit ``torch.cat([level.feats, torch.cat([batch_point_sample(...) per scene])], 1)``.
+
+    ``prepared``: the B workspaces ``prepare_features_many([img_features_l[b] for b in range(B)])`` returned (made earlier, e.g. on a
+    side stream), read in place; ``None``: made here.  Cb, Ci: multiples of 64 up to 512; a scene may have no row; ``n = 0`` launches
+    nothing.  With grad mode on and ``level.feats`` or ``img_features_l`` requiring grad the result is ONE autograd node whose backward
+    is one library call (``ptx_level_join_bwd``: no float atomics, bitwise reproducible); otherwise it is the plain forward."""
+    feats, coords, ends = level.feats, level.coords, [int(e) for e in level.scene_rows]
+    if not (isinstance(feats, torch.Tensor) and feats.is_cuda and coords.is_cuda and img_features_l.is_cuda):
+        raise RuntimeError("join_level_features (HIP) needs GPU tensors: there is no CPU path")
+    if img_features_l.dim() != 5:
+        raise ValueError(f"img_features_l: (B,V,C,H,W) expected, got {tuple(img_features_l.shape)}")
+    if img_features_l.dtype not in _DT:
+        img_features_l = img_features_l.float()
+    img = img_features_l.contiguous()
+    B, V, Ci, H, W = img.shape
+    n = feats.shape[0]
+    if feats.dim() != 2 or feats.dtype != torch.float32 or coords.dtype != torch.int32 or tuple(coords.shape) != (n, 4):
+        raise ValueError(f"level: feats (n,Cb) fp32 and coords (n,4) int32 expected, got {tuple(feats.shape)} {feats.dtype}, "
+                         f"{tuple(coords.shape)} {coords.dtype}")
+    Cb = feats.shape[1]
+    for name, c in (("Cb", Cb), ("Ci", Ci)):
+        if c < 64 or c > 512 or c % 64:
+            raise ValueError(f"join_level_features: {name}={c}: a multiple of 64 up to 512")
+    if B != tables.B or V != tables.V:
+        raise ValueError(f"join_level_features: img_features_l has B={B}, V={V}; the tables were built for B={tables.B}, V={tables.V}")
+    if len(ends) != B or any(e < s for s, e in zip([0] + ends[:-1], ends)) or ends[-1] != n:
+        raise ValueError(f"level.scene_rows={ends}: {B} ascending row ends, the last one n={n}")
+    dev = feats.device
+    if tables.dev.device != dev or img.device != dev:
+        raise ValueError("join_level_features: level, img_features_l and tables live on different devices")
+    if prepared is not None:
+        need = _abi.lib().ptx_point_sample_workspace_bytes(V, Ci, H, W)
+        if len(prepared) != B or any(p.numel() < need or p.device != dev for p in prepared):
+            raise RuntimeError("prepared: not the workspaces of prepare_features_many() for these feature maps")
+    elif n > 0:
+        prepared = prepare_features_many([img[b] for b in range(B)])
+    coords = coords.contiguous()
+    if torch.is_grad_enabled() and (feats.requires_grad or img.requires_grad):
+        return _LevelJoinFn.apply(feats, img, coords, ends, tables, prepared)
+    return _join(feats.detach().contiguous(), img, coords, tables, prepared, None)
+
+
+def join_level_features_per_scene(level, img_features_l: torch.Tensor, tables: JoinTables, prepared: Optional[Sequence[torch.Tensor]] = None
+                                  ) -> torch.Tensor:
+    """The route ``join_level_features`` replaces, DET:428-479 literally and with the same arguments: one ``batch_point_sample`` launch per
+    scene, a ``torch.cat`` over the scenes and one over the channels.  Same bits, forward and backward; kept for comparison and timing
+    (``GroundingDetector(fused_join=False)``, ``tools/detector_time.py``, the tests)."""
+    img = img_features_l if img_features_l.dtype in _DT else img_features_l.float()
+    lo = [0] + [int(e) for e in level.scene_rows[:-1]]
+    parts = []
+    for b, (s, e) in enumerate(zip(lo, level.scene_rows)):
+        pts = level.coords[s:e, 1:4].to(torch.float32) * tables.voxel_size
+        feats = img[b].contiguous()
+        prep = None if prepared is None else prepared[b]
+        if torch.is_grad_enabled() and feats.requires_grad:
+            parts.append(_PointSampleFn.apply(feats, prep, pts, tables.proj[b], tables.pre[b], tables.scal[b]))
+        else:
+            parts.append(_sample(feats, prep, pts, tables.proj[b], tables.pre[b], tables.scal[b], None))
+    return torch.cat([level.feats, torch.cat(parts)], 1)
+
+
+def _join(feats, img, coords, tables, prepared, valid_num):
+    """The ``ptx_level_join`` call: arguments already checked."""
+    import ctypes
+    B, V, Ci, H, W = img.shape
+    n, Cb = feats.shape
+    out = torch.empty((n, Cb + Ci), dtype=torch.float32, device=feats.device)
+    if n == 0:
+        return out
+    if feats.data_ptr() % 16:
+        feats = feats.clone()
+    ptrs = (ctypes.c_void_p * B)(*[p.data_ptr() for p in prepared])
+    _abi.check(_abi.lib().ptx_level_join(coords.data_ptr(), n, feats.data_ptr(), Cb, ptrs, tables.host.ctypes.data, tables.dev.data_ptr(),
+                                         B, V, Ci, H, W, tables.voxel_size, 1 if tables.aligned else 0, out.data_ptr(),
+                                         None if valid_num is None else valid_num.data_ptr(),
+                                         torch.cuda.current_stream(feats.device).cuda_stream), "ptx_level_join")
+    return out
+
+
+class _LevelJoinFn(torch.autograd.Function):
+    """``join_level_features`` as ONE autograd node.  Both halves of the output are linear in their inputs and the sampling's
+    backward needs the geometry only, so the coordinates, the tables and the forward's ``valid_num`` are kept -- no feature maps."""
+
+    @staticmethod
+    def forward(ctx, feats, img, coords, ends, tables, prepared):
+        valid_num = torch.empty((feats.shape[0],), dtype=torch.int32, device=feats.device)
+        out = _join(feats.detach().contiguous(), img, coords, tables, prepared, valid_num)
+        ctx.save_for_backward(coords, valid_num)
+        ctx.tables, ctx.ends, ctx.img_shape, ctx.img_dtype, ctx.Cb = tables, ends, tuple(img.shape), img.dtype, feats.shape[1]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        import ctypes
+        coords, valid_num = ctx.saved_tensors
+        tables, ends, Cb = ctx.tables, ctx.ends, ctx.Cb
+        B, V, Ci, H, W = ctx.img_shape
+        n, dev = coords.shape[0], coords.device
+        want_f, want_i = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dfeats = torch.empty((n, Cb), dtype=torch.float32, device=dev) if want_f else None
+        if n == 0:
+            dimg = torch.zeros(ctx.img_shape, dtype=ctx.img_dtype, device=dev) if want_i else None
+            return dfeats, dimg, None, None, None, None
+        dimg = torch.empty(ctx.img_shape, dtype=ctx.img_dtype, device=dev) if want_i else None   # every element is written
+        g = g.to(torch.float32).contiguous()
+        if g.data_ptr() % 16:
+            g = g.clone()
+        lib = _abi.lib()
+        bil = 1 if tables.aligned else 0
+        ws = None
+        if want_i:
+            rows = max(e - s for s, e in zip([0] + ends[:-1], ends))
+            nbytes = lib.ptx_level_join_bwd_workspace_bytes(rows, V, H, W, bil)
+            if nbytes == 0:
+                raise RuntimeError(f"level-join backward: rows={rows} V={V} H={H} W={W} is outside the 32-bit index range")
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        _abi.check(lib.ptx_level_join_bwd(coords.data_ptr(), n, (ctypes.c_int32 * B)(*ends), g.data_ptr(), Cb, valid_num.data_ptr(),
+                                          tables.host.ctypes.data, tables.dev.data_ptr(), B, V, Ci, H, W, tables.voxel_size, bil,
+                                          None if dfeats is None else dfeats.data_ptr(), None if dimg is None else dimg.data_ptr(),
+                                          _DT[ctx.img_dtype], None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
+                                          torch.cuda.current_stream(dev).cuda_stream), "ptx_level_join_bwd")
+        return dfeats, dimg, None, None, None, None

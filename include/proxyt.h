@@ -1139,6 +1139,37 @@ PTX_API int ptx_train_step_layout(const PtxTrainStep *a, PtxTrainStepLayout *out
 PTX_API int ptx_train_step_fwd(const PtxTrainStep *a, void *stream);
 PTX_API int ptx_train_step_bwd(const PtxTrainStep *a, void *stream);
 
+/* ------------------------------------------------------------------ the CLIP text encoder (ABI 13, by addition)
+ * The eval forward of CLIPTextModel up to last_hidden_state (csrc/text_encoder.hip), restated in numpy by text_encoder_host.py: pre-norm
+ * layers of width C = 64 H (up to 1280; head dimension 64 only), MLP width I (a multiple of 64 up to 5120) with quick-GELU, 1 <= T <= 256
+ * tokens and no more than the position table holds, 1 <= B <= 64 texts; n = B T rows.  The same rules: fp32, no float atomics, fixed
+ * summation orders (two calls give the same bits, and a row's bits do not depend on the other rows), everything on `stream`, no host
+ * wait, host checks before anything is enqueued.
+ *
+ * out (B,T,C): out[b,t] = token_embedding[ids[b,t]] + position_embedding[t], ids (B,T) int64 on the device.  An id outside [0, vocab)
+ * reads nothing and fills its row with NaN.  One launch. */
+PTX_API int ptx_txt_embed(const long long *ids, int B, int T, const float *token_embedding, const float *position_embedding, int vocab,
+                          int positions, int C, float *out, void *stream);
+/* out (n,Cout) = act(LayerNorm(x) @ weight^T + bias) on x (n,Cin): per row the mean, then the centred variance, rstd = 1 / sqrtf(var + eps),
+ * written once to stats (n,2) = (mean, rstd), workspace; (x - mean) rstd ln_weight + ln_bias applied in the operand load; act: 0 none,
+ * 1 quick-GELU v / (1 + expf(-1.702 v)).  bias optional.  Cin: a multiple of 64 up to 1280; Cout: a multiple of 64 up to 5120.  Two
+ * launches. */
+PTX_API int ptx_txt_ln_linear(const float *x, long n, const float *ln_weight, const float *ln_bias, float eps, const float *weight,
+                              const float *bias, int Cin, int Cout, int act, float *out, float *stats, void *stream);
+/* Causal self attention of H heads of 64 on qkv (B,T,3 C) = [q|k|v]: out (B,T,C), heads merged.  q is scaled by 1/8; key j is admitted for
+ * query t iff j <= t and mask[b,j] (mask (B,T), 1 = a token; NULL: every key is one).  A masked key is never read, a key tile without an
+ * admitted key is skipped, a query without an admitted key gets zeros; every one of the T query rows is computed.  One launch. */
+PTX_API int ptx_txt_attention(const float *qkv, const uint8_t *mask, int B, int T, int H, float *out, void *stream);
+/* out (n,Cout) = x @ weight^T + bias (+ residual), Cin and Cout multiples of 64 up to 5120; out may be residual, not x.  Up to 768 input
+ * channels: one launch, ascending k.  Beyond: the contraction is cut into ceil(Cin / 768) slices of equal length, each slice's sums go to
+ * the workspace (ptx_txt_linear_workspace_bytes(n, Cin, Cout) bytes, 16-byte aligned; 0 without slices or out of range) and a second
+ * launch adds the slices in ascending order, then the bias, then the residual. */
+PTX_API size_t ptx_txt_linear_workspace_bytes(long n, int Cin, int Cout);
+PTX_API int ptx_txt_linear(const float *x, long n, const float *weight, const float *bias, int Cin, int Cout, const float *residual,
+                           float *out, void *workspace, size_t ws_bytes, void *stream);
+/* out (n,C) = LayerNorm(x), the statistics as in ptx_txt_ln_linear; C: a multiple of 64 up to 1280.  One launch. */
+PTX_API int ptx_txt_ln(const float *x, long n, int C, const float *weight, const float *bias, float eps, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ Only what the path needs lives here:
 * ``decoder.GroundingDecoder``               -- the transformer decoder behind it (self, text and scene attention, FFN, box refinement);
 * ``grounding_loss.GroundingLoss``           -- the head's loss behind the decoder: 9-DoF box IoU, Hungarian match costs, focal and corner loss;
 * ``detector.GroundingDetector``             -- all of the above as one module: ``loss`` and ``predict`` of the whole grounder;
+* ``text_encoder.ClipTextEncoder``           -- the CLIP text encoder in front of it: token ids to ``last_hidden_state``;
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -27,6 +28,7 @@ from .query_select import QuerySelect
 from .decoder import GroundingDecoder
 from .grounding_loss import GroundingLoss
 from .detector import GroundingDetector
+from .text_encoder import ClipTextEncoder
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "GroundingDecoder", "GroundingDetector", "GroundingLoss", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "ClipTextEncoder", "GroundingDecoder", "GroundingDetector", "GroundingLoss", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
 __version__ = "0.1.0"

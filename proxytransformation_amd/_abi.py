@@ -287,6 +287,12 @@ SIGNATURES.update({
     "ptx_train_attn_tmp_floats": (_Z, [_I, _I, _I, _I, _I]),
     "ptx_train_attn_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P]),
     "ptx_train_attn_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _U64, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "ptx_txt_embed": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "ptx_txt_ln_linear": (_I, [_P, _L, _P, _P, _F, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "ptx_txt_attention": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "ptx_txt_linear_workspace_bytes": (_Z, [_L, _I, _I]),
+    "ptx_txt_linear": (_I, [_P, _L, _P, _P, _I, _I, _P, _P, _P, _Z, _P]),
+    "ptx_txt_ln": (_I, [_P, _L, _I, _P, _P, _F, _P, _P]),
 })
 
 _lib: Optional[C.CDLL] = None

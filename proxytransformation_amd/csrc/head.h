@@ -1,4 +1,4 @@
-// What query_select.hip, decoder.hip and neck.hip share: the limits of the stages behind the neck, the main loop of the 64 x 64 NT tile
+// What query_select.hip, decoder.hip, neck.hip and text_encoder.hip share: the limits of the stages behind the neck, the main loop of the 64 x 64 NT tile
 // on the exact-fp32 matrix instruction with its C/D row formula and the two epilogues, the 16-lane row reduction with the 9-value box
 // head, and the radix threshold search of the two top-k kernels.  Orders of addition are part of each piece: the callers' bits depend
 // on them.

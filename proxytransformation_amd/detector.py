@@ -10,9 +10,12 @@ backbone and the text encoder, as one module -- the stages of this package calle
     decoder (after the renaming of DET:605-617)     DET:582-621    decoder.GroundingDecoder
     bbox_head: scores, loss / predict               DET:700, 787   GroundingDecoder.head_scores, grounding_loss.GroundingLoss
 
-The 2D backbone and the text encoder stay outside: the detector takes their outputs (``img_features``: one ``(B,V,C_l,H_l,W_l)`` per
-level; ``encoded_text (B,T,text_width)`` with ``text_token_mask``).  ``share_pred_layer=True`` is the shipped head: ONE classification
-and ONE regression branch (``self.query_select``) serve the query selection, every decoder layer and the scores."""
+The 2D backbone stays outside, and by default the text encoder too: the detector takes their outputs (``img_features``: one
+``(B,V,C_l,H_l,W_l)`` per level; ``encoded_text (B,T,text_width)`` with ``text_token_mask``).  With ``text_encoder=`` (a
+``text_encoder.ClipTextEncoder`` or its keywords) the detector holds the encoder and ``loss`` / ``predict`` / ``forward`` take
+``input_ids=`` and ``attention_mask=`` in place of the encoded text (DET:661-668, 740-753 behind the tokenizer).
+``share_pred_layer=True`` is the shipped head: ONE classification and ONE regression branch (``self.query_select``) serve the query
+selection, every decoder layer and the scores."""
 from __future__ import annotations
 
 import inspect
@@ -29,11 +32,14 @@ from .module import ProxyTransformationNormReverse
 from .neck import MinkNeck
 from .query_select import QuerySelect
 from .registry import MODELS
+from .text_encoder import ClipTextEncoder
 
 __all__ = ["GroundingDetector"]
 
 #: the prefixes of a reference checkpoint that belong to modules outside this one: skipped by ``load_reference_state_dict``
+#: (``text_encoder.`` only while the detector holds no encoder)
 _OUTSIDE = ("backbone.", "text_encoder.")
+_TEXT = "text_encoder."
 
 
 def _build(who: str, name: str, cfg, cls, differentiable: bool):
@@ -55,11 +61,14 @@ def _build(who: str, name: str, cfg, cls, differentiable: bool):
 
 class GroundingDetector(nn.Module):
     """``GroundingDetector(preshape, backbone_3d, neck_3d, decoder, bbox_head, num_queries=256, voxel_size=0.01, use_xyz_feat=True,
-    coord_type='DEPTH', train_cfg=None, test_cfg=None, text_width=768, *, differentiable=False, matcher='host', fused_join=True)``:
+    coord_type='DEPTH', train_cfg=None, test_cfg=None, text_width=768, *, differentiable=False, matcher='host', fused_join=True,
+    text_encoder=None)``:
     the reference's keywords (configs/grounding/*.py, ``model=``), each child a config dict or a ready module.  ``bbox_head`` is the
     ``GroundingHead`` config: it becomes ``self.bbox_head`` (``GroundingLoss``: loss and predict, no parameters) and ``self.query_select``
     (``QuerySelect``: the shared branches).  ``text_width``: the text encoder's hidden size, ``text_feat_map = nn.Linear(text_width,
-    embed_dims)``.
+    embed_dims)``.  ``text_encoder``: None (the default: the module, its ``state_dict`` and its methods are what they were), a
+    ``ClipTextEncoder`` or its keyword dict; ``text_width`` then defaults to its ``hidden_size`` and must equal it.  The encoder is never
+    trained (``lr_mult=0.0`` in the reference): it runs under ``no_grad`` and its parameters receive no gradient.
 
     Inputs of every method: ``points`` list of B ``(N_b,3)``; ``encoded_text (B,T,text_width)``, ``text_token_mask (B,T)`` bool (True =
     token); ``img_features`` one ``(B,V,C_l,H_l,W_l)`` per backbone level; ``scenes`` one dict per sample with ``depth2img =
@@ -74,9 +83,19 @@ class GroundingDetector(nn.Module):
 
     def __init__(self, preshape, backbone_3d, neck_3d, decoder, bbox_head, num_queries: int = 256, voxel_size: float = 0.01,
                  use_xyz_feat: bool = True, coord_type: str = "DEPTH", train_cfg: Optional[dict] = None, test_cfg: Optional[dict] = None,
-                 text_width: int = 768, *, differentiable: bool = False, matcher: str = "host", fused_join: bool = True):
+                 text_width: Optional[int] = None, *, differentiable: bool = False, matcher: str = "host", fused_join: bool = True,
+                 text_encoder=None):
         super().__init__()
         who = "GroundingDetector"
+        if text_encoder is not None:
+            text_encoder = _build(who, "text_encoder", text_encoder, ClipTextEncoder, False)
+            if not isinstance(text_encoder, ClipTextEncoder):
+                raise TypeError(f"{who}: text_encoder must be a ClipTextEncoder or its keyword dict, got {type(text_encoder).__name__}")
+            if text_width is not None and int(text_width) != text_encoder.hidden_size:
+                raise ValueError(f"{who}: text_width={text_width} differs from the text encoder's hidden_size={text_encoder.hidden_size}")
+            text_width = text_encoder.hidden_size
+        elif text_width is None:
+            text_width = 768
         self.differentiable, self.fused_join = bool(differentiable), bool(fused_join)
         d = self.differentiable
         if not use_xyz_feat:
@@ -125,6 +144,7 @@ class GroundingDetector(nn.Module):
                                         box_coder=self.bbox_head.box_coder, differentiable=d)
         self.text_feat_map = nn.Linear(int(text_width), self.embed_dims)
         self.text_width = int(text_width)
+        self.text_encoder = text_encoder     # None: no child, no entry in the state dict
         self._staging: dict = {}            # per stream: the pinned staging buffer of the join tables
 
     def __deepcopy__(self, memo):
@@ -200,6 +220,30 @@ class GroundingDetector(nn.Module):
                 trace.update(points=outs, coordinates=coords, features=feats, scene_rows=ends, levels=levels, joined=joined, tables=tables)
             return self.neck_3d(joined, B, keep_out=keep_out)                                         # DET:482
 
+    def encode_text(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None):
+        """``(encoded_text (B,T,text_width), text_token_mask = attention_mask.bool())`` from the tokenizer's output (DET:661-668): the
+        text encoder's ``last_hidden_state``, detached.  ``attention_mask=None``: every position is a token."""
+        if self.text_encoder is None:
+            raise ValueError("GroundingDetector: input_ids need a text encoder; construct the detector with text_encoder=")
+        encoded = self.text_encoder(input_ids, attention_mask)
+        if attention_mask is None:
+            mask = torch.ones(tuple(input_ids.shape), dtype=torch.bool, device=encoded.device)
+        else:
+            mask = (attention_mask != 0).to(encoded.device)
+        return encoded, mask
+
+    def _text(self, encoded_text, text_token_mask, input_ids, attention_mask):
+        """The text operands of a call: the encoded text as given, or the encoder's output for ``input_ids`` / ``attention_mask``."""
+        if input_ids is None:
+            if attention_mask is not None:
+                raise ValueError("GroundingDetector: attention_mask goes with input_ids; with encoded_text pass text_token_mask")
+            if encoded_text is None or text_token_mask is None:
+                raise ValueError("GroundingDetector: encoded_text and text_token_mask, or input_ids (and attention_mask), are required")
+            return encoded_text, text_token_mask
+        if encoded_text is not None or text_token_mask is not None:
+            raise ValueError("GroundingDetector: input_ids / attention_mask take the place of encoded_text / text_token_mask; pass one pair")
+        return self.encode_text(input_ids, attention_mask)
+
     def map_text(self, encoded_text: torch.Tensor, _mode: Optional[bool] = None) -> torch.Tensor:
         """``text_feat_map(encoded_text)`` (DET:659) through ``decoder.linear``."""
         rec = self._records(encoded_text) if _mode is None else _mode
@@ -228,9 +272,11 @@ class GroundingDetector(nn.Module):
                                                                      differentiable=self.differentiable and mode)
             return head
 
-    def forward(self, points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape=(480, 480), bbox=None,
-                trace: Optional[dict] = None) -> dict:
-        """The whole chain up to the head's outputs (``forward_transformer``'s dict)."""
+    def forward(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=(480, 480), bbox=None,
+                trace: Optional[dict] = None, *, input_ids=None, attention_mask=None) -> dict:
+        """The whole chain up to the head's outputs (``forward_transformer``'s dict).  ``input_ids=`` / ``attention_mask=`` (with a text
+        encoder) take the place of ``encoded_text`` / ``text_token_mask``."""
+        encoded_text, text_token_mask = self._text(encoded_text, text_token_mask, input_ids, attention_mask)
         mode = self._records(encoded_text, *img_features)      # one decision for the whole chain, from the caller's inputs
         text_dict = dict(text_feats=self.map_text(encoded_text, mode), text_token_mask=text_token_mask)
         keep: list = []
@@ -242,17 +288,20 @@ class GroundingDetector(nn.Module):
             trace.update(text_feats=text_dict["text_feats"], neck=(feats, scores, xyz), keep=keep, select=sel)
         return head
 
-    def loss(self, points, encoded_text, text_token_mask, img_features, scenes, gt_bboxes, positive_maps, img_pad_shape=(480, 480),
-             bbox=None, trace: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+    def loss(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, gt_bboxes=None, positive_maps=None,
+             img_pad_shape=(480, 480), bbox=None, trace: Optional[dict] = None, *, input_ids=None,
+             attention_mask=None) -> Dict[str, torch.Tensor]:
         """DET:623-705: the reference's loss dict (``loss_cls``, ``loss_bbox``, ``d{i}.loss_cls``, ``d{i}.loss_bbox``)."""
+        encoded_text, text_token_mask = self._text(encoded_text, text_token_mask, input_ids, attention_mask)
         head = self.forward(points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape, bbox, trace)
         return self.bbox_head.loss(head["all_layers_cls_scores"], head["all_layers_pred_bboxes"], text_token_mask, gt_bboxes, positive_maps)
 
-    def predict(self, points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape=(480, 480), bbox=None,
-                trace: Optional[dict] = None) -> List[dict]:
+    def predict(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=(480, 480), bbox=None,
+                trace: Optional[dict] = None, *, input_ids=None, attention_mask=None) -> List[dict]:
         """DET:707-794 with ``GroundingHead.predict`` (grounding_head.py:566-604): per scene ``dict(bboxes_3d (K,9), scores_3d (K,),
         target_scores_3d (K,))``; the reference regards the scores as the target scores at inference."""
-        head = self.forward(points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape, bbox, trace)
+        head = self.forward(points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape, bbox, trace, input_ids=input_ids,
+                            attention_mask=attention_mask)
         boxes, scores = self.bbox_head.predict(head["all_layers_cls_scores"], head["all_layers_pred_bboxes"])
         return [dict(bboxes_3d=boxes[b], scores_3d=scores[b], target_scores_3d=scores[b]) for b in range(boxes.shape[0])]
 
@@ -269,11 +318,13 @@ class GroundingDetector(nn.Module):
         return batch.points, batch.bbox
 
     # ------------------------------------------------------------------------------------------------------------- the host chain
-    def forward_host(self, points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape=(480, 480), dtype=None,
-                     decisions: Optional[dict] = None, gt_bboxes=None, positive_maps=None, host=None) -> dict:
+    def forward_host(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=(480, 480),
+                     dtype=None, decisions: Optional[dict] = None, gt_bboxes=None, positive_maps=None, host=None, *, input_ids=None,
+                     attention_mask=None) -> dict:
         """The same chain (eval mode) from the stages' own host restatements in numpy ``dtype`` (float64, the default, or float32):
         ``host.forward`` (the preshape) -> ``host.voxelize`` -> ``MinkResNet.forward_host`` -> ``host.point_sample`` per scene and
-        level plus the two concatenations -> ``MinkNeck.forward_host`` -> ``text_feat_map`` -> ``QuerySelect.forward_host`` -> the
+        level plus the two concatenations -> ``MinkNeck.forward_host`` -> (with ``input_ids=``: ``ClipTextEncoder.forward_host`` ->)
+        ``text_feat_map`` -> ``QuerySelect.forward_host`` -> the
         renaming of DET:605-617 -> ``GroundingDecoder.forward_host`` -> ``contrastive_scores_host`` -> ``predict_host`` (and ``loss_host``
         when ``gt_bboxes`` / ``positive_maps`` are given).  It calls no device code.  ``decisions``: the device's discrete decisions,
         handed in where two precisions may differ -- ``points`` (the preshape's output clouds: which points survive, and through the
@@ -290,6 +341,15 @@ class GroundingDetector(nn.Module):
         from . import decoder_host, grounding_loss_host as glh
         from .pipeline import projection_matrices
         dt = np.dtype(np.float64 if dtype is None else dtype)
+        if input_ids is not None:
+            if encoded_text is not None or text_token_mask is not None:
+                raise ValueError("GroundingDetector.forward_host: input_ids / attention_mask take the place of encoded_text / text_token_mask")
+            if self.text_encoder is None:
+                raise ValueError("GroundingDetector.forward_host: input_ids need a text encoder; construct the detector with text_encoder=")
+            ids = input_ids.detach().cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)
+            encoded_text = self.text_encoder.forward_host(ids, attention_mask, dtype=dt)
+            text_token_mask = np.ones(ids.shape, bool) if attention_mask is None else \
+                (attention_mask.detach().cpu().numpy() if isinstance(attention_mask, torch.Tensor) else np.asarray(attention_mask)) != 0
         decisions = dict(decisions or {})
         arr = lambda t, d=None: (t.detach().cpu().float().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(d or dt)   # noqa: E731
         B = len(points)
@@ -376,14 +436,23 @@ class GroundingDetector(nn.Module):
 
     def reference_state_dict(self) -> Dict[str, torch.Tensor]:
         """The state dict under the reference's names: ``preshape.*``, ``backbone_3d.*``, ``neck_3d.*``, ``decoder.*``,
-        ``text_feat_map.*`` and the ``NL + 1`` aliases ``bbox_head.cls_branches.{i}.*`` / ``bbox_head.reg_branches.{i}.*``."""
+        ``text_feat_map.*``, with a text encoder ``text_encoder.text_model.*``, and the ``NL + 1`` aliases
+        ``bbox_head.cls_branches.{i}.*`` / ``bbox_head.reg_branches.{i}.*``."""
         sd = self.state_dict()
         return {ref: sd[own] for ref, own in self._reference_names()}
 
     def load_reference_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True) -> dict:
-        """Loads a reference checkpoint's ``state_dict``.  ``backbone.*`` and ``text_encoder.*`` belong to modules outside this one:
-        skipped and listed.  The aliases of a shared branch must be equal (``ValueError`` naming the key).  ``strict``: a missing
-        or unexpected key raises ``KeyError``.  Returns ``dict(skipped, missing, unexpected)``."""
+        """Loads a reference checkpoint's ``state_dict``.  ``backbone.*`` and -- while the detector holds no text encoder --
+        ``text_encoder.*`` belong to modules outside this one: skipped and listed.  With a text encoder its tensors are loaded, under
+        ``text_encoder.text_model.*`` or ``text_encoder.*`` (``ClipTextEncoder.normalise_names``), a ``position_ids`` buffer ignored.
+        The aliases of a shared branch must be equal (``ValueError`` naming the key).  ``strict``: a missing or unexpected key raises
+        ``KeyError``.  Returns ``dict(skipped, missing, unexpected)``."""
+        outside = _OUTSIDE
+        if self.text_encoder is not None:
+            outside = tuple(p for p in _OUTSIDE if p != _TEXT)
+            text = ClipTextEncoder.normalise_names({k[len(_TEXT):]: v for k, v in state_dict.items() if k.startswith(_TEXT)})
+            state_dict = {k: v for k, v in state_dict.items() if not k.startswith(_TEXT)}
+            state_dict.update({_TEXT + k: v for k, v in text.items()})
         wanted = self._reference_names()
         own_sd, first, missing = {}, {}, []
         for ref, own in wanted:
@@ -398,8 +467,8 @@ class GroundingDetector(nn.Module):
             else:
                 own_sd[own], first[own] = t, ref
         names = {ref for ref, _ in wanted}
-        skipped = sorted(k for k in state_dict if k.startswith(_OUTSIDE))
-        unexpected = sorted(k for k in state_dict if k not in names and not k.startswith(_OUTSIDE))
+        skipped = sorted(k for k in state_dict if k.startswith(outside))
+        unexpected = sorted(k for k in state_dict if k not in names and not k.startswith(outside))
         if strict and (missing or unexpected):
             raise KeyError(f"GroundingDetector.load_reference_state_dict(strict=True): missing {missing[:8]}"
                            f"{' ...' if len(missing) > 8 else ''}, unexpected {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")

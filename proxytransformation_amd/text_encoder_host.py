@@ -18,7 +18,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
-__all__ = ["attention_host", "embed_host", "forward_host", "layer_norm_host", "quick_gelu_host"]
+__all__ = ["attention_host", "embed_host", "forward_host", "layer_norm_host", "linear_host", "ln_linear_host", "quick_gelu_host",
+           "row_stats_host"]
 
 HEAD_DIM = 64
 
@@ -33,18 +34,42 @@ def embed_host(ids: np.ndarray, token_embedding: np.ndarray, position_embedding:
     return x
 
 
-def layer_norm_host(x: np.ndarray, weight: np.ndarray, bias: np.ndarray, eps: float) -> np.ndarray:
+def row_stats_host(x: np.ndarray, eps: float):
+    """``(mean, rstd)`` of every row, each of ``x.shape[:-1]``: the row mean first, then ``1 / sqrt(var + eps)`` of the centred variance --
+    what ``ptx_txt_ln_linear`` leaves in ``stats[:, 0]`` and ``stats[:, 1]``."""
     dt = x.dtype
     mean = x.mean(-1, keepdims=True, dtype=dt)
     d = x - mean
     var = (d * d).mean(-1, keepdims=True, dtype=dt)
     rstd = dt.type(1.0) / np.sqrt(var + dt.type(eps))
-    return d * rstd * weight + bias
+    return mean[..., 0], rstd[..., 0]
+
+
+def layer_norm_host(x: np.ndarray, weight: np.ndarray, bias: np.ndarray, eps: float) -> np.ndarray:
+    mean, rstd = row_stats_host(x, eps)
+    return (x - mean[..., None]) * rstd[..., None] * weight + bias
 
 
 def quick_gelu_host(v: np.ndarray) -> np.ndarray:
     dt = v.dtype
     return v / (dt.type(1.0) + np.exp(dt.type(-1.702) * v))
+
+
+def ln_linear_host(x: np.ndarray, ln_w: np.ndarray, ln_b: np.ndarray, eps: float, w: np.ndarray, bias: Optional[np.ndarray],
+                   act: int) -> np.ndarray:
+    """``act(LayerNorm(x) @ w^T + bias)`` (``ptx_txt_ln_linear``): ``w (Cout,Cin)``, ``bias (Cout)`` or None; act 0: none, 1: quick-GELU."""
+    v = layer_norm_host(x, ln_w, ln_b, eps) @ w.T
+    if bias is not None:
+        v = v + bias
+    return quick_gelu_host(v) if act else v
+
+
+def linear_host(x: np.ndarray, w: np.ndarray, bias: Optional[np.ndarray], residual: Optional[np.ndarray]) -> np.ndarray:
+    """``x @ w^T + bias + residual`` in that order (``ptx_txt_linear``): ``w (Cout,Cin)``; ``bias (Cout)`` and ``residual`` may be None."""
+    v = x @ w.T
+    if bias is not None:
+        v = v + bias
+    return v if residual is None else v + residual
 
 
 def attention_host(qkv: np.ndarray, mask: Optional[np.ndarray], num_heads: int) -> np.ndarray:
@@ -82,14 +107,12 @@ def forward_host(params: Dict[str, np.ndarray], input_ids, attention_mask, num_h
         layers += 1
     for i in range(layers):
         L = lambda name, i=i: P(f"encoder.layers.{i}.{name}")      # noqa: E731
-        h = layer_norm_host(x, L("layer_norm1.weight"), L("layer_norm1.bias"), eps)
         w = np.concatenate([L("self_attn.q_proj.weight"), L("self_attn.k_proj.weight"), L("self_attn.v_proj.weight")])
         bq = np.concatenate([L("self_attn.q_proj.bias"), L("self_attn.k_proj.bias"), L("self_attn.v_proj.bias")])
-        a = attention_host(h @ w.T + bq, mask, num_heads)
-        x = x + (a @ L("self_attn.out_proj.weight").T + L("self_attn.out_proj.bias"))
-        h = layer_norm_host(x, L("layer_norm2.weight"), L("layer_norm2.bias"), eps)
-        h = quick_gelu_host(h @ L("mlp.fc1.weight").T + L("mlp.fc1.bias"))
-        x = x + (h @ L("mlp.fc2.weight").T + L("mlp.fc2.bias"))
+        a = attention_host(ln_linear_host(x, L("layer_norm1.weight"), L("layer_norm1.bias"), eps, w, bq, 0), mask, num_heads)
+        x = linear_host(a, L("self_attn.out_proj.weight"), L("self_attn.out_proj.bias"), x)
+        h = ln_linear_host(x, L("layer_norm2.weight"), L("layer_norm2.bias"), eps, L("mlp.fc1.weight"), L("mlp.fc1.bias"), 1)
+        x = linear_host(h, L("mlp.fc2.weight"), L("mlp.fc2.bias"), x)
     out = layer_norm_host(x, P("final_layer_norm.weight"), P("final_layer_norm.bias"), eps)
     assert out.dtype == dt
     return out

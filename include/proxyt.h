@@ -399,7 +399,10 @@ PTX_API int ptx_ingest_draw(int V, int H, int W, int per_view, int N, uint64_t k
  * device-mapped pinned host memory: published with system scope as soon as the count is KNOWN (preset to -1 and poll with
  * ptx_wait_counts instead of draining the stream); the rows themselves are ordered on `stream` like any other result.
  * Rows written == PTX_VOX_BROKEN (0x7fffffff): a tile of the single-pass emit gave up waiting for the tiles in front of it
- * (2^24 polls); rows, inverse and the count of that call are invalid. */
+ * (2^24 polls); rows, inverse and the count of that call are invalid.
+ * The key range: a voxel index is kept when it lies in [-2^18, 2^18) on every axis (scene < 64).  A point with a NaN or infinite
+ * coordinate has no voxel: it is OUTSIDE the range and is counted in nvox_overflow[1] like a coordinate past +-2^18 (a NaN quotient
+ * would convert to the integer 0; the range test therefore asks for a finite quotient first). */
 #define PTX_VOX_BROKEN 0x7fffffff
 PTX_API size_t ptx_voxel_workspace_bytes(int B, int Ncap);
 PTX_API int ptx_voxelize(const float *points, const int32_t *counts, int B, int Ncap, float voxel_size, int32_t *coords,
@@ -421,8 +424,9 @@ PTX_API int ptx_voxelize_rep(const float *points, const int32_t *counts, int B, 
  * respect to the points: dfeats (nvox,3) fp32; inverse (B,Ncap), rep and counts (B, device) as ptx_voxelize_rep wrote / read them;
  * dpoints (B,Ncap,3) fp32.  Point (b,i), i < counts[b], receives dfeats[inverse[b,i]] if rep[inverse[b,i]] == b * Ncap + i and exact
  * zeros otherwise (the other points of a voxel).  One per-point pass on `stream`: every element of dpoints below the counts is
- * written exactly once, zeros included (rows past the counts are unspecified) -- no memset, no float atomics, no workspace, no host
- * wait, bitwise reproducible.  The coordinates (floor) get no gradient.  dfeats may be NULL when nvox == 0. */
+ * written exactly once, zeros included (rows past a count: when Ncap is a multiple of 4 and inverse / dpoints are 16-byte aligned,
+ * the rest of the group of four points in which a scene's count ends is written as +0.0; nothing else past a count is touched) --
+ * no memset, no float atomics, no workspace, no host wait, bitwise reproducible.  The coordinates (floor) get no gradient.  dfeats may be NULL when nvox == 0. */
 PTX_API int ptx_voxel_features_bwd(const float *dfeats, int nvox, const int32_t *inverse, const int32_t *rep, const int32_t *counts,
                            int B, int Ncap, float *dpoints, void *stream);
 /* ABI 12.  The coordinates of a COARSER MinkowskiEngine level over voxel rows the calls above produced -- what a strided layer of the
@@ -431,7 +435,9 @@ PTX_API int ptx_voxel_features_bwd(const float *dfeats, int nvox, const int32_t 
  * coords_in (rows,4) int32 (scene, x, y, z), scene b's rows [in_scene_end[b-1], in_scene_end[b]) with in_scene_end a [host] array
  * of B ints (read during the call); every row maps to floor(c / stride) * stride (stride: a power of two), one output row per
  * distinct result in first-occurrence order: coords (rows,4) int32 and points (rows,3) fp32 = coordinate * voxel_size.
- * nvox_overflow / scene_end / workspace as ptx_voxelize_ex (workspace: ptx_voxel_workspace_bytes(B, largest scene's rows)). */
+ * nvox_overflow / scene_end / workspace as ptx_voxelize_ex (workspace: ptx_voxel_workspace_bytes(B, largest scene's rows)).  The key
+ * range applies to the COARSE index: a row is kept when floor(c / stride) lies in [-2^18, 2^18) on every axis, i.e. c in
+ * [-2^18 * stride, 2^18 * stride); any other row is counted in nvox_overflow[1]. */
 PTX_API int ptx_voxel_coarsen(const int32_t *coords_in, const int32_t *in_scene_end, int B, int stride, float voxel_size,
                       int32_t *coords, float *points, int32_t *nvox_overflow, int32_t *scene_end, void *workspace, size_t ws_bytes,
                       void *stream);

@@ -453,7 +453,11 @@ def voxelize(outs, voxel_size: float = 0.01):
     ``p / voxel_size`` (fp32 division) to int32 and prepends the scene index; ``ME.SparseTensor`` keeps one row per
     distinct coordinate.  MinkowskiEngine is not vendored under /root/reference and its choice of the surviving
     duplicate / row order is unspecified ("random subsample"): pinned to the first point of every voxel in (scene,
-    point) order.  Returns coords (Nv,4) int32, feats (Nv,3) f32, list of per-scene inverse maps."""
+    point) order.  Returns coords (Nv,4) int32, feats (Nv,3) f32, list of per-scene inverse maps.
+
+    The inputs are finite points whose voxel lies in [-2^18, 2^18) per axis.  The device refuses anything else: a coordinate past
+    that range AND a NaN or infinite coordinate are "outside" (counted, ``quantize`` raises); this restatement does not model the
+    refusal (numpy's float -> int32 conversion of a NaN is unspecified)."""
     coords, feats = [], []
     for b, p in enumerate(outs):
         p = _f32(p)

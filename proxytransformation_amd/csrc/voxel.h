@@ -39,8 +39,10 @@ __device__ __forceinline__ bool vox_key(const VoxArgs &a, int b, int i, int (&v)
         const float *p = a.points + ((size_t)b * a.Ncap + i) * 3;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            v[d] = (int)floorf(__fdiv_rn(p[d], a.voxel_size));            // torch: floor(p / voxel_size), fp32
-            ok = ok && v[d] >= -kVoxBias && v[d] < kVoxBias;
+            const float q = floorf(__fdiv_rn(p[d], a.voxel_size));        // torch: floor(p / voxel_size), fp32
+            v[d] = (int)q;
+            // a NaN quotient converts to 0 and would pass the integer check: only a finite quotient can be inside the range
+            ok = ok && __builtin_isfinite(q) && v[d] >= -kVoxBias && v[d] < kVoxBias;
         }
     }
     key = ((unsigned long long)b << 57) | ((unsigned long long)(v[0] + kVoxBias) << 38) |

@@ -91,8 +91,11 @@ def bound_terms(n, d, w, nvalid, dout, shape):
     return to(k[:, None]), to(S), to(E)
 
 
-def check_bound(got, want, k, S, what):
-    """|got - want| <= (k + 4) 2^-23 sum|terms| for EVERY element; prints the worst ratio before asserting."""
+def check_bound(got, want, k, S, what, require_max_k=None):
+    """|got - want| <= (k + 4) 2^-23 sum|terms| for EVERY element; prints the worst ratio before asserting.  ``require_max_k``: the
+    longest list of the case must reach it (a case that is about long lists fails when its geometry does not produce them)."""
+    if require_max_k is not None:
+        assert int(k.max()) >= require_max_k, f"{what}: longest list {int(k.max())} < {require_max_k}"
     err = np.abs(got.astype(np.float64) - want.astype(np.float64))
     lim = (k + 4.0) * EPS * S
     ratio = np.where(lim > 0, err / np.where(lim > 0, lim, 1.0), np.where(err > 0, np.inf, 0.0))

@@ -1176,6 +1176,33 @@ PTX_API int ptx_txt_linear(const float *x, long n, const float *weight, const fl
 /* out (n,C) = LayerNorm(x), the statistics as in ptx_txt_ln_linear; C: a multiple of 64 up to 1280.  One launch. */
 PTX_API int ptx_txt_ln(const float *x, long n, int C, const float *weight, const float *bias, float eps, float *out, void *stream);
 
+/* ------------------------------------------------------------------ the image backbone's convolutions (ABI 13, by addition)
+ * The dense 2D convolutions of mmdet.ResNet (Bottleneck depths, every BatchNorm frozen) on NCHW float32 activations (csrc/conv2d.hip),
+ * restated in numpy by image_backbone_host.py.  fp32 on the exact-fp32 matrix instruction (the stem: plain FMA), no float atomics, a
+ * fixed k order: an image's bits depend neither on the batch size nor on its place in the batch; everything on `stream`, no host wait;
+ * host checks (PTX_EINVAL with the numbers in the message) come before anything is enqueued.  The epilogue of all three, in the order of
+ * ptx_sparse_conv3d: v * scale[co] + shift[co] (two roundings), + residual, ReLU; scale, shift, residual may be NULL.  The ReLU keeps a
+ * NaN, and so does the stem's max-pool: a NaN pixel gives NaN in exactly the outputs whose receptive field holds it (torch's rule).
+ *
+ * The stem: out (N,C0,h2,w2) = max_pool2d(relu?(conv2d(xn, weight, stride 2, pad 3) * scale + shift), 3, stride 2, pad 1) in one launch,
+ * h1 = (H-1)/2 + 1, h2 = (h1-1)/2 + 1 (likewise w); the half-resolution map is never written.  x (N,3,H,W): x_dtype 0 float32, 1 uint8.
+ * xn = x, or with mean / std (3 floats each, on the device, both or neither) xn = ((float)x - mean[c]) / std[c], one float32 subtraction
+ * and one correctly rounded float32 division, while the pixels are staged; the convolution's padding is zero AFTER that.  weight
+ * (7*7*3, C0) = the (C0,3,7,7) kernel permuted to (ci, ky, kx, co) -- output channel contiguous.  C0: a multiple of 16 from 16 to 64;
+ * H, W: 32 to 2048; N: 1 to 4096.  A work-group owns 6 x 16 pooled pixels. */
+PTX_API int ptx_conv_stem(const void *x, int x_dtype, int N, int H, int W, const float *weight, int C0, const float *scale,
+                          const float *shift, int relu, const float *mean, const float *std, float *out, void *stream);
+/* out (N,Cout,Ho,Wo)[n,co,y,x] = epilogue(sum_ci weight[co,ci] x[n,ci,s y,s x]), s = stride 1 or 2, Ho = (H-1)/s + 1; weight (Cout,Cin);
+ * residual (N,Cout,Ho,Wo).  Cin, Cout: multiples of 16 from 16 to 2048; H, W >= 1; N: 1 to 4096.  out may be residual, not x.  One
+ * launch. */
+PTX_API int ptx_conv1x1(const float *x, int N, int Cin, int H, int W, const float *weight, int Cout, int stride, const float *scale,
+                        const float *shift, const float *residual, int relu, float *out, void *stream);
+/* out (N,C,Ho,Wo) = epilogue(conv2d(x, w, stride s, pad 1)) as an implicit GEMM over k = (ky, kx, ci) (K = 9 C, no im2col buffer): weight
+ * (C,3,3,C) = the (co,ci,ky,kx) kernel permuted to (co, ky, kx, ci) -- input channel contiguous.  C: a multiple of 16 from 16 to 512;
+ * the rest as ptx_conv1x1.  One launch. */
+PTX_API int ptx_conv3x3(const float *x, int N, int C, int H, int W, const float *weight, int stride, const float *scale,
+                        const float *shift, const float *residual, int relu, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ Only what the path needs lives here:
 * ``grounding_loss.GroundingLoss``           -- the head's loss behind the decoder: 9-DoF box IoU, Hungarian match costs, focal and corner loss;
 * ``detector.GroundingDetector``             -- all of the above as one module: ``loss`` and ``predict`` of the whole grounder;
 * ``text_encoder.ClipTextEncoder``           -- the CLIP text encoder in front of it: token ids to ``last_hidden_state``;
+* ``image_backbone.ResNet``                  -- the 2D image backbone in front of it (mmdet.ResNet, frozen): images to the feature levels;
 * ``registry.MODELS``                        -- embodiedscan/mmengine registry or a stand-alone shim;
 * ``shard``                                  -- scene sharding across the GPUs of one node;
 * ``synth``                                  -- seeded synthetic scenes / closed-form weights.
@@ -29,6 +30,7 @@ from .decoder import GroundingDecoder
 from .grounding_loss import GroundingLoss
 from .detector import GroundingDetector
 from .text_encoder import ClipTextEncoder
+from .image_backbone import ResNet
 
-__all__ = ["MODELS", "REGISTRY_BACKEND", "ClipTextEncoder", "GroundingDecoder", "GroundingDetector", "GroundingLoss", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect"]
+__all__ = ["MODELS", "REGISTRY_BACKEND", "ClipTextEncoder", "GroundingDecoder", "GroundingDetector", "GroundingLoss", "MinkNeck", "MinkResNet", "ProxyTransformationNormReverse", "QuerySelect", "ResNet"]
 __version__ = "0.1.0"

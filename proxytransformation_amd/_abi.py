@@ -293,6 +293,9 @@ SIGNATURES.update({
     "ptx_txt_linear_workspace_bytes": (_Z, [_L, _I, _I]),
     "ptx_txt_linear": (_I, [_P, _L, _P, _P, _I, _I, _P, _P, _P, _Z, _P]),
     "ptx_txt_ln": (_I, [_P, _L, _I, _P, _P, _F, _P, _P]),
+    "ptx_conv_stem": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "ptx_conv1x1": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "ptx_conv3x3": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
 })
 
 _lib: Optional[C.CDLL] = None

@@ -10,10 +10,12 @@ backbone and the text encoder, as one module -- the stages of this package calle
     decoder (after the renaming of DET:605-617)     DET:582-621    decoder.GroundingDecoder
     bbox_head: scores, loss / predict               DET:700, 787   GroundingDecoder.head_scores, grounding_loss.GroundingLoss
 
-The 2D backbone stays outside, and by default the text encoder too: the detector takes their outputs (``img_features``: one
+By default the 2D backbone and the text encoder stay outside: the detector takes their outputs (``img_features``: one
 ``(B,V,C_l,H_l,W_l)`` per level; ``encoded_text (B,T,text_width)`` with ``text_token_mask``).  With ``text_encoder=`` (a
 ``text_encoder.ClipTextEncoder`` or its keywords) the detector holds the encoder and ``loss`` / ``predict`` / ``forward`` take
-``input_ids=`` and ``attention_mask=`` in place of the encoded text (DET:661-668, 740-753 behind the tokenizer).
+``input_ids=`` and ``attention_mask=`` in place of the encoded text (DET:661-668, 740-753 behind the tokenizer).  With ``backbone=`` (an
+``image_backbone.ResNet`` or its config dict) it holds the 2D backbone (DET:357-379) and the same methods take ``imgs=``
+``(B,V,3,H,W)`` in place of ``img_features``.
 ``share_pred_layer=True`` is the shipped head: ONE classification and ONE regression branch (``self.query_select``) serve the query
 selection, every decoder layer and the scores."""
 from __future__ import annotations
@@ -28,6 +30,7 @@ from .backbone import MinkResNet, SparseLevel
 from .decoder import GroundingDecoder, linear
 from .fusion import JoinTables, image_transform_scalars, join_level_features, join_level_features_per_scene, prepare_features_many, reverse_3d_flow
 from .grounding_loss import GroundingLoss
+from .image_backbone import ResNet
 from .module import ProxyTransformationNormReverse
 from .neck import MinkNeck
 from .query_select import QuerySelect
@@ -37,9 +40,10 @@ from .text_encoder import ClipTextEncoder
 __all__ = ["GroundingDetector"]
 
 #: the prefixes of a reference checkpoint that belong to modules outside this one: skipped by ``load_reference_state_dict``
-#: (``text_encoder.`` only while the detector holds no encoder)
+#: (each only while the detector does not hold that module)
 _OUTSIDE = ("backbone.", "text_encoder.")
 _TEXT = "text_encoder."
+_IMAGE = "backbone."
 
 
 def _build(who: str, name: str, cfg, cls, differentiable: bool):
@@ -62,13 +66,18 @@ def _build(who: str, name: str, cfg, cls, differentiable: bool):
 class GroundingDetector(nn.Module):
     """``GroundingDetector(preshape, backbone_3d, neck_3d, decoder, bbox_head, num_queries=256, voxel_size=0.01, use_xyz_feat=True,
     coord_type='DEPTH', train_cfg=None, test_cfg=None, text_width=768, *, differentiable=False, matcher='host', fused_join=True,
-    text_encoder=None)``:
+    text_encoder=None, backbone=None, pixel_mean=None, pixel_std=None, bgr_to_rgb=False)``:
     the reference's keywords (configs/grounding/*.py, ``model=``), each child a config dict or a ready module.  ``bbox_head`` is the
     ``GroundingHead`` config: it becomes ``self.bbox_head`` (``GroundingLoss``: loss and predict, no parameters) and ``self.query_select``
     (``QuerySelect``: the shared branches).  ``text_width``: the text encoder's hidden size, ``text_feat_map = nn.Linear(text_width,
     embed_dims)``.  ``text_encoder``: None (the default: the module, its ``state_dict`` and its methods are what they were), a
     ``ClipTextEncoder`` or its keyword dict; ``text_width`` then defaults to its ``hidden_size`` and must equal it.  The encoder is never
-    trained (``lr_mult=0.0`` in the reference): it runs under ``no_grad`` and its parameters receive no gradient.
+    trained (``lr_mult=0.0`` in the reference): it runs under ``no_grad`` and its parameters receive no gradient.  ``backbone``: None
+    (the default: the module, its ``state_dict`` and its methods are what they were), an ``image_backbone.ResNet`` or its config dict
+    (``type='mmdet.ResNet'``); ``pixel_mean`` / ``pixel_std`` / ``bgr_to_rgb``: the data preprocessor's values, applied by the backbone's
+    stem.  The backbone is inference-only: with ``differentiable=True`` in training the loss's backward stops at its output and its
+    parameters get no gradient -- this DIFFERS from the reference, which trains the convolutions of stages 2 to 4
+    (``frozen_stages=1``); training the 2D backbone is out of scope.
 
     Inputs of every method: ``points`` list of B ``(N_b,3)``; ``encoded_text (B,T,text_width)``, ``text_token_mask (B,T)`` bool (True =
     token); ``img_features`` one ``(B,V,C_l,H_l,W_l)`` per backbone level; ``scenes`` one dict per sample with ``depth2img =
@@ -84,9 +93,19 @@ class GroundingDetector(nn.Module):
     def __init__(self, preshape, backbone_3d, neck_3d, decoder, bbox_head, num_queries: int = 256, voxel_size: float = 0.01,
                  use_xyz_feat: bool = True, coord_type: str = "DEPTH", train_cfg: Optional[dict] = None, test_cfg: Optional[dict] = None,
                  text_width: Optional[int] = None, *, differentiable: bool = False, matcher: str = "host", fused_join: bool = True,
-                 text_encoder=None):
+                 text_encoder=None, backbone=None, pixel_mean=None, pixel_std=None, bgr_to_rgb: bool = False):
         super().__init__()
         who = "GroundingDetector"
+        if backbone is not None:
+            if isinstance(backbone, dict) and backbone.get("type") in ("mmdet.ResNet", "ResNet"):
+                backbone = dict(backbone, type="ResNet")    # this package's class, also where mmdet's own holds the name in the registry
+            backbone = _build(who, "backbone", backbone, ResNet, False)
+            if not isinstance(backbone, ResNet):
+                raise TypeError(f"{who}: backbone must be an image_backbone.ResNet or its config dict, got {type(backbone).__name__}")
+        elif pixel_mean is not None or pixel_std is not None or bgr_to_rgb:
+            raise ValueError(f"{who}: pixel_mean / pixel_std / bgr_to_rgb go with backbone=")
+        if (pixel_mean is None) != (pixel_std is None):
+            raise ValueError(f"{who}: pixel_mean and pixel_std go together")
         if text_encoder is not None:
             text_encoder = _build(who, "text_encoder", text_encoder, ClipTextEncoder, False)
             if not isinstance(text_encoder, ClipTextEncoder):
@@ -145,6 +164,12 @@ class GroundingDetector(nn.Module):
         self.text_feat_map = nn.Linear(int(text_width), self.embed_dims)
         self.text_width = int(text_width)
         self.text_encoder = text_encoder     # None: no child, no entry in the state dict
+        self.backbone = backbone             # likewise
+        if backbone is not None and len(backbone.out_indices) != int(self.backbone_3d.num_stages):
+            raise ValueError(f"{who}: the backbone returns {len(backbone.out_indices)} levels, backbone_3d has {self.backbone_3d.num_stages}")
+        self.pixel_mean = None if pixel_mean is None else tuple(float(v) for v in pixel_mean)
+        self.pixel_std = None if pixel_std is None else tuple(float(v) for v in pixel_std)
+        self.bgr_to_rgb = bool(bgr_to_rgb)
         self._staging: dict = {}            # per stream: the pinned staging buffer of the join tables
 
     def __deepcopy__(self, memo):
@@ -244,6 +269,27 @@ class GroundingDetector(nn.Module):
             raise ValueError("GroundingDetector: input_ids / attention_mask take the place of encoded_text / text_token_mask; pass one pair")
         return self.encode_text(input_ids, attention_mask)
 
+    def extract_image_features(self, imgs: torch.Tensor) -> List[torch.Tensor]:
+        """DET:357-379: the backbone's levels ``(B,V,C_l,H_l,W_l)`` of ``imgs (B,V,3,H,W)`` (float32 or uint8), detached; the data
+        preprocessor's ``pixel_mean`` / ``pixel_std`` / ``bgr_to_rgb`` are applied by the stem."""
+        if self.backbone is None:
+            raise ValueError("GroundingDetector: imgs need a backbone; construct the detector with backbone=")
+        if not isinstance(imgs, torch.Tensor) or imgs.dim() != 5:
+            raise ValueError(f"GroundingDetector: imgs (B,V,3,H,W) expected, got {tuple(getattr(imgs, 'shape', ()))}")
+        return list(self.backbone(imgs, mean=self.pixel_mean, std=self.pixel_std, bgr_to_rgb=self.bgr_to_rgb))
+
+    def _images(self, img_features, imgs, img_pad_shape):
+        """The image operands of a call: the feature levels as given, or the backbone's for ``imgs``; and ``img_pad_shape``, which
+        defaults to the images' ``(H, W)`` (without images: to (480, 480), as it always did)."""
+        if imgs is None:
+            if img_features is None:
+                raise ValueError("GroundingDetector: img_features, or imgs (with a backbone), are required")
+            return img_features, ((480, 480) if img_pad_shape is None else img_pad_shape)
+        if img_features is not None:
+            raise ValueError("GroundingDetector: imgs take the place of img_features; pass one of them")
+        feats = self.extract_image_features(imgs)
+        return feats, (tuple(int(v) for v in imgs.shape[-2:]) if img_pad_shape is None else img_pad_shape)
+
     def map_text(self, encoded_text: torch.Tensor, _mode: Optional[bool] = None) -> torch.Tensor:
         """``text_feat_map(encoded_text)`` (DET:659) through ``decoder.linear``."""
         rec = self._records(encoded_text) if _mode is None else _mode
@@ -272,11 +318,13 @@ class GroundingDetector(nn.Module):
                                                                      differentiable=self.differentiable and mode)
             return head
 
-    def forward(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=(480, 480), bbox=None,
-                trace: Optional[dict] = None, *, input_ids=None, attention_mask=None) -> dict:
+    def forward(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=None, bbox=None,
+                trace: Optional[dict] = None, *, input_ids=None, attention_mask=None, imgs=None) -> dict:
         """The whole chain up to the head's outputs (``forward_transformer``'s dict).  ``input_ids=`` / ``attention_mask=`` (with a text
-        encoder) take the place of ``encoded_text`` / ``text_token_mask``."""
+        encoder) take the place of ``encoded_text`` / ``text_token_mask``; ``imgs=`` (with a backbone) takes the place of
+        ``img_features``.  ``img_pad_shape``: None is the images' ``(H, W)``, without images (480, 480)."""
         encoded_text, text_token_mask = self._text(encoded_text, text_token_mask, input_ids, attention_mask)
+        img_features, img_pad_shape = self._images(img_features, imgs, img_pad_shape)
         mode = self._records(encoded_text, *img_features)      # one decision for the whole chain, from the caller's inputs
         text_dict = dict(text_feats=self.map_text(encoded_text, mode), text_token_mask=text_token_mask)
         keep: list = []
@@ -289,19 +337,19 @@ class GroundingDetector(nn.Module):
         return head
 
     def loss(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, gt_bboxes=None, positive_maps=None,
-             img_pad_shape=(480, 480), bbox=None, trace: Optional[dict] = None, *, input_ids=None,
-             attention_mask=None) -> Dict[str, torch.Tensor]:
+             img_pad_shape=None, bbox=None, trace: Optional[dict] = None, *, input_ids=None, attention_mask=None,
+             imgs=None) -> Dict[str, torch.Tensor]:
         """DET:623-705: the reference's loss dict (``loss_cls``, ``loss_bbox``, ``d{i}.loss_cls``, ``d{i}.loss_bbox``)."""
         encoded_text, text_token_mask = self._text(encoded_text, text_token_mask, input_ids, attention_mask)
-        head = self.forward(points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape, bbox, trace)
+        head = self.forward(points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape, bbox, trace, imgs=imgs)
         return self.bbox_head.loss(head["all_layers_cls_scores"], head["all_layers_pred_bboxes"], text_token_mask, gt_bboxes, positive_maps)
 
-    def predict(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=(480, 480), bbox=None,
-                trace: Optional[dict] = None, *, input_ids=None, attention_mask=None) -> List[dict]:
+    def predict(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=None, bbox=None,
+                trace: Optional[dict] = None, *, input_ids=None, attention_mask=None, imgs=None) -> List[dict]:
         """DET:707-794 with ``GroundingHead.predict`` (grounding_head.py:566-604): per scene ``dict(bboxes_3d (K,9), scores_3d (K,),
         target_scores_3d (K,))``; the reference regards the scores as the target scores at inference."""
         head = self.forward(points, encoded_text, text_token_mask, img_features, scenes, img_pad_shape, bbox, trace, input_ids=input_ids,
-                            attention_mask=attention_mask)
+                            attention_mask=attention_mask, imgs=imgs)
         boxes, scores = self.bbox_head.predict(head["all_layers_cls_scores"], head["all_layers_pred_bboxes"])
         return [dict(bboxes_3d=boxes[b], scores_3d=scores[b], target_scores_3d=scores[b]) for b in range(boxes.shape[0])]
 
@@ -318,12 +366,13 @@ class GroundingDetector(nn.Module):
         return batch.points, batch.bbox
 
     # ------------------------------------------------------------------------------------------------------------- the host chain
-    def forward_host(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=(480, 480),
+    def forward_host(self, points, encoded_text=None, text_token_mask=None, img_features=None, scenes=None, img_pad_shape=None,
                      dtype=None, decisions: Optional[dict] = None, gt_bboxes=None, positive_maps=None, host=None, *, input_ids=None,
-                     attention_mask=None) -> dict:
+                     attention_mask=None, imgs=None) -> dict:
         """The same chain (eval mode) from the stages' own host restatements in numpy ``dtype`` (float64, the default, or float32):
         ``host.forward`` (the preshape) -> ``host.voxelize`` -> ``MinkResNet.forward_host`` -> ``host.point_sample`` per scene and
-        level plus the two concatenations -> ``MinkNeck.forward_host`` -> (with ``input_ids=``: ``ClipTextEncoder.forward_host`` ->)
+        level plus the two concatenations -> ``MinkNeck.forward_host`` -> (with ``imgs=``: ``ResNet.forward_host`` in front of it all; with ``input_ids=``:
+        ``ClipTextEncoder.forward_host`` ->)
         ``text_feat_map`` -> ``QuerySelect.forward_host`` -> the
         renaming of DET:605-617 -> ``GroundingDecoder.forward_host`` -> ``contrastive_scores_host`` -> ``predict_host`` (and ``loss_host``
         when ``gt_bboxes`` / ``positive_maps`` are given).  It calls no device code.  ``decisions``: the device's discrete decisions,
@@ -341,6 +390,18 @@ class GroundingDetector(nn.Module):
         from . import decoder_host, grounding_loss_host as glh
         from .pipeline import projection_matrices
         dt = np.dtype(np.float64 if dtype is None else dtype)
+        if imgs is not None:
+            if img_features is not None:
+                raise ValueError("GroundingDetector.forward_host: imgs take the place of img_features; pass one of them")
+            if self.backbone is None:
+                raise ValueError("GroundingDetector.forward_host: imgs need a backbone; construct the detector with backbone=")
+            img_features = self.backbone.forward_host(imgs, dtype=dt, mean=self.pixel_mean, std=self.pixel_std, bgr_to_rgb=self.bgr_to_rgb)
+            if img_pad_shape is None:
+                img_pad_shape = tuple(int(v) for v in imgs.shape[-2:])
+        elif img_features is None:
+            raise ValueError("GroundingDetector.forward_host: img_features, or imgs (with a backbone), are required")
+        if img_pad_shape is None:
+            img_pad_shape = (480, 480)
         if input_ids is not None:
             if encoded_text is not None or text_token_mask is not None:
                 raise ValueError("GroundingDetector.forward_host: input_ids / attention_mask take the place of encoded_text / text_token_mask")
@@ -436,20 +497,21 @@ class GroundingDetector(nn.Module):
 
     def reference_state_dict(self) -> Dict[str, torch.Tensor]:
         """The state dict under the reference's names: ``preshape.*``, ``backbone_3d.*``, ``neck_3d.*``, ``decoder.*``,
-        ``text_feat_map.*``, with a text encoder ``text_encoder.text_model.*``, and the ``NL + 1`` aliases
+        ``text_feat_map.*``, with a text encoder ``text_encoder.text_model.*``, with a backbone ``backbone.*``, and the ``NL + 1`` aliases
         ``bbox_head.cls_branches.{i}.*`` / ``bbox_head.reg_branches.{i}.*``."""
         sd = self.state_dict()
         return {ref: sd[own] for ref, own in self._reference_names()}
 
     def load_reference_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True) -> dict:
-        """Loads a reference checkpoint's ``state_dict``.  ``backbone.*`` and -- while the detector holds no text encoder --
-        ``text_encoder.*`` belong to modules outside this one: skipped and listed.  With a text encoder its tensors are loaded, under
+        """Loads a reference checkpoint's ``state_dict``.  While the detector holds no backbone / no text encoder, ``backbone.*`` /
+        ``text_encoder.*`` belong to modules outside this one: skipped and listed.  With a backbone its tensors are loaded under
+        ``backbone.*`` (mmdet's names).  With a text encoder its tensors are loaded, under
         ``text_encoder.text_model.*`` or ``text_encoder.*`` (``ClipTextEncoder.normalise_names``), a ``position_ids`` buffer ignored.
         The aliases of a shared branch must be equal (``ValueError`` naming the key).  ``strict``: a missing or unexpected key raises
         ``KeyError``.  Returns ``dict(skipped, missing, unexpected)``."""
-        outside = _OUTSIDE
+        outside = _OUTSIDE if self.backbone is None else tuple(p for p in _OUTSIDE if p != _IMAGE)
         if self.text_encoder is not None:
-            outside = tuple(p for p in _OUTSIDE if p != _TEXT)
+            outside = tuple(p for p in outside if p != _TEXT)
             text = ClipTextEncoder.normalise_names({k[len(_TEXT):]: v for k, v in state_dict.items() if k.startswith(_TEXT)})
             state_dict = {k: v for k, v in state_dict.items() if not k.startswith(_TEXT)}
             state_dict.update({_TEXT + k: v for k, v in text.items()})

@@ -37,8 +37,9 @@ from torch.autograd.function import once_differentiable
 
 from . import _abi, decoder_host, query_select
 from . import train as _train_ops
+from ._doors import (MAX_QUERIES, MAX_SCENES, MAX_TEXT, PreparedOperands, _f32, _f32_grad, _gpu, _mask_bytes, _np, _ptr, _stream, _wants_grad,
+                     _width)
 from .query_select import QuerySelect
-from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _mask_bytes, _np, _ptr, _stream, _wants_grad, _width
 
 __all__ = ["GroundingDecoder", "attention", "boxes", "contrastive_scores", "layer_norm", "linear", "linear_add_ln", "posembed", "posembed_folded"]
 
@@ -777,7 +778,7 @@ class _Layer(nn.Module):
         self.self_posembed = _PositionEmbeddingLearned(3, self.embed_dims)          # constructed by the reference, never called
 
 
-class GroundingDecoder(nn.Module):
+class GroundingDecoder(PreparedOperands, nn.Module):
     """``SparseFeatureFusionTransformerDecoder(num_layers, layer_cfg, post_norm_cfg=None, return_intermediate=True, init_cfg=None,
     with_cp=None)``, eval forward.  ``layer_cfg`` holds ``self_attn_cfg``, ``cross_attn_text_cfg``, ``cross_attn_cfg`` (``embed_dims``,
     ``num_heads``; dropout rates are accepted: dropout is the identity in eval) and ``ffn_cfg`` (``embed_dims``, ``feedforward_channels``,
@@ -805,8 +806,7 @@ class GroundingDecoder(nn.Module):
     and not to the eval bits.  In ``.eval()`` it is the eval forward, and raises when an input requires grad (frozen BatchNorms).
 
     The operands the launches take (concatenated projections, folded position embeddings) are prepared once and rebuilt when a parameter
-    or buffer is replaced or its ``_version`` changes (``load_state_dict``, in-place updates).  A write through ``.data`` bumps no
-    version and is not seen: move the module (``.to``) or write in place under ``no_grad`` instead."""
+    or buffer is replaced or its ``_version`` changes (``load_state_dict``, in-place updates): ``_doors.PreparedOperands``."""
 
     def __init__(self, num_layers: int, layer_cfg: dict, post_norm_cfg=None, return_intermediate: bool = True, init_cfg=None, with_cp=None,
                  differentiable: bool = False):
@@ -824,49 +824,30 @@ class GroundingDecoder(nn.Module):
         self.self_posembed = _PositionEmbeddingLearned(9, self.embed_dims)
         self.cross_posembed = _PositionEmbeddingLearned(3, self.embed_dims)
         self.norm = nn.LayerNorm(self.embed_dims)
-        self._prepared = None
 
-    # -- the operands the launches take, rebuilt when a parameter changes
-    def _apply(self, fn, *args, **kwargs):
-        self._prepared = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def _state_key(self, dev):
-        """The device and every tensor's identity and ``_version``: a parameter REPLACED by another one of the same version is a change
-        too.  ``_prepare`` keeps the tensors it was built from alive, so that no new tensor can take the ``id`` of a freed one."""
-        return (str(dev),) + tuple((id(t), t.data_ptr(), t._version) for t in self._tensors())
-
-    def _tensors(self):
-        return list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
-
-    def _prepare(self, dev) -> dict:
-        key = self._state_key(dev)
-        if self._prepared is not None and self._prepared["key"] == key:
-            return self._prepared
+    # -- the operands the launches take (PreparedOperands._prepare caches them)
+    def _build_operands(self, dev) -> dict:
         C, NL = self.embed_dims, self.num_layers
         group = max(1, MAX_COUT // (2 * C))                  # layers per hoisted key/value projection
         f = lambda t: t.detach().to(dev, torch.float32)       # noqa: E731
-        prep = dict(key=key, tensors=self._tensors(), self_pos=_fold(self.self_posembed, dev), cross_pos=_fold(self.cross_posembed, dev),
-                    groups=[], layers=[])
-        with torch.no_grad():
-            for lo in range(0, NL, group):
-                ids = list(range(lo, min(lo + group, NL)))
-                entry = dict(ids=ids)
-                for name in ("cross_attn", "cross_attn_text"):
-                    ws = [f(getattr(self.layers[i], name).attn.in_proj_weight) for i in ids]
-                    bs = [f(getattr(self.layers[i], name).attn.in_proj_bias) for i in ids]
-                    entry[name] = (torch.cat([w[C:2 * C] for w in ws] + [w[2 * C:] for w in ws]).contiguous(),
-                                   torch.cat([b[C:2 * C] for b in bs] + [b[2 * C:] for b in bs]).contiguous())
-                prep["groups"].append(entry)
-            for layer in self.layers:
-                d = {}
-                for name in ("self_attn", "cross_attn_text", "cross_attn"):
-                    a = getattr(layer, name).attn
-                    w, b = f(a.in_proj_weight).contiguous(), f(a.in_proj_bias).contiguous()
-                    d[name] = dict(w=w, b=b, wq=w[:C], bq=b[:C], wkv=w[C:], bkv=b[C:], wo=f(a.out_proj.weight).contiguous(),
-                                   bo=f(a.out_proj.bias).contiguous(), H=getattr(layer, name).num_heads)
-                prep["layers"].append(d)
-        self._prepared = prep
+        prep = dict(self_pos=_fold(self.self_posembed, dev), cross_pos=_fold(self.cross_posembed, dev), groups=[], layers=[])
+        for lo in range(0, NL, group):
+            ids = list(range(lo, min(lo + group, NL)))
+            entry = dict(ids=ids)
+            for name in ("cross_attn", "cross_attn_text"):
+                ws = [f(getattr(self.layers[i], name).attn.in_proj_weight) for i in ids]
+                bs = [f(getattr(self.layers[i], name).attn.in_proj_bias) for i in ids]
+                entry[name] = (torch.cat([w[C:2 * C] for w in ws] + [w[2 * C:] for w in ws]).contiguous(),
+                               torch.cat([b[C:2 * C] for b in bs] + [b[2 * C:] for b in bs]).contiguous())
+            prep["groups"].append(entry)
+        for layer in self.layers:
+            d = {}
+            for name in ("self_attn", "cross_attn_text", "cross_attn"):
+                a = getattr(layer, name).attn
+                w, b = f(a.in_proj_weight).contiguous(), f(a.in_proj_bias).contiguous()
+                d[name] = dict(w=w, b=b, wq=w[:C], bq=b[:C], wkv=w[C:], bkv=b[C:], wo=f(a.out_proj.weight).contiguous(),
+                               bo=f(a.out_proj.bias).contiguous(), H=getattr(layer, name).num_heads)
+            prep["layers"].append(d)
         return prep
 
     @staticmethod

@@ -26,6 +26,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 from torch import nn
 
+from ._doors import _np
 from .backbone import MinkResNet, SparseLevel
 from .decoder import GroundingDecoder, linear
 from .fusion import JoinTables, image_transform_scalars, join_level_features, join_level_features_per_scene, prepare_features_many, reverse_3d_flow
@@ -407,12 +408,11 @@ class GroundingDetector(nn.Module):
                 raise ValueError("GroundingDetector.forward_host: input_ids / attention_mask take the place of encoded_text / text_token_mask")
             if self.text_encoder is None:
                 raise ValueError("GroundingDetector.forward_host: input_ids need a text encoder; construct the detector with text_encoder=")
-            ids = input_ids.detach().cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)
+            ids = _np(input_ids)
             encoded_text = self.text_encoder.forward_host(ids, attention_mask, dtype=dt)
-            text_token_mask = np.ones(ids.shape, bool) if attention_mask is None else \
-                (attention_mask.detach().cpu().numpy() if isinstance(attention_mask, torch.Tensor) else np.asarray(attention_mask)) != 0
+            text_token_mask = np.ones(ids.shape, bool) if attention_mask is None else _np(attention_mask) != 0
         decisions = dict(decisions or {})
-        arr = lambda t, d=None: (t.detach().cpu().float().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(d or dt)   # noqa: E731
+        arr = lambda t, d=None: _np(t.float() if isinstance(t, torch.Tensor) else t, d or dt)      # noqa: E731  (.float(): numpy has no bf16)
         B = len(points)
         mask = arr(text_token_mask, bool)
         w, b = arr(self.text_feat_map.weight), arr(self.text_feat_map.bias)

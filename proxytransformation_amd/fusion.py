@@ -8,6 +8,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi
+from ._doors import _stream
 
 _DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
@@ -132,7 +133,7 @@ def _sample(feats, prepared, pts, proj, pre, scal, valid_num):
     _abi.check(lib.ptx_point_sample(pts.data_ptr(), N, feats_ptr, _DT[feats.dtype], V, C, H, W, proj.data_ptr(),
                                     None if pre is None else pre.data_ptr(), *scal, out.data_ptr(),
                                     None if valid_num is None else valid_num.data_ptr(), ws.data_ptr(), ws.numel(),
-                                    torch.cuda.current_stream(dev).cuda_stream),
+                                    _stream(dev)),
                "ptx_point_sample")
     return out
 
@@ -169,7 +170,7 @@ class _PointSampleFn(torch.autograd.Function):
         _abi.check(lib.ptx_point_sample_bwd(pts.data_ptr(), N, dout.data_ptr(), valid_num.data_ptr(), V, C, H, W, proj.data_ptr(),
                                             None if pre is None else pre.data_ptr(), *ctx.scal, dfeats.data_ptr(),
                                             _DT[ctx.feat_dtype], ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream(dev).cuda_stream), "ptx_point_sample_bwd")
+                                            _stream(dev)), "ptx_point_sample_bwd")
         return dfeats, None, None, None, None, None
 
 
@@ -189,7 +190,7 @@ def prepare_features(img_features: torch.Tensor) -> torch.Tensor:
         raise RuntimeError(f"unsupported feature shape {tuple(feats.shape)} (C <= 512)")
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=feats.device)
     _abi.check(lib.ptx_point_sample_prepare(feats.data_ptr(), _DT[feats.dtype], V, C, H, W, ws.data_ptr(), ws.numel(),
-                                            torch.cuda.current_stream(feats.device).cuda_stream), "ptx_point_sample_prepare")
+                                            _stream(feats.device)), "ptx_point_sample_prepare")
     return ws
 
 
@@ -211,7 +212,7 @@ def prepare_features_many(maps) -> list:
     dev = maps[0].device
     flat = torch.empty((sum(sizes),), dtype=torch.uint8, device=dev)
     views = list(flat.split_with_sizes(sizes))
-    st = torch.cuda.current_stream(dev).cuda_stream
+    st = _stream(dev)
     for m, ws in zip(maps, views):
         V, C, H, W = m.shape
         _abi.check(lib.ptx_point_sample_prepare(m.data_ptr(), _DT[m.dtype], V, C, H, W, ws.data_ptr(), ws.numel(), st),
@@ -373,7 +374,7 @@ def _join(feats, img, coords, tables, prepared, valid_num):
     _abi.check(_abi.lib().ptx_level_join(coords.data_ptr(), n, feats.data_ptr(), Cb, ptrs, tables.host.ctypes.data, tables.dev.data_ptr(),
                                          B, V, Ci, H, W, tables.voxel_size, 1 if tables.aligned else 0, out.data_ptr(),
                                          None if valid_num is None else valid_num.data_ptr(),
-                                         torch.cuda.current_stream(feats.device).cuda_stream), "ptx_level_join")
+                                         _stream(feats.device)), "ptx_level_join")
     return out
 
 
@@ -419,5 +420,5 @@ class _LevelJoinFn(torch.autograd.Function):
                                           tables.host.ctypes.data, tables.dev.data_ptr(), B, V, Ci, H, W, tables.voxel_size, bil,
                                           None if dfeats is None else dfeats.data_ptr(), None if dimg is None else dimg.data_ptr(),
                                           _DT[ctx.img_dtype], None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
-                                          torch.cuda.current_stream(dev).cuda_stream), "ptx_level_join_bwd")
+                                          _stream(dev)), "ptx_level_join_bwd")
         return dfeats, dimg, None, None, None, None

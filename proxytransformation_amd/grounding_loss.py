@@ -39,7 +39,7 @@ from torch import nn
 
 from . import _abi
 from .grounding_loss_host import SAP_MAX_COLS, SAP_MAX_ROWS
-from .sparse import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _mask_bytes, _stream
+from ._doors import MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _mask_bytes, _stream
 
 __all__ = ["GroundingLoss", "box_iou3d", "grounding_loss", "hungarian_assign", "match_costs", "predict_scores"]
 

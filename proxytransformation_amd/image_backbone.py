@@ -29,9 +29,10 @@ import torch
 from torch import nn
 
 from . import _abi, image_backbone_host
+from ._doors import PreparedOperands, _np, _ptr, _stream
 from .image_backbone_host import ARCH, EPS, EXPANSION
 from .registry import MODELS, REGISTRY_BACKEND
-from .sparse import _ptr, _stream, bn_fold
+from .sparse import bn_fold
 
 __all__ = ["ResNet"]
 
@@ -60,7 +61,7 @@ def _refuse(name: str, value, why: str):
     raise NotImplementedError(f"{WHO}: {name}={value!r} is not implemented ({why})")
 
 
-class ResNet(nn.Module):
+class ResNet(PreparedOperands, nn.Module):
     """``ResNet(depth, in_channels=3, stem_channels=None, base_channels=64, num_stages=4, strides=(1,2,2,2), dilations=(1,1,1,1),
     out_indices=(0,1,2,3), style='pytorch', ...)``: mmdet's keywords; registered as ``mmdet.ResNet`` and ``ResNet``.  The ``state_dict``
     is torchvision's / mmdet's: ``conv1.weight``, ``bn1.*``, ``layer{s}.{b}.conv{1,2,3}.weight``, ``layer{s}.{b}.bn{1,2,3}.*``,
@@ -72,8 +73,8 @@ class ResNet(nn.Module):
     ``init_cfg``, ``with_cp``, ``zero_init_residual``.  ``NotImplementedError`` naming the keyword: ``style='caffe'``, ``deep_stem``,
     ``avg_down``, ``dcn``, ``plugins``, ``conv_cfg``, other ``strides`` / ``dilations``, depths 18 / 34.
 
-    The folded operands the launches take are prepared once per device and rebuilt when a parameter or buffer is replaced or its
-    ``_version`` changes (``load_state_dict``, ``.to()``), as ``ClipTextEncoder`` does it."""
+    The folded operands the launches take are prepared once per device and rebuilt when a parameter or floating-point buffer is replaced
+    or its ``_version`` changes (``load_state_dict``, ``.to()``): ``_doors.PreparedOperands``."""
 
     def __init__(self, depth: int, in_channels: int = 3, stem_channels: Optional[int] = None, base_channels: int = 64, num_stages: int = 4,
                  strides: Sequence[int] = (1, 2, 2, 2), dilations: Sequence[int] = (1, 1, 1, 1), out_indices: Sequence[int] = (0, 1, 2, 3),
@@ -139,7 +140,6 @@ class ResNet(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
         for p in self.parameters():
             p.requires_grad_(False)                          # always inference: every BatchNorm frozen, no convolution trained
-        self._prepared = None
 
     @property
     def out_channels(self) -> List[int]:
@@ -153,45 +153,25 @@ class ResNet(nn.Module):
                 m.training = False
         return self
 
-    # -- the operands the launches take, rebuilt when a parameter or buffer changes
-    def _apply(self, fn, *args, **kwargs):
-        self._prepared = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        self._prepared = None
-        return super().load_state_dict(state_dict, strict=strict, **kw)
-
-    def _state_key(self, dev):
-        """What the prepared operands were made from: identity, storage and ``_version`` of every parameter and buffer, so that a tensor
-        assigned or updated in place behind ``load_state_dict`` / ``_apply`` is seen too.  A walk over 318 tensors at the shipped depth:
-        about 0.1 ms of host time per forward, beside 53 launches."""
-        return (str(dev),) + tuple((id(t), t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
-
-    def _prepare(self, dev) -> dict:
-        key = self._state_key(dev)
-        if self._prepared is not None and self._prepared["key"] == key:
-            return self._prepared
+    # -- the operands the launches take (PreparedOperands._prepare caches them)
+    def _build_operands(self, dev) -> dict:
         f = lambda t: t.detach().to(dev, torch.float32).contiguous()      # noqa: E731
-        with torch.no_grad():
-            fold = lambda bn: tuple(f(t) for t in bn_fold(bn))            # noqa: E731
-            w = f(self.conv1.weight)                                      # (C0,3,7,7) -> (ci,ky,kx,co): output channel contiguous
-            prep = dict(key=key, tensors=list(self.parameters()) + list(self.buffers()),
-                        stem=w.permute(1, 2, 3, 0).contiguous(), stem_bgr=w.flip(1).permute(1, 2, 3, 0).contiguous(),
-                        bn1=fold(self.bn1), stages=[], norm={})
-            for s in range(self.num_stages):
-                blocks = []
-                for blk in getattr(self, f"layer{s + 1}"):
-                    planes, out = blk.conv1.out_channels, blk.conv3.out_channels
-                    d = dict(stride=blk.stride, planes=planes, out=out, inplanes=blk.conv1.in_channels,
-                             w1=f(blk.conv1.weight).reshape(planes, -1), bn1=fold(blk.bn1),
-                             w2=f(blk.conv2.weight).permute(0, 2, 3, 1).contiguous(), bn2=fold(blk.bn2),     # (co,ky,kx,ci)
-                             w3=f(blk.conv3.weight).reshape(out, planes), bn3=fold(blk.bn3), wd=None, bnd=None)
-                    if blk.downsample is not None:
-                        d["wd"], d["bnd"] = f(blk.downsample[0].weight).reshape(out, -1), fold(blk.downsample[1])
-                    blocks.append(d)
-                prep["stages"].append(blocks)
-        self._prepared = prep
+        fold = lambda bn: tuple(f(t) for t in bn_fold(bn))            # noqa: E731
+        w = f(self.conv1.weight)                                      # (C0,3,7,7) -> (ci,ky,kx,co): output channel contiguous
+        prep = dict(stem=w.permute(1, 2, 3, 0).contiguous(), stem_bgr=w.flip(1).permute(1, 2, 3, 0).contiguous(), bn1=fold(self.bn1),
+                    stages=[], norm={})
+        for s in range(self.num_stages):
+            blocks = []
+            for blk in getattr(self, f"layer{s + 1}"):
+                planes, out = blk.conv1.out_channels, blk.conv3.out_channels
+                d = dict(stride=blk.stride, planes=planes, out=out, inplanes=blk.conv1.in_channels,
+                         w1=f(blk.conv1.weight).reshape(planes, -1), bn1=fold(blk.bn1),
+                         w2=f(blk.conv2.weight).permute(0, 2, 3, 1).contiguous(), bn2=fold(blk.bn2),     # (co,ky,kx,ci)
+                         w3=f(blk.conv3.weight).reshape(out, planes), bn3=fold(blk.bn3), wd=None, bnd=None)
+                if blk.downsample is not None:
+                    d["wd"], d["bnd"] = f(blk.downsample[0].weight).reshape(out, -1), fold(blk.downsample[1])
+                blocks.append(d)
+            prep["stages"].append(blocks)
         return prep
 
     def _norm(self, prep, dev, mean, std, bgr_to_rgb):
@@ -291,12 +271,11 @@ class ResNet(nn.Module):
 
     def forward_host(self, imgs, dtype=np.float64, mean=None, std=None, bgr_to_rgb: bool = False) -> List[np.ndarray]:
         """The same chain in numpy ``dtype`` (``image_backbone_host.resnet_host``): the specification.  It calls no device code."""
-        arr = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)      # noqa: E731
-        x = arr(imgs)
+        x = _np(imgs)
         if x.ndim not in (4, 5) or x.shape[-3] != 3:
             raise ValueError(f"{WHO}.forward_host: imgs must be (N,3,H,W) or (B,V,3,H,W), got {x.shape}")
         lead = x.shape[:-3]
-        params = {k: arr(v) for k, v in self.state_dict().items()}
+        params = {k: _np(v) for k, v in self.state_dict().items()}
         outs = image_backbone_host.resnet_host(params, x.reshape((-1,) + x.shape[-3:]), self.stage_blocks[:self.out_indices[-1] + 1],
                                                self.strides, self.out_indices, dtype, mean, std, bgr_to_rgb)
         return [o.reshape(lead + o.shape[1:]) for o in outs]

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _abi
+from ._doors import _ptr, _stream
 from .registry import MODELS
 
 __all__ = ["ProxyTransformationNormReverse"]
@@ -197,10 +198,6 @@ def _exit_check():
 
 
 atexit.register(_exit_check)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _invalidate_after_load(mod, _incompatible_keys):
@@ -979,7 +976,7 @@ class _VoxelFeatures(torch.autograd.Function):
         B, Ncap = inverse.shape
         dfeats = dfeats.to(torch.float32).contiguous()
         dpoints = torch.empty((B, Ncap, 3), dtype=torch.float32, device=inverse.device)
-        stream = torch.cuda.current_stream(inverse.device).cuda_stream
+        stream = _stream(inverse.device)
         _abi.check(_abi.lib().ptx_voxel_features_bwd(_ptr(dfeats) if dfeats.numel() else None, dfeats.shape[0], inverse.data_ptr(),
                                                      rep.data_ptr(), counts.data_ptr(), B, Ncap, dpoints.data_ptr(), stream),
                    "ptx_voxel_features_bwd")

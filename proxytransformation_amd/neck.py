@@ -39,10 +39,11 @@ import torch
 from torch import nn
 
 from . import _abi, neck_host, sparse
+from ._doors import _channel_vectors, _f32, _f32_grad, _int32_array, _np, _ptr, _stream, _train, _wants_grad, _workspace
 from .backbone import SparseLevel
 from .neck_host import ACT_ELU, ACT_NONE
 from .registry import MODELS, REGISTRY_BACKEND
-from .sparse import SparseBatchNorm, SparseConv3d, _channel_vectors, _f32, _f32_grad, _int32_array, _np, _ptr, _stream, _train, _workspace
+from .sparse import SparseBatchNorm, SparseConv3d
 
 __all__ = ["GenerativeConvTranspose", "MinkNeck", "conv_transpose_gen", "neck_head", "prune_scores", "rows_gather", "topk_prune", "union_add"]
 
@@ -261,7 +262,7 @@ def topk_prune(scores: torch.Tensor, coords: torch.Tensor, scene_rows: Sequence[
     lower row index; the new scene ends need no wait.  Inference-only unless ``differentiable=True``: then, with grad mode on and
     ``feats`` requiring grad, the gradient flows to the kept rows (``dfeats[i] = g[dest[i]]``, dropped rows ``+0.0``, pure copies); the
     scores never get one (the reference selects under ``torch.no_grad()``) and must not require grad."""
-    if differentiable and sparse._wants_grad(scores):
+    if differentiable and _wants_grad(scores):
         raise ValueError("topk_prune(differentiable=True): the scores select rows and get no gradient, but they require grad; detach them")
     train = _train("topk_prune", differentiable, scores, feats)
     feats_in = feats
@@ -444,7 +445,7 @@ class MinkNeck(nn.Module):
         if any(modes):
             raise NotImplementedError("MinkNeck(differentiable=True): some BatchNorms are in training mode and some are not; the training chain "
                                       "needs all of them in training mode (bn.train()), the folded route none")
-        if sparse._wants_grad(*[lv.feats for lv in levels if isinstance(lv.feats, torch.Tensor)], *self.parameters()):
+        if _wants_grad(*[lv.feats for lv in levels if isinstance(lv.feats, torch.Tensor)], *self.parameters()):
             raise NotImplementedError("MinkNeck(differentiable=True) with eval-mode BatchNorms: training through frozen BatchNorms is not "
                                       "implemented; call bn.train() on the neck's BatchNorms (module.train()), or run under torch.no_grad()")
         return False

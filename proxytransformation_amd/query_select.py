@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from . import _abi, query_select_host
-from .sparse import (MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _index, _int32_array, _mask_bytes, _np, _ptr, _stream, _train,
+from ._doors import (MAX_QUERIES, MAX_SCENES, MAX_TEXT, _f32, _f32_grad, _gpu, _index, _int32_array, _mask_bytes, _np, _ptr, _stream, _train,
                      _width)
 
 __all__ = ["QuerySelect", "decode", "linear", "pack", "score", "select_bwd", "topk_sorted"]

@@ -43,15 +43,14 @@ CPU path for the layers themselves: tensors must be on the GPU and the library m
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
-import numpy as np
 import torch
 from torch import nn
 
 from . import _abi
+from ._doors import _channel_vectors, _f32, _f32_grad, _int32_array, _ptr, _stream, _train, _wants_grad, _workspace
 from .sparse_host import (_check_geometry, _segments, kernel_map_host, kernel_map_transpose_host, kernel_offsets,     # noqa: F401
                           sparse_conv3d_bwd_host, sparse_conv3d_host, sparse_max_pool3d_bwd_host, sparse_max_pool3d_host,
                           sparse_norm_bwd_host, sparse_norm_host)
@@ -142,113 +141,6 @@ def kernel_map(coords: torch.Tensor, scene_rows: Sequence[int], tensor_stride: i
                      tensor_stride=int(tensor_stride) * int(stride), n_in=n_in)
 
 
-def _f32(t: Optional[torch.Tensor], what: str, dev) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    if not t.is_cuda:
-        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
-    if t.device != dev:
-        raise ValueError(f"{what}: all tensors must be on {dev}")
-    t = t.detach()
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.to(torch.float32).contiguous()
-    return t
-
-
-def _f32_grad(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """fp32 and contiguous WITHOUT leaving the graph: the differentiable path's twin of ``_f32``, and what a backward makes of ``g``."""
-    if t is None or (t.dtype == torch.float32 and t.is_contiguous()):
-        return t
-    return t.to(torch.float32).contiguous()
-
-
-def _channel_vectors(what: str, C: int, dev, **vecs) -> list:
-    """The per-channel operands of a layer, each ``None`` or detached fp32 of ``C`` elements, flat."""
-    out = []
-    for name, v in vecs.items():
-        v = _f32(v, what, dev)
-        if v is not None:
-            v = v.reshape(-1)
-            if v.numel() != C:
-                raise ValueError(f"{what}: {name} must have {C} elements, got {v.numel()}")
-        out.append(v)
-    return out
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _int32_array(values: Sequence[int]):
-    """Scene / segment ends as the host array the entry points take."""
-    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
-
-
-MAX_SCENES, MAX_QUERIES, MAX_TEXT = 64, 1024, 256     # the limits of the stages behind the neck (csrc/head.h)
-
-
-def _stream(dev) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _gpu(what: str, *tensors) -> None:
-    if not all(t.is_cuda for t in tensors if t is not None):
-        raise RuntimeError(f"{what} (HIP) needs GPU tensors: there is no CPU path")
-
-
-def _width(what: str, C: int) -> int:
-    C = int(C)
-    if C % 64 or not 64 <= C <= 512:
-        raise ValueError(f"{what}: the feature width must be a multiple of 64 from 64 to 512, got {C}")
-    return C
-
-
-def _mask_bytes(what: str, name: str, mask: torch.Tensor, shape) -> torch.Tensor:
-    """``mask`` (the operand ``name`` of ``what``) as the contiguous bool tensor of ``shape`` the entry points read as bytes."""
-    _gpu(what, mask)
-    if tuple(mask.shape) != tuple(shape):
-        raise ValueError(f"{what}: {name} must be {tuple(shape)}, got {tuple(mask.shape)}")
-    if mask.dtype != torch.bool or not mask.is_contiguous():
-        mask = mask.to(torch.bool).contiguous()
-    return mask
-
-
-def _index(what: str, index: torch.Tensor, B: int) -> int:
-    """``K`` of a selection ``index (B,K)``: contiguous int64, as the entry points read it."""
-    if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != B or not index.is_contiguous():
-        raise ValueError(f"{what}: index must be contiguous int64 (B,K), got {index.dtype} {tuple(index.shape)}")
-    return int(index.shape[1])
-
-
-def _np(t, dt):
-    return (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)).astype(dt)
-
-
-def _wants_grad(*tensors) -> bool:
-    return torch.is_grad_enabled() and any(t is not None and t.is_floating_point() and t.requires_grad for t in tensors)
-
-
-def _train(what: str, differentiable: bool, *tensors) -> bool:
-    """The opt-in rule of every layer: record for autograd only with ``differentiable=True`` and an input that requires grad; without the
-    flag such an input is refused instead of being answered with a detached result."""
-    wanted = _wants_grad(*tensors)
-    if wanted and not differentiable:
-        raise NotImplementedError(f"{what} is inference-only by default: its backward pass is not enabled, and an input requires grad. "
-                                  f"Pass differentiable=True, or call it under torch.no_grad() (or detach the inputs)")
-    return wanted
-
-
-_WORKSPACES: dict = {}             # (tag, device, stream) -> uint8 workspace, reused across layers and steps, grown on demand
-
-
-def _workspace(tag: str, nbytes: int, dev) -> torch.Tensor:
-    key = (tag, str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _WORKSPACES[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    return ws
-
-
 def _transposed(kmap: KernelMap, n_in: int) -> torch.Tensor:
     """``kmap.nbr_t``, built by one call of ``ptx_sparse_kernel_map_transpose`` on the current stream the first time it is asked for."""
     if kmap.nbr_t is None:
@@ -256,8 +148,7 @@ def _transposed(kmap: KernelMap, n_in: int) -> torch.Tensor:
         nbr = kmap.nbr if kmap.nbr.is_contiguous() else kmap.nbr.contiguous()
         nbr_t = torch.empty((n_in, kvol), dtype=torch.int32, device=nbr.device)
         _abi.check(_abi.lib().ptx_sparse_kernel_map_transpose(nbr.data_ptr(), n_out, kvol, n_in, nbr_t.data_ptr(),
-                                                              torch.cuda.current_stream(nbr.device).cuda_stream),
-                   "ptx_sparse_kernel_map_transpose")
+                                                              _stream(nbr.device)), "ptx_sparse_kernel_map_transpose")
         kmap.nbr_t = nbr_t
     return kmap.nbr_t
 
@@ -269,12 +160,12 @@ def _conv_forward(feats, kmap, weight, vecs, residual, relu, elu=False) -> torch
     if elu or cin > 512:                                     # the neck's entry point: activation selector, Cin up to 1024
         _abi.check(_abi.lib().ptx_sparse_conv3d_act(feats.data_ptr(), feats.shape[0], kmap.nbr.data_ptr(), n_out, kvol, weight.data_ptr(), cin,
                                                     cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(residual),
-                                                    2 if elu else int(bool(relu)), out.data_ptr(),
-                                                    torch.cuda.current_stream(feats.device).cuda_stream), "ptx_sparse_conv3d_act")
+                                                    2 if elu else int(bool(relu)), out.data_ptr(), _stream(feats.device)),
+                   "ptx_sparse_conv3d_act")
         return out
     _abi.check(_abi.lib().ptx_sparse_conv3d(feats.data_ptr(), feats.shape[0], kmap.nbr.data_ptr(), n_out, kvol, weight.data_ptr(), cin,
                                             cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(residual), int(bool(relu)),
-                                            out.data_ptr(), torch.cuda.current_stream(feats.device).cuda_stream), "ptx_sparse_conv3d")
+                                            out.data_ptr(), _stream(feats.device)), "ptx_sparse_conv3d")
     return out
 
 
@@ -318,7 +209,7 @@ class _SparseConv3dFn(torch.autograd.Function):
         _abi.check(lib.ptx_sparse_conv3d_bwd(g.data_ptr(), _ptr(out), _ptr(scale), int(relu), feats.data_ptr(), n_in, kmap.nbr.data_ptr(),
                                              _ptr(nbr_t), n_out, kvol, weight.data_ptr(), cin, cout, _ptr(gz),
                                              _ptr(dres) if (relu and scale is not None) else None, _ptr(dbias), _ptr(dfeats), _ptr(dweight),
-                                             _ptr(ws), 0 if ws is None else ws.numel(), torch.cuda.current_stream(dev).cuda_stream),
+                                             _ptr(ws), 0 if ws is None else ws.numel(), _stream(dev)),
                    "ptx_sparse_conv3d_bwd")
         if dbias is not None:
             dbias = dbias.reshape(ctx.bias_shape)
@@ -333,7 +224,7 @@ class _SparseMaxPool3dFn(torch.autograd.Function):
         out = torch.empty((n_out, C), dtype=torch.float32, device=feats.device)
         arg = torch.empty((n_out, C), dtype=torch.uint8, device=feats.device)
         _abi.check(_abi.lib().ptx_sparse_max_pool3d_arg(feats.data_ptr(), kmap.nbr.data_ptr(), n_out, kvol, C, out.data_ptr(), arg.data_ptr(),
-                                                        torch.cuda.current_stream(feats.device).cuda_stream), "ptx_sparse_max_pool3d_arg")
+                                                        _stream(feats.device)), "ptx_sparse_max_pool3d_arg")
         ctx.kmap, ctx.n_in = kmap, int(feats.shape[0])
         ctx.save_for_backward(arg)
         return out
@@ -349,7 +240,7 @@ class _SparseMaxPool3dFn(torch.autograd.Function):
         dfeats = torch.empty((n_in, C), dtype=torch.float32, device=g.device)
         nbr_t = _transposed(kmap, n_in)
         _abi.check(_abi.lib().ptx_sparse_max_pool3d_bwd(g.data_ptr(), arg.data_ptr(), nbr_t.data_ptr(), n_in, n_out, kvol, C,
-                                                        dfeats.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream),
+                                                        dfeats.data_ptr(), _stream(g.device)),
                    "ptx_sparse_max_pool3d_bwd")
         return dfeats, None
 
@@ -420,7 +311,7 @@ def sparse_max_pool3d(feats: torch.Tensor, kmap: KernelMap, differentiable: bool
         return _SparseMaxPool3dFn.apply(_f32_grad(feats_in), kmap)
     out = torch.empty((n_out, feats.shape[1]), dtype=torch.float32, device=dev)
     _abi.check(_abi.lib().ptx_sparse_max_pool3d(feats.data_ptr(), kmap.nbr.data_ptr(), n_out, kvol, int(feats.shape[1]), out.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_max_pool3d")
+                                                _stream(dev)), "ptx_sparse_max_pool3d")
     return out
 
 
@@ -447,11 +338,11 @@ def _norm_forward(x, ends, eps, weight, bias, residual, relu, running=None, mome
     if elu:
         _abi.check(_abi.lib().ptx_sparse_norm_fwd_act(x.data_ptr(), seg, S, n, C, float(eps), _ptr(weight), _ptr(bias), _ptr(residual), 2, _ptr(rm),
                                                       _ptr(rv), float(momentum), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_fwd_act")
+                                                      _stream(dev)), "ptx_sparse_norm_fwd_act")
         return out, stats
     _abi.check(_abi.lib().ptx_sparse_norm_fwd(x.data_ptr(), seg, S, n, C, float(eps), _ptr(weight), _ptr(bias), _ptr(residual), int(bool(relu)),
                                               _ptr(rm), _ptr(rv), float(momentum), stats.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_fwd")
+                                              _stream(dev)), "ptx_sparse_norm_fwd")
     return out, stats
 
 
@@ -461,7 +352,7 @@ def _norm_apply(x, ends, stats, weight, bias, residual, relu):
     out = torch.empty_like(x)
     seg = _int32_array(ends)
     _abi.check(_abi.lib().ptx_sparse_norm_apply(x.data_ptr(), seg, S, n, C, stats.data_ptr(), _ptr(weight), _ptr(bias), _ptr(residual),
-                                                int(bool(relu)), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream),
+                                                int(bool(relu)), out.data_ptr(), _stream(x.device)),
                "ptx_sparse_norm_apply")
     return out
 
@@ -500,13 +391,13 @@ class _SparseNormFn(torch.autograd.Function):
             ws = _norm_workspace(n, S, C, dev)
             _abi.check(_abi.lib().ptx_sparse_norm_bwd_act(g.data_ptr(), x.data_ptr(), _ptr(out), 2, _int32_array(ctx.ends), S, n, C,
                                                           stats.data_ptr(), _ptr(w), _ptr(dx), _ptr(dw), _ptr(db), _ptr(dres), ws.data_ptr(),
-                                                          ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_bwd_act")
+                                                          ws.numel(), _stream(dev)), "ptx_sparse_norm_bwd_act")
         elif need_x or need_w or need_b or (need_r and ctx.relu):
             ws = _norm_workspace(n, S, C, dev)
             seg = _int32_array(ctx.ends)
             _abi.check(_abi.lib().ptx_sparse_norm_bwd(g.data_ptr(), x.data_ptr(), _ptr(out), seg, S, n, C, stats.data_ptr(), _ptr(w), _ptr(dx),
                                                       _ptr(dw), _ptr(db), _ptr(dres) if ctx.relu else None, ws.data_ptr(), ws.numel(),
-                                                      torch.cuda.current_stream(dev).cuda_stream), "ptx_sparse_norm_bwd")
+                                                      _stream(dev)), "ptx_sparse_norm_bwd")
         if dw is not None:
             dw = dw.reshape(ctx.shapes[0])
         if db is not None:

@@ -28,7 +28,7 @@ import torch
 from torch import nn
 
 from . import _abi, text_encoder_host
-from .sparse import MAX_SCENES, MAX_TEXT, _ptr, _stream
+from ._doors import MAX_SCENES, MAX_TEXT, PreparedOperands, _np, _ptr, _stream
 
 __all__ = ["ClipTextEncoder"]
 
@@ -78,7 +78,7 @@ class _TextModel(nn.Module):
         self.final_layer_norm = nn.LayerNorm(C, eps=eps)
 
 
-class ClipTextEncoder(nn.Module):
+class ClipTextEncoder(PreparedOperands, nn.Module):
     """``ClipTextEncoder(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
     max_position_embeddings=77, layer_norm_eps=1e-5, hidden_act='quick_gelu')``: ``CLIPTextConfig``'s keywords, ``CLIPTextModel``'s
     parameter names (``text_model.embeddings.token_embedding.weight``, ``text_model.encoder.layers.{i}.self_attn.q_proj.weight``, ...,
@@ -90,7 +90,7 @@ class ClipTextEncoder(nn.Module):
     ``'quick_gelu'`` raises ``NotImplementedError``.
 
     The operands the launches take (the concatenated ``[q|k|v]`` weight) are prepared once and rebuilt when a parameter is replaced or
-    its ``_version`` changes (``load_state_dict``, in-place updates), as ``GroundingDecoder`` does it."""
+    its ``_version`` changes (``load_state_dict``, in-place updates): ``_doors.PreparedOperands``."""
 
     def __init__(self, vocab_size: int = 49408, hidden_size: int = 768, intermediate_size: int = 3072, num_hidden_layers: int = 12,
                  num_attention_heads: int = 12, max_position_embeddings: int = 77, layer_norm_eps: float = 1e-5,
@@ -118,7 +118,6 @@ class ClipTextEncoder(nn.Module):
         self.text_model = _TextModel(self.vocab_size, self.max_position_embeddings, C, I, self.num_hidden_layers, self.layer_norm_eps)
         for p in self.parameters():
             p.requires_grad_(False)                          # lr_mult=0.0 in the reference: never trained
-        self._prepared = None
 
     # -- checkpoints
     @staticmethod
@@ -135,33 +134,20 @@ class ClipTextEncoder(nn.Module):
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         return super().load_state_dict(self.normalise_names(state_dict), strict=strict, **kw)
 
-    # -- the operands the launches take, rebuilt when a parameter changes
-    def _apply(self, fn, *args, **kwargs):
-        self._prepared = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def _state_key(self, dev):
-        return (str(dev),) + tuple((id(t), t.data_ptr(), t._version) for t in self.parameters())
-
-    def _prepare(self, dev) -> dict:
-        key = self._state_key(dev)
-        if self._prepared is not None and self._prepared["key"] == key:
-            return self._prepared
+    # -- the operands the launches take (PreparedOperands._prepare caches them)
+    def _build_operands(self, dev) -> dict:
         f = lambda t: t.detach().to(dev, torch.float32).contiguous()      # noqa: E731
         tm = self.text_model
-        prep = dict(key=key, tensors=list(self.parameters()), tok=f(tm.embeddings.token_embedding.weight),
-                    pos=f(tm.embeddings.position_embedding.weight), fw=f(tm.final_layer_norm.weight), fb=f(tm.final_layer_norm.bias),
-                    layers=[])
-        with torch.no_grad():
-            for layer in tm.encoder.layers:
-                a = layer.self_attn
-                prep["layers"].append(dict(
-                    ln1=(f(layer.layer_norm1.weight), f(layer.layer_norm1.bias)), ln2=(f(layer.layer_norm2.weight), f(layer.layer_norm2.bias)),
-                    wqkv=torch.cat([f(a.q_proj.weight), f(a.k_proj.weight), f(a.v_proj.weight)]).contiguous(),
-                    bqkv=torch.cat([f(a.q_proj.bias), f(a.k_proj.bias), f(a.v_proj.bias)]).contiguous(),
-                    wo=f(a.out_proj.weight), bo=f(a.out_proj.bias), w1=f(layer.mlp.fc1.weight), b1=f(layer.mlp.fc1.bias),
-                    w2=f(layer.mlp.fc2.weight), b2=f(layer.mlp.fc2.bias)))
-        self._prepared = prep
+        prep = dict(tok=f(tm.embeddings.token_embedding.weight), pos=f(tm.embeddings.position_embedding.weight),
+                    fw=f(tm.final_layer_norm.weight), fb=f(tm.final_layer_norm.bias), layers=[])
+        for layer in tm.encoder.layers:
+            a = layer.self_attn
+            prep["layers"].append(dict(
+                ln1=(f(layer.layer_norm1.weight), f(layer.layer_norm1.bias)), ln2=(f(layer.layer_norm2.weight), f(layer.layer_norm2.bias)),
+                wqkv=torch.cat([f(a.q_proj.weight), f(a.k_proj.weight), f(a.v_proj.weight)]).contiguous(),
+                bqkv=torch.cat([f(a.q_proj.bias), f(a.k_proj.bias), f(a.v_proj.bias)]).contiguous(),
+                wo=f(a.out_proj.weight), bo=f(a.out_proj.bias), w1=f(layer.mlp.fc1.weight), b1=f(layer.mlp.fc1.bias),
+                w2=f(layer.mlp.fc2.weight), b2=f(layer.mlp.fc2.bias)))
         return prep
 
     # -- the forward
@@ -218,12 +204,11 @@ class ClipTextEncoder(nn.Module):
 
     def forward_host(self, input_ids, attention_mask=None, dtype=np.float64) -> np.ndarray:
         """The same chain in numpy ``dtype`` (``text_encoder_host.forward_host``): the specification.  It calls no device code."""
-        arr = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)      # noqa: E731
-        ids = arr(input_ids)
+        ids = _np(input_ids)
         if ids.ndim != 2 or ids.dtype.kind not in "iu":
             raise ValueError(f"ClipTextEncoder.forward_host: input_ids must be integers (B,T), got {ids.dtype} {ids.shape}")
         if ids.shape[1] > self.max_position_embeddings:
             raise ValueError(f"ClipTextEncoder.forward_host: T={ids.shape[1]} exceeds the position table ({self.max_position_embeddings})")
-        params = {k: arr(v) for k, v in self.state_dict().items()}
-        mask = None if attention_mask is None else arr(attention_mask) != 0
+        params = {k: _np(v) for k, v in self.state_dict().items()}
+        mask = None if attention_mask is None else _np(attention_mask) != 0
         return text_encoder_host.forward_host(params, ids, mask, self.num_attention_heads, self.layer_norm_eps, dtype)

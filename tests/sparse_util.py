@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from proxytransformation_amd import _abi, sparse
+from tests.util import header_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
@@ -301,16 +302,15 @@ def composition(feats, nbr, weight, bias=None, scale=None, shift=None, residual=
 def assert_declared(names):
     """Every name is declared ``PTX_API`` in include/proxyt.h, bound in ``_abi.SIGNATURES``, exported by csrc/exports.map and found in the
     loaded library.  Returns ``{name: its parameter list as the header spells it}``."""
-    code = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "proxyt.h")).read(), flags=re.S)
+    protos = header_prototypes()
     patterns = re.findall(r"global:\s*([^;]+);", open(os.path.join(ROOT, "proxytransformation_amd", "csrc", "exports.map")).read())
     assert patterns
     lib = _abi.lib()
     params = {}
     for name in names:
-        m = re.search(r"PTX_API\s+\w+\s+" + name + r"\s*\(([^;]*)\)\s*;", code)
-        assert m, name
+        assert name in protos, name
         assert name in _abi.SIGNATURES, name
         assert any(re.fullmatch(p.strip().replace("*", ".*"), name) for p in patterns), name
         getattr(lib, name)
-        params[name] = m.group(1)
+        params[name] = ", ".join(protos[name][1])
     return params

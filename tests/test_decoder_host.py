@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from proxytransformation_amd import GroundingDecoder, _abi, decoder, decoder_host as dh
+from proxytransformation_amd import ClipTextEncoder, GroundingDecoder, ResNet, _abi, decoder, decoder_host as dh
 from tests import decoder_util as du
 from tests import query_select_util as qu
 from tests import sparse_util as su
@@ -212,37 +212,69 @@ def test_host_chain_with_two_groups_of_hoisted_projections_is_the_torch_stage():
                     assert su.rel(a32[lid], a64[lid]) < 1e-5, (name, T, lid)
 
 
-def test_prepared_operands_are_rebuilt_when_a_parameter_is_replaced_or_changed():
-    """``_prepare`` returns the same object while nothing changed, and a new one after ``load_state_dict``, an in-place update under
-    ``no_grad`` (a parameter, a BatchNorm buffer) and after a parameter is REPLACED by a new ``nn.Parameter`` of the same ``_version`` --
-    the version alone does not identify a tensor."""
+def _cached_decoder(seed=21):
+    m = du.module(**du.SMALL, seed=seed)
+    return m, m.layers[0].cross_attn.attn, "in_proj_weight", lambda prep: prep["layers"][0]["cross_attn"]["w"]
+
+
+def _cached_text_encoder(seed=21):
+    torch.manual_seed(seed)
+    m = ClipTextEncoder(vocab_size=64, hidden_size=64, intermediate_size=64, num_hidden_layers=1, num_attention_heads=1,
+                        max_position_embeddings=8)
+    return m, m.text_model.encoder.layers[0].self_attn.out_proj, "weight", lambda prep: prep["layers"][0]["wo"]
+
+
+def _cached_resnet(seed=21):
+    torch.manual_seed(seed)
+    m = ResNet(depth=50, base_channels=16, num_stages=1, out_indices=(0,))
+    return m, m.layer1[0].conv1, "weight", lambda prep: prep["stages"][0][0]["w1"].reshape(16, 16, 1, 1)
+
+
+@pytest.mark.parametrize("make", [_cached_decoder, _cached_text_encoder, _cached_resnet], ids=["decoder", "text_encoder", "resnet"])
+def test_prepared_operands_are_rebuilt_when_a_parameter_is_replaced_or_changed(make):
+    """The one cache of prepared operands (``_doors.PreparedOperands``) under its three modules, each at its smallest size: ``_prepare``
+    returns the same object while nothing changed, and a new one after ``load_state_dict`` (copying, and with ``assign=True``), an
+    in-place update under ``no_grad`` (a parameter, a BatchNorm's floating-point buffer) and after a parameter is REPLACED by a new
+    ``nn.Parameter`` of the same ``_version`` -- the version alone does not identify a tensor.  An integer buffer
+    (``num_batches_tracked``) is not watched: no operand reads it."""
     cpu = torch.device("cpu")
-    m = du.module(**du.SMALL)
+    m, holder, attr, operand = make()
     first = m._prepare(cpu)
     assert m._prepare(cpu) is first
-    attn = m.layers[0].cross_attn.attn
-    old = attn.in_proj_weight
+    old = getattr(holder, attr)
     new = torch.nn.Parameter(old.detach().clone() * 2)
     with torch.no_grad():
         while new._version < old._version:
             new.add_(0.0)
     assert new._version == old._version and new is not old
-    attn.in_proj_weight = new
+    setattr(holder, attr, new)
     second = m._prepare(cpu)
     assert second is not first and m._prepare(cpu) is second
-    assert torch.equal(second["layers"][0]["cross_attn"]["w"], new.detach())
-    assert torch.equal(second["groups"][0]["cross_attn"][0][:64], new.detach()[64:128])          # the hoisted [K_0 K_1 | V_0 V_1]
-    assert torch.equal(first["groups"][0]["cross_attn"][0][:64], old.detach()[64:128])
+    assert torch.equal(operand(second), new.detach()) and torch.equal(operand(first), old.detach())
+    if make is _cached_decoder:
+        assert torch.equal(second["groups"][0]["cross_attn"][0][:64], new.detach()[64:128])      # the hoisted [K_0 K_1 | V_0 V_1]
+        assert torch.equal(first["groups"][0]["cross_attn"][0][:64], old.detach()[64:128])
+    other = make(seed=5)[0]
+    changes = [lambda: new.mul_(0.5), lambda: m.load_state_dict(other.state_dict()),
+               lambda: m.load_state_dict(make(seed=6)[0].state_dict(), assign=True)]
+    if make is _cached_decoder:
+        changes.insert(1, lambda: m.cross_posembed.position_embedding_head[1].running_var.mul_(1.5))
+    if make is _cached_resnet:
+        changes.insert(1, lambda: m.bn1.running_var.mul_(2))
     last = second
-    changes = (lambda: new.mul_(0.5), lambda: m.cross_posembed.position_embedding_head[1].running_var.mul_(1.5),
-               lambda: m.load_state_dict(du.module(**du.SMALL, seed=5).state_dict()))
-    for change in changes:
+    for i, change in enumerate(changes):
         with torch.no_grad():
             change()
         again = m._prepare(cpu)
-        assert again is not last and m._prepare(cpu) is again
+        assert again is not last and m._prepare(cpu) is again, i
         last = again
-    assert torch.equal(last["layers"][0]["cross_attn"]["w"], du.module(**du.SMALL, seed=5).layers[0].cross_attn.attn.in_proj_weight.detach())
+        if change is changes[-2]:
+            assert torch.equal(operand(last), getattr(make(seed=5)[1], attr).detach())
+    assert torch.equal(operand(last), getattr(make(seed=6)[1], attr).detach())
+    if make is _cached_resnet:
+        before = m.bn1.num_batches_tracked.item()
+        m.bn1.num_batches_tracked.add_(1)
+        assert m.bn1.num_batches_tracked.item() == before + 1 and m._prepare(cpu) is last
 
 
 # ------------------------------------------------------------------------------------------------------------------ the ABI

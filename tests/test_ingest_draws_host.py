@@ -4,13 +4,13 @@ restatement of the kernel's draws, which the GPU tests pin the kernel to bit for
 deterministic."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 from proxytransformation_amd import _abi
 from proxytransformation_amd.ingest import MultiViewIngest, device_choices, scene_key
+from tests.util import header_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PTX_EINVAL = -1
@@ -31,7 +31,7 @@ def _chi2(counts, expected):
 
 def test_header_declares_and_library_exports_the_draw():
     src = open(os.path.join(ROOT, "include", "proxyt.h")).read()
-    assert re.search(r"PTX_API int ptx_ingest_draw\(", src)
+    assert header_prototypes()["ptx_ingest_draw"][0] == "int"
     assert "#define PTX_ABI_VERSION 13" in src and _abi.ABI_VERSION == 13
     assert "ptx_ingest_draw" in _abi.SIGNATURES
     lib = _abi.lib()

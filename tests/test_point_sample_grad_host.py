@@ -2,12 +2,12 @@
 ``ptx_point_sample_bwd_workspace_bytes``): declared, bound and exported by both builds, ABI still 13, and every argument check made
 on the host before anything is enqueued (the pointers handed in are bogus and never touched)."""
 import os
-import re
 import subprocess
 
 import pytest
 
 from proxytransformation_amd import _abi
+from tests.util import header_prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PTX_EINVAL, PTX_ENOSPACE = -1, -3
@@ -16,8 +16,9 @@ NAMES = ("ptx_point_sample_bwd_workspace_bytes", "ptx_point_sample_bwd")
 
 def test_header_declares_and_both_libraries_export_the_backward():
     src = open(os.path.join(ROOT, "include", "proxyt.h")).read()
-    assert re.search(r"PTX_API size_t ptx_point_sample_bwd_workspace_bytes\(int N, int V, int H, int W, int bilinear\);", src)
-    assert re.search(r"PTX_API int ptx_point_sample_bwd\(", src)
+    protos = header_prototypes()
+    assert protos["ptx_point_sample_bwd_workspace_bytes"] == ("size_t", ["int N", "int V", "int H", "int W", "int bilinear"])
+    assert protos["ptx_point_sample_bwd"][0] == "int"
     assert "#define PTX_ABI_VERSION 13" in src and _abi.ABI_VERSION == 13
     lib = _abi.lib()
     assert lib.ptx_abi_version() == 13

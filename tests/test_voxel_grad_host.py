@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import torch
 
+from tests.util import header_prototypes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("ptx_voxelize_rep", "ptx_voxel_features_bwd")
 
@@ -80,15 +82,9 @@ def test_the_rule_on_empty_inputs():
 
 
 # ------------------------------------------------------------------ the ABI surface
-def _prototypes():
-    src = open(os.path.join(ROOT, "include", "proxyt.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"PTX_API\s+[a-z_0-9 ]+?\**\s*(ptx_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;", src, flags=re.S)}
-
-
 def test_header_declares_the_two_entry_points_and_the_binding_matches():
     from proxytransformation_amd import _abi
-    protos = _prototypes()
+    protos = {name: ", ".join(params) for name, (_, params) in header_prototypes().items()}
     assert len(protos) >= 90 and "ptx_voxelize_ex" in protos
     for name in NEW:
         assert name in protos, f"{name} is not declared in include/proxyt.h"

@@ -2,8 +2,9 @@
 from __future__ import annotations
 
 import os
+import re
 from functools import lru_cache
-from typing import Dict
+from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
@@ -13,6 +14,22 @@ from proxytransformation_amd.synth import PreshapeConfig, fill_state_dict
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 GOLDEN_CASES = ("g1_cfg1", "g2_sparse", "g3_room")
+HEADER = os.path.join(os.path.dirname(GOLDEN_DIR), os.pardir, "include", "proxyt.h")
+
+
+@lru_cache(maxsize=None)
+def header_prototypes() -> Dict[str, Tuple[str, List[str]]]:
+    """``{name: (return type, [parameter declarations])}`` of every ``PTX_API`` prototype of include/proxyt.h with its comments
+    stripped, each declaration as the header spells it with its white space collapsed; ``(void)`` is no parameter."""
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(HEADER).read(), flags=re.S)
+    one = lambda text: " ".join(text.split())      # noqa: E731
+    protos = {}
+    for m in re.finditer(r"\bPTX_API\s+([^;()]*?)\s*\b(ptx_[a-z0-9_]+)\s*\(([^;()]*)\)\s*;", code):
+        params = [one(p) for p in m.group(3).split(",")]
+        assert m.group(2) not in protos and all(params), m.group(0)
+        protos[m.group(2)] = (one(m.group(1)), [] if params == ["void"] else params)
+    assert len(protos) == len(re.findall(r"^\s*PTX_API\b", code, flags=re.M)), "a PTX_API declaration that header_prototypes cannot read"
+    return protos
 
 
 @lru_cache(maxsize=None)

@@ -1203,6 +1203,45 @@ PTX_API int ptx_conv1x1(const float *x, int N, int Cin, int H, int W, const floa
 PTX_API int ptx_conv3x3(const float *x, int N, int C, int H, int W, const float *weight, int stride, const float *scale,
                         const float *shift, const float *residual, int relu, float *out, void *stream);
 
+/* ------------------------------------------------------------------ backward of ptx_conv1x1 / ptx_conv3x3 (ABI 13, by addition)
+ * csrc/conv2d_bwd.hip, restated in numpy by image_backbone_grad_host.py.  With z the convolution before the epilogue, out =
+ * relu((z * scale + shift) + residual) the forward's result and g = d loss / d out (N,Cout,Ho,Wo); every BatchNorm is frozen: scale and
+ * shift take no gradient and there is no dbias.  Each of dresidual, dx, dweight is optional: NULL means it is not computed and its work
+ * is not done.
+ *   gz        (N,Cout,Ho,Wo) = g * [out > 0] * scale[co], each factor only where present (relu: 0 or 1, out is read only with relu;
+ *             scale may be NULL); the mask is ptx_sparse_conv3d_bwd's: a NaN out passes nothing.  Scratch the call writes; required when
+ *             (relu or scale) and (dx or dweight).  Without relu and scale the products read g itself and gz is not touched.
+ *   dresidual (N,Cout,Ho,Wo) = g * [out > 0].  gz and dresidual come from one launch of their own (k_conv_epi_bwd), ahead of the others.
+ *   dx        (N,Cin,H,W): dx[n,ci,y,x] = sum over every (ky, kx, co) whose output (oy, ox) = ((y + 1 - ky) / s, (x + 1 - kx) / s) exists
+ *             (both numerators even at s = 2, inside the map; 1x1: (y / s, x / s)) of weight[co,ci,ky,kx] * gz[n,co,oy,ox], k = (ky, kx, co)
+ *             ascending on the forward's tiles (16 rows x 256 pixels below 64 input channels, steps of 32 k; else 64 x 64, steps of 64 k;
+ *             each step from zero, then added).  Every element is written: a pixel no output reads (odd rows and columns of a strided
+ *             1x1) gets 0.0f; at stride 2 the structurally absent taps are multiplied by zero, the pixels are not split by parity.
+ *             dx_accumulate = 1: the completed sum is added to what dx held, one rounding.  The weight is taken in the forward's layout
+ *             and re-laid as (ci, ky, kx, co) into the workspace by a launch inside the call (k_conv_wt): no prepared transposed
+ *             operand exists, so nothing has to be rebuilt after an optimizer step and every call pays for the re-layout.
+ *   dweight   in the weight operand's layout, (Cout,Cin) or (co,ky,kx,ci): dweight[co,k] = sum over (n, oy, ox) of gz[n,co,oy,ox] *
+ *             x[n,ci,s oy - 1 + ky,s ox - 1 + kx]; a tap outside the image is never read.  The flattened pixel index is cut into T =
+ *             ceil(N Ho Wo / 64) steps of 64 and the steps are dealt evenly to S = ptx_conv_dweight_chunks(...) chunks (chunk c: steps
+ *             [c T / S, (c + 1) T / S)); a chunk sums its steps in ascending order, each step's product from zero on the exact-fp32 matrix
+ *             instruction and then added; the chunks' partials are added in ascending order (ptx_sparse_conv3d_bwd's slab sum).  S =
+ *             min(ceil(1024 / tiles), ceil(T / 4), 256 MiB / the weight's bytes), at least 1, tiles = ceil(Cout / 64) ceil(K / 64): a function
+ *             of the shapes only, which never falls when N grows.
+ * No float atomics: two calls give the same bits.  Widths: multiples of 16, 16 to 2048 (1x1) / 16 to 512 (3x3); N, H, W, stride as the
+ * forward takes them; x (N,Cin,H,W) is needed for dweight, weight for dx.  All float buffers and the workspace 16-byte aligned; no output
+ * (gz, dresidual, dx, dweight, workspace) may overlap an input or another output.  workspace: ptx_conv_bwd_workspace_bytes(KS, ...) bytes
+ * (KS 1 or 3, 3 with Cin = Cout; a function of the shapes only; 0: unsupported), needed for dx and, with S > 1, for dweight; a short one is
+ * PTX_ENOSPACE.  Host checks (PTX_EINVAL with the numbers) come before anything is enqueued.  ptx_conv_dweight_chunks launches nothing
+ * and answers PTX_EINVAL (negative) for unsupported shapes. */
+PTX_API size_t ptx_conv_bwd_workspace_bytes(int KS, int N, int Cin, int Cout, int H, int W, int stride);
+PTX_API int ptx_conv_dweight_chunks(int KS, int N, int Cin, int Cout, int H, int W, int stride);
+PTX_API int ptx_conv1x1_bwd(const float *g, const float *out, const float *scale, int relu, const float *x, int N, int Cin, int H, int W,
+                            const float *weight, int Cout, int stride, float *gz, float *dresidual, float *dx, int dx_accumulate,
+                            float *dweight, void *workspace, size_t ws_bytes, void *stream);
+PTX_API int ptx_conv3x3_bwd(const float *g, const float *out, const float *scale, int relu, const float *x, int N, int C, int H, int W,
+                            const float *weight, int stride, float *gz, float *dresidual, float *dx, int dx_accumulate, float *dweight,
+                            void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

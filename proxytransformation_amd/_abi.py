@@ -296,6 +296,10 @@ SIGNATURES.update({
     "ptx_conv_stem": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P]),
     "ptx_conv1x1": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P]),
     "ptx_conv3x3": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "ptx_conv_bwd_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "ptx_conv_dweight_chunks": (_I, [_I, _I, _I, _I, _I, _I, _I]),
+    "ptx_conv1x1_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
+    "ptx_conv3x3_bwd": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _Z, _P]),
 })
 
 _lib: Optional[C.CDLL] = None

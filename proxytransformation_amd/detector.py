@@ -76,9 +76,10 @@ class GroundingDetector(nn.Module):
     trained (``lr_mult=0.0`` in the reference): it runs under ``no_grad`` and its parameters receive no gradient.  ``backbone``: None
     (the default: the module, its ``state_dict`` and its methods are what they were), an ``image_backbone.ResNet`` or its config dict
     (``type='mmdet.ResNet'``); ``pixel_mean`` / ``pixel_std`` / ``bgr_to_rgb``: the data preprocessor's values, applied by the backbone's
-    stem.  The backbone is inference-only: with ``differentiable=True`` in training the loss's backward stops at its output and its
-    parameters get no gradient -- this DIFFERS from the reference, which trains the convolutions of stages 2 to 4
-    (``frozen_stages=1``); training the 2D backbone is out of scope.
+    stem.  The detector's own ``differentiable=`` is NOT forwarded to the backbone: a backbone built from a plain config is
+    inference-only, the loss's backward stops at its output and its parameters get no gradient.  Training it, as the reference does
+    for the convolutions of stages 2 to 4 (``frozen_stages=1``), is asked for with ``backbone=dict(..., differentiable=True)`` or a ready
+    ``ResNet(differentiable=True)``: ``loss(..., imgs=imgs)`` then reaches those kernels through the levels' gradient.
 
     Inputs of every method: ``points`` list of B ``(N_b,3)``; ``encoded_text (B,T,text_width)``, ``text_token_mask (B,T)`` bool (True =
     token); ``img_features`` one ``(B,V,C_l,H_l,W_l)`` per backbone level; ``scenes`` one dict per sample with ``depth2img =
@@ -271,8 +272,10 @@ class GroundingDetector(nn.Module):
         return self.encode_text(input_ids, attention_mask)
 
     def extract_image_features(self, imgs: torch.Tensor) -> List[torch.Tensor]:
-        """DET:357-379: the backbone's levels ``(B,V,C_l,H_l,W_l)`` of ``imgs (B,V,3,H,W)`` (float32 or uint8), detached; the data
-        preprocessor's ``pixel_mean`` / ``pixel_std`` / ``bgr_to_rgb`` are applied by the stem."""
+        """DET:357-379: the backbone's levels ``(B,V,C_l,H_l,W_l)`` of ``imgs (B,V,3,H,W)`` (float32 or uint8); the data
+        preprocessor's ``pixel_mean`` / ``pixel_std`` / ``bgr_to_rgb`` are applied by the stem.  Detached -- unless the backbone records
+        (``ResNet(differentiable=True)``, grad mode on, a trainable kernel that requires grad): then the levels of its trainable stages
+        are attached to its kernels."""
         if self.backbone is None:
             raise ValueError("GroundingDetector: imgs need a backbone; construct the detector with backbone=")
         if not isinstance(imgs, torch.Tensor) or imgs.dim() != 5:

@@ -12,13 +12,17 @@ between the launches and in the result.  No device synchronise, no torch op on t
 (the stem: plain FMA); no float atomics and a fixed k order: two calls give the same bits, and an image's levels depend neither on the
 batch nor on ``chunk``.
 
-Always inference: the forward runs under ``no_grad``, the parameters do not require grad, no gradient reaches the images.  This DIFFERS
-from the reference, which trains the convolutions of stages 2 to 4 (``frozen_stages=1``): training the backbone is out of scope.
+By default inference: the forward runs under ``no_grad``, the parameters do not require grad, no gradient reaches the images.
+``differentiable=True`` trains what the reference trains (``frozen_stages=1``: the convolutions of stages 2 to 4): the kernels of the
+stages ``> frozen_stages`` require grad and a forward in grad mode records the trainable tail as one autograd node, whose backward is
+``ptx_conv1x1_bwd`` / ``ptx_conv3x3_bwd`` (csrc/conv2d_bwd.hip) block by block in reverse, restated by ``image_backbone_grad_host.py``.
+Out of scope there: ``frozen_stages < 1`` (the stem's and the max-pool's backward), a gradient to the images, a trainable or
+training-mode BatchNorm, ``chunk`` while recording, double backward, activation checkpointing (``with_cp``).
 
 Parity-unpinned: the parameter names and shapes are torchvision's / mmdet's as restated from the config and the well-known layout
 (tests/golden/image_backbone_state_dict.json), not checked against a real checkpoint file; mmdet and torchvision are not dependencies.
 
-Out of scope: BasicBlock depths (18 / 34), ``style='caffe'``, ``deep_stem``, ``avg_down``, dilation, DCN, plugins, bf16 / fp16, training.
+Out of scope: BasicBlock depths (18 / 34), ``style='caffe'``, ``deep_stem``, ``avg_down``, dilation, DCN, plugins, bf16 / fp16.
 There is no CPU path: the module must be on the GPU and the library must be built."""
 from __future__ import annotations
 
@@ -28,8 +32,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _abi, image_backbone_host
-from ._doors import PreparedOperands, _np, _ptr, _stream
+from . import _abi, image_backbone_grad_host, image_backbone_host
+from ._doors import PreparedOperands, _np, _ptr, _stream, _workspace
 from .image_backbone_host import ARCH, EPS, EXPANSION
 from .registry import MODELS, REGISTRY_BACKEND
 from .sparse import bn_fold
@@ -61,6 +65,86 @@ def _refuse(name: str, value, why: str):
     raise NotImplementedError(f"{WHO}: {name}={value!r} is not implemented ({why})")
 
 
+class _Tail(torch.autograd.Function):
+    """The trainable tail as one autograd node: ``(trainable kernels...) -> (the levels of the stages >= frozen)``.  The forward is
+    ``ResNet._stages`` with every block's ``x, t1, t2, idn, out`` kept.  The backward walks the blocks in reverse, per block in the
+    order of ``image_backbone_grad_host.bottleneck_grad_host``: ``ptx_conv1x1_bwd`` of ``conv3`` (its ``dresidual`` is the identity
+    branch's gradient), ``ptx_conv3x3_bwd`` of ``conv2``, ``ptx_conv1x1_bwd`` of the ``downsample`` where there is one (it writes the
+    block's input gradient), ``ptx_conv1x1_bwd`` of ``conv1`` with ``dx_accumulate`` onto what the identity branch left.  A level that is
+    both an output and the next stage's input: the next stage's first block starts its input gradient from a copy of the level's
+    gradient and its downsample accumulates too -- ``(level + downsample) + conv1``; that copy is the one torch op on the data path.
+    The first trainable block computes no input gradient.  No device synchronise; no double backward."""
+
+    @staticmethod
+    def forward(ctx, net, prep, cur, ch, cw, frozen, levels, *weights):
+        keep: list = []
+        with torch.no_grad():
+            net._stages(prep, cur, ch, cw, frozen, net.out_indices[-1] + 1, levels, 0, keep)
+        outs = tuple(levels[s] for s in net.out_indices if s >= frozen)
+        ctx.keep, ctx.frozen, ctx.stages = keep, frozen, [s for s in net.out_indices if s >= frozen]
+        ctx.names = net._trainable_names(net.out_indices[-1] + 1)
+        ctx.save_for_backward(*weights, *outs)              # an in-place write to a kernel or a level before the backward is an error
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        ctx.saved_tensors                                   # (the version check)
+        keep, frozen = ctx.keep, ctx.frozen
+        dev = keep[0][3].device
+        lib, st = _abi.lib(), _stream(dev)
+        level_grad = {s: g.to(torch.float32).contiguous() for s, g in zip(ctx.stages, grads)}
+        need = dict(zip(ctx.names, ctx.needs_input_grad[7:]))
+        like = lambda t: torch.empty(t.shape, dtype=torch.float32, device=dev)      # noqa: E731
+        got = {}
+
+        def bwd(KS, name, g, out, scale, relu, x, w, cin, cout, stride, dres, dx, acc):
+            n, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+            dw = None
+            if need[name]:
+                dw = got[name] = torch.empty((cout, cin) if KS == 1 else (cout, 3, 3, cin), dtype=torch.float32, device=dev)
+            gz = like(g) if (dx is not None or dw is not None) else None
+            nbytes = int(lib.ptx_conv_bwd_workspace_bytes(KS, n, cin, cout, H, W, stride))
+            ws = _workspace("conv_bwd", nbytes, dev)
+            if KS == 1:
+                rc = lib.ptx_conv1x1_bwd(g.data_ptr(), _ptr(out), scale.data_ptr(), relu, x.data_ptr(), n, cin, H, W, w.data_ptr(), cout, stride,
+                                         _ptr(gz), _ptr(dres), _ptr(dx), acc, _ptr(dw), ws.data_ptr(), nbytes, st)
+            else:
+                rc = lib.ptx_conv3x3_bwd(g.data_ptr(), _ptr(out), scale.data_ptr(), relu, x.data_ptr(), n, cin, H, W, w.data_ptr(), stride,
+                                         _ptr(gz), _ptr(dres), _ptr(dx), acc, _ptr(dw), ws.data_ptr(), nbytes, st)
+            _abi.check(rc, "ptx_conv1x1_bwd" if KS == 1 else "ptx_conv3x3_bwd")
+
+        g = None
+        for s, b, d, x, t1, t2, idn, out in reversed(keep):
+            p = f"layer{s + 1}.{b}."
+            if g is None:
+                g = level_grad[s]                           # the last stage
+            first = s == frozen and b == 0                  # its input comes from a frozen stage: no input gradient
+            dres, dt2, dt1 = like(out), like(t2), like(t1)
+            bwd(1, p + "conv3.weight", g, out, d["bn3"][0], 1, t2, d["w3"], d["planes"], d["out"], 1, dres, dt2, 0)
+            bwd(3, p + "conv2.weight", dt2, t2, d["bn2"][0], 1, t1, d["w2"], d["planes"], d["planes"], d["stride"], None, dt1, 0)
+            dcur, held = None, 1
+            if d["wd"] is not None:
+                joined = level_grad.get(s - 1) if b == 0 and not first else None
+                if not first:
+                    dcur = joined.clone() if joined is not None else like(x)
+                bwd(1, p + "downsample.0.weight", dres, None, d["bnd"][0], 0, x, d["wd"], d["inplanes"], d["out"], d["stride"], None, dcur,
+                    1 if joined is not None else 0)
+            elif not first:
+                dcur = dres                                 # the identity
+            bwd(1, p + "conv1.weight", dt1, t1, d["bn1"][0], 1, x, d["w1"], d["inplanes"], d["planes"], 1, None, dcur, held)
+            g = dcur
+        dws = []
+        for name in ctx.names:
+            dw = got.get(name)
+            if dw is not None and dw.dim() == 4:
+                dw = dw.permute(0, 3, 1, 2)                 # (co,ky,kx,ci) -> the parameter's (co,ci,ky,kx)
+            elif dw is not None:
+                dw = dw.reshape(dw.shape + (1, 1))
+            dws.append(dw)
+        return (None,) * 7 + tuple(dws)
+
+
 class ResNet(PreparedOperands, nn.Module):
     """``ResNet(depth, in_channels=3, stem_channels=None, base_channels=64, num_stages=4, strides=(1,2,2,2), dilations=(1,1,1,1),
     out_indices=(0,1,2,3), style='pytorch', ...)``: mmdet's keywords; registered as ``mmdet.ResNet`` and ``ResNet``.  The ``state_dict``
@@ -68,9 +152,12 @@ class ResNet(PreparedOperands, nn.Module):
     ``layer{s}.0.downsample.{0.weight,1.*}``; BatchNorm ``eps`` 1e-5.
 
     Accepted: ``depth`` 50 / 101 / 152, ``in_channels=3``, ``stem_channels`` (None: ``base_channels``) a multiple of 16 up to 64,
-    ``base_channels`` a multiple of 16 up to 64, 1 to 4 stages with mmdet's strides and no dilation.  Accepted and inert (every BatchNorm is
-    frozen in both modes, nothing is trained or initialised from a file): ``frozen_stages``, ``norm_cfg`` (``BN``), ``norm_eval``,
-    ``init_cfg``, ``with_cp``, ``zero_init_residual``.  ``NotImplementedError`` naming the keyword: ``style='caffe'``, ``deep_stem``,
+    ``base_channels`` a multiple of 16 up to 64, 1 to 4 stages with mmdet's strides and no dilation.  Accepted and, without
+    ``differentiable``, inert (every BatchNorm is frozen in both modes, nothing is initialised from a file): ``frozen_stages``,
+    ``norm_cfg`` (``BN``), ``norm_eval``, ``init_cfg``, ``with_cp``, ``zero_init_residual``.  ``differentiable`` (not one of mmdet's; last;
+    default False): train the convolution kernels of the stages ``> frozen_stages``, downsamples included -- they get
+    ``requires_grad=True``, every BatchNorm parameter and every frozen stage stays False.  It needs ``frozen_stages >= 1``,
+    ``norm_eval=True`` and ``norm_cfg=dict(type='BN', requires_grad=False)``, else ``NotImplementedError`` naming the keyword.  ``NotImplementedError`` naming the keyword: ``style='caffe'``, ``deep_stem``,
     ``avg_down``, ``dcn``, ``plugins``, ``conv_cfg``, other ``strides`` / ``dilations``, depths 18 / 34.
 
     The folded operands the launches take are prepared once per device and rebuilt when a parameter or floating-point buffer is replaced
@@ -80,7 +167,7 @@ class ResNet(PreparedOperands, nn.Module):
                  strides: Sequence[int] = (1, 2, 2, 2), dilations: Sequence[int] = (1, 1, 1, 1), out_indices: Sequence[int] = (0, 1, 2, 3),
                  style: str = "pytorch", deep_stem: bool = False, avg_down: bool = False, frozen_stages: int = -1, conv_cfg=None,
                  norm_cfg=None, norm_eval: bool = True, dcn=None, stage_with_dcn=(False, False, False, False), plugins=None,
-                 with_cp: bool = False, zero_init_residual: bool = True, pretrained=None, init_cfg=None):
+                 with_cp: bool = False, zero_init_residual: bool = True, pretrained=None, init_cfg=None, differentiable: bool = False):
         super().__init__()
         if depth in (18, 34):
             _refuse("depth", depth, "BasicBlock depths are out of scope; 50, 101 or 152")
@@ -124,6 +211,16 @@ class ResNet(PreparedOperands, nn.Module):
         self.strides, self.dilations, self.out_indices, self.style = strides[:ns], dilations[:ns], out_indices, style
         self.frozen_stages, self.norm_eval, self.with_cp, self.zero_init_residual = frozen_stages, norm_eval, with_cp, zero_init_residual
         self.stage_blocks = ARCH[depth][:ns]
+        self.differentiable = bool(differentiable)
+        if self.differentiable:
+            # what the backward does not have: the stem's and the max-pool's, a gradient to the images, a BatchNorm that trains
+            if not int(frozen_stages) >= 1:
+                _refuse("differentiable", differentiable, f"needs frozen_stages >= 1, got {frozen_stages}: the stem and the max-pool have "
+                                                          f"no backward and no gradient reaches the images")
+            if not norm_eval:
+                _refuse("differentiable", differentiable, "needs norm_eval=True: every BatchNorm is the fixed * scale + shift")
+            if norm_cfg is None or dict(norm_cfg).get("requires_grad", True):
+                _refuse("differentiable", differentiable, "needs norm_cfg=dict(type='BN', requires_grad=False): no BatchNorm parameter is trained")
         self.conv1 = nn.Conv2d(3, stem, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(stem, eps=EPS)
         inplanes = stem
@@ -139,7 +236,10 @@ class ResNet(PreparedOperands, nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
         for p in self.parameters():
-            p.requires_grad_(False)                          # always inference: every BatchNorm frozen, no convolution trained
+            p.requires_grad_(False)                          # every BatchNorm frozen; no convolution trained without differentiable
+        if self.differentiable:
+            for name in self._trainable_names():             # the kernels of the stages > frozen_stages, their downsamples included
+                self.get_parameter(name).requires_grad_(True)
 
     @property
     def out_channels(self) -> List[int]:
@@ -215,7 +315,20 @@ class ResNet(PreparedOperands, nn.Module):
         (float32 or uint8, on the device).  ``mean`` / ``std`` (3 values each): the data preprocessor's ``(x - mean) / std``, applied in
         the stem; ``bgr_to_rgb``: its channel swap, which costs nothing (the stem's weight is prepared with its input planes reversed).
         ``chunk``: images per pass (default: all, at most 4096), to bound the workspace; the result has the same bits for every
-        ``chunk``."""
+        ``chunk``.
+
+        With ``differentiable=True``, grad mode on and a trainable kernel that requires grad, the call records for autograd: the stem
+        and the frozen stages run as always, the trainable tail is ONE autograd node ``(trainable kernels...) -> (the levels of the
+        stages >= frozen_stages)`` whose forward is the same launch sequence with every block's intermediates kept -- the levels have the
+        inference forward's bits -- and whose backward is ``_Tail.backward``.  The levels of frozen stages come without ``grad_fn``; no
+        gradient is produced for ``imgs``.  ``chunk`` must then be ``None`` or at least the number of images (``ValueError``: the weight
+        gradient's bits would depend on it).  Under ``no_grad``, or when no trainable kernel requires grad, this is the inference path and
+        nothing is saved."""
+        return self._forward(imgs, mean, std, bgr_to_rgb, chunk)
+
+    def _forward(self, imgs, mean, std, bgr_to_rgb, chunk, keep=None):
+        """``forward``; ``keep`` (a list, one pass, not recording): the blocks of the stages ``>= frozen_stages`` leave their
+        intermediates in it (``relu_masks``)."""
         H, W = self._check(imgs)
         dev = self.conv1.weight.device
         if dev.type != "cuda" or not imgs.is_cuda:
@@ -223,51 +336,111 @@ class ResNet(PreparedOperands, nn.Module):
         if imgs.device != dev:
             raise ValueError(f"{WHO}: imgs on {imgs.device}, the module on {dev}")
         lead = tuple(imgs.shape[:-3])
+        x = imgs.detach().reshape((-1, 3, H, W)).contiguous()
+        N = int(x.shape[0])
+        step = MAX_IMAGES if chunk is None else int(chunk)
+        if step < 1:
+            raise ValueError(f"{WHO}: chunk must be positive, got {chunk}")
+        recording = keep is None and self._records()
+        if recording and step < N:
+            raise ValueError(f"{WHO}: chunk={chunk} below the {N} images while recording for autograd: the weight gradient is summed over "
+                             f"the pixels of one pass in chunks, so its bits would depend on chunk; pass chunk=None (or >= {N}), or "
+                             f"call under torch.no_grad()")
+        if recording and N > MAX_IMAGES:
+            raise ValueError(f"{WHO}: at most {MAX_IMAGES} images while recording for autograd, got {N}")
+        step = min(step, MAX_IMAGES, N)
         with torch.no_grad():
-            x = imgs.detach().reshape((-1, 3, H, W)).contiguous()
-            N = int(x.shape[0])
-            step = MAX_IMAGES if chunk is None else int(chunk)
-            if step < 1:
-                raise ValueError(f"{WHO}: chunk must be positive, got {chunk}")
-            step = min(step, MAX_IMAGES, N)
             prep = self._prepare(dev)
             mean_t, std_t = self._norm(prep, dev, mean, std, bgr_to_rgb)
             shapes = self.level_shapes(H, W)
             last = self.out_indices[-1]
             levels = {s: torch.empty((N,) + shapes[s], dtype=torch.float32, device=dev) for s in self.out_indices}
-            lib, st = _abi.lib(), _stream(dev)
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
             h2, w2 = ((H - 1) // 2 + 1 - 1) // 2 + 1, ((W - 1) // 2 + 1 - 1) // 2 + 1
+            # the stages that run here, outside autograd
+            frozen = min(self.frozen_stages, last + 1) if recording or keep is not None else last + 1
             for i0 in range(0, N, step):
                 n = min(step, N - i0)
-                xin = x[i0:i0 + n]
-                cur, ch, cw = new(n, self.stem_channels, h2, w2), h2, w2
-                _abi.check(lib.ptx_conv_stem(xin.data_ptr(), 1 if x.dtype == torch.uint8 else 0, n, H, W,
-                                             prep["stem_bgr" if bgr_to_rgb else "stem"].data_ptr(), self.stem_channels,
-                                             prep["bn1"][0].data_ptr(), prep["bn1"][1].data_ptr(), 1, _ptr(mean_t), _ptr(std_t),
-                                             cur.data_ptr(), st), "ptx_conv_stem")
-                for s in range(last + 1):
-                    blocks = prep["stages"][s]
-                    for b, d in enumerate(blocks):
-                        sd = d["stride"]
-                        ho, wo = (ch - 1) // sd + 1, (cw - 1) // sd + 1
-                        t1, t2 = new(n, d["planes"], ch, cw), new(n, d["planes"], ho, wo)
-                        out = levels[s][i0:i0 + n] if (b == len(blocks) - 1 and s in levels) else new(n, d["out"], ho, wo)
-                        _abi.check(lib.ptx_conv1x1(cur.data_ptr(), n, d["inplanes"], ch, cw, d["w1"].data_ptr(), d["planes"], 1,
-                                                   d["bn1"][0].data_ptr(), d["bn1"][1].data_ptr(), None, 1, t1.data_ptr(), st), "ptx_conv1x1")
-                        _abi.check(lib.ptx_conv3x3(t1.data_ptr(), n, d["planes"], ch, cw, d["w2"].data_ptr(), sd, d["bn2"][0].data_ptr(),
-                                                   d["bn2"][1].data_ptr(), None, 1, t2.data_ptr(), st), "ptx_conv3x3")
-                        idn = cur
-                        if d["wd"] is not None:
-                            idn = new(n, d["out"], ho, wo)
-                            _abi.check(lib.ptx_conv1x1(cur.data_ptr(), n, d["inplanes"], ch, cw, d["wd"].data_ptr(), d["out"], sd,
-                                                       d["bnd"][0].data_ptr(), d["bnd"][1].data_ptr(), None, 0, idn.data_ptr(), st),
-                                       "ptx_conv1x1")
-                        _abi.check(lib.ptx_conv1x1(t2.data_ptr(), n, d["planes"], ho, wo, d["w3"].data_ptr(), d["out"], 1,
-                                                   d["bn3"][0].data_ptr(), d["bn3"][1].data_ptr(), idn.data_ptr(), 1, out.data_ptr(), st),
-                                   "ptx_conv1x1")
-                        cur, ch, cw = out, ho, wo
+                cur = self._stem(prep, x[i0:i0 + n], n, H, W, h2, w2, bgr_to_rgb, mean_t, std_t)
+                cur = self._stages(prep, cur, h2, w2, 0, frozen, levels, i0)
+            if keep is not None:
+                if step < N:
+                    raise ValueError(f"{WHO}: the intermediates are kept for one pass only, got chunk={chunk} for {N} images")
+                self._stages(prep, cur, *shapes[frozen - 1][1:], frozen, last + 1, levels, 0, keep)
+        if recording and frozen <= last:
+            ch, cw = shapes[frozen - 1][1:]
+            weights = [self.get_parameter(name) for name in self._trainable_names(last + 1)]
+            tail = _Tail.apply(self, prep, cur, ch, cw, frozen, levels, *weights)
+            levels = {**levels, **dict(zip([s for s in self.out_indices if s >= frozen], tail))}
         return [levels[s].reshape(lead + tuple(levels[s].shape[1:])) for s in self.out_indices]
+
+    def _records(self) -> bool:
+        """Whether this call records for autograd: ``differentiable=True``, grad mode on, and a trainable kernel that requires grad."""
+        return (self.differentiable and torch.is_grad_enabled()
+                and any(self.get_parameter(name).requires_grad for name in self._trainable_names(self.out_indices[-1] + 1)))
+
+    def _trainable_names(self, stages: Optional[int] = None) -> List[str]:
+        return image_backbone_grad_host.trainable_kernels(self.stage_blocks[:stages], self.frozen_stages)
+
+    def _stem(self, prep, xin, n, H, W, h2, w2, bgr_to_rgb, mean_t, std_t):
+        cur = torch.empty((n, self.stem_channels, h2, w2), dtype=torch.float32, device=xin.device)
+        _abi.check(_abi.lib().ptx_conv_stem(xin.data_ptr(), 1 if xin.dtype == torch.uint8 else 0, n, H, W,
+                                            prep["stem_bgr" if bgr_to_rgb else "stem"].data_ptr(), self.stem_channels,
+                                            prep["bn1"][0].data_ptr(), prep["bn1"][1].data_ptr(), 1, _ptr(mean_t), _ptr(std_t),
+                                            cur.data_ptr(), _stream(xin.device)), "ptx_conv_stem")
+        return cur
+
+    def _stages(self, prep, cur, ch, cw, s0, s1, levels, i0, keep=None):
+        """The launches of stages ``s0 .. s1 - 1`` on ``cur (n,C,ch,cw)``; a stage in ``levels`` ends in ``levels[s][i0:i0 + n]``.  ``keep``:
+        a list that receives every block's ``(s, b, operands, x, t1, t2, idn, out)`` -- what the backward reads."""
+        dev, n = cur.device, int(cur.shape[0])
+        lib, st = _abi.lib(), _stream(dev)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+        for s in range(s0, s1):
+            blocks = prep["stages"][s]
+            for b, d in enumerate(blocks):
+                sd = d["stride"]
+                ho, wo = (ch - 1) // sd + 1, (cw - 1) // sd + 1
+                t1, t2 = new(n, d["planes"], ch, cw), new(n, d["planes"], ho, wo)
+                out = levels[s][i0:i0 + n] if (b == len(blocks) - 1 and s in levels) else new(n, d["out"], ho, wo)
+                _abi.check(lib.ptx_conv1x1(cur.data_ptr(), n, d["inplanes"], ch, cw, d["w1"].data_ptr(), d["planes"], 1,
+                                           d["bn1"][0].data_ptr(), d["bn1"][1].data_ptr(), None, 1, t1.data_ptr(), st), "ptx_conv1x1")
+                _abi.check(lib.ptx_conv3x3(t1.data_ptr(), n, d["planes"], ch, cw, d["w2"].data_ptr(), sd, d["bn2"][0].data_ptr(),
+                                           d["bn2"][1].data_ptr(), None, 1, t2.data_ptr(), st), "ptx_conv3x3")
+                idn = cur
+                if d["wd"] is not None:
+                    idn = new(n, d["out"], ho, wo)
+                    _abi.check(lib.ptx_conv1x1(cur.data_ptr(), n, d["inplanes"], ch, cw, d["wd"].data_ptr(), d["out"], sd,
+                                               d["bnd"][0].data_ptr(), d["bnd"][1].data_ptr(), None, 0, idn.data_ptr(), st),
+                               "ptx_conv1x1")
+                _abi.check(lib.ptx_conv1x1(t2.data_ptr(), n, d["planes"], ho, wo, d["w3"].data_ptr(), d["out"], 1,
+                                           d["bn3"][0].data_ptr(), d["bn3"][1].data_ptr(), idn.data_ptr(), 1, out.data_ptr(), st),
+                           "ptx_conv1x1")
+                if keep is not None:
+                    keep.append((s, b, d, cur, t1, t2, idn, out))
+                cur, ch, cw = out, ho, wo
+        return cur
+
+    def relu_masks(self, imgs: torch.Tensor, *, mean=None, std=None, bgr_to_rgb: bool = False) -> dict:
+        """``{"layer{s}.{b}.t1" / ".t2" / ".out": [. > 0]}`` (numpy bool) of every block of the stages ``>= frozen_stages`` in the device's
+        own forward: what ``grad_host(..., masks=)`` replays when a device backward is compared with the host's."""
+        keep: list = []
+        self._forward(imgs, mean, std, bgr_to_rgb, None, keep)
+        masks = {}
+        for s, b, _, _, t1, t2, _, out in keep:
+            for name, t in (("t1", t1), ("t2", t2), ("out", out)):
+                masks[f"layer{s + 1}.{b}.{name}"] = (t > 0).cpu().numpy()
+        return masks
+
+    def grad_host(self, imgs, grads, dtype=np.float64, masks=None, mean=None, std=None, bgr_to_rgb: bool = False) -> dict:
+        """``{kernel name: d loss / d kernel}`` of every trainable kernel, in numpy ``dtype``, for the gradients ``grads`` of the
+        ``out_indices`` levels (``image_backbone_grad_host.resnet_grad_host``): the specification of the recorded backward.  It calls no
+        device code.  ``masks``: ``relu_masks``'s, to replay a device forward's ReLU decisions."""
+        x = _np(imgs)
+        params = {k: _np(v) for k, v in self.state_dict().items()}
+        gs = [_np(g).reshape((-1,) + tuple(_np(g).shape[-3:])) for g in grads]
+        return image_backbone_grad_host.resnet_grad_host(params, x.reshape((-1,) + x.shape[-3:]),  gs,
+                                                         self.stage_blocks[:self.out_indices[-1] + 1], self.strides, self.out_indices,
+                                                         self.frozen_stages, dtype, masks, mean, std, bgr_to_rgb)
 
     def forward_host(self, imgs, dtype=np.float64, mean=None, std=None, bgr_to_rgb: bool = False) -> List[np.ndarray]:
         """The same chain in numpy ``dtype`` (``image_backbone_host.resnet_host``): the specification.  It calls no device code."""
